@@ -9,7 +9,11 @@ GPU is fixed; --batch-total T: strong scaling, T / N per GPU -- the form BASELIN
 configs 4 and 5 in) with no data-path collective; the trajectory chunk [K, B, 13 Nb] of the timed rollout is all-gathered
 once over RCCL inside the timed region (north_star: "RCCL all-gather of trajectories").
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline line
+(value, ms_per_step, ...).  --full adds everything else this benchmark measures, each in runs of its own after the
+timed region: the joined-per-step leg, the one-launch-per-kernel roofline leg, gradient parity against the CPU oracle,
+the CPU baseline and, for N > 1, the ranks' devices and slices.  --dump-outputs DIR writes what the timed path returned
+in its last step (next states, status, Newton iterations, gradients) as DIR/<name>.npy, for comparing two builds.
 """
 import argparse
 import ctypes as C
@@ -23,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "dojo.jl_amd", "host"))
 
 HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_VECTOR_PEAK_TFLOPS = 78.6   # MI355X vector fp64: half the 157.3 TFLOP/s fp32 vector peak of the guide (32 flop/clk/SIMD; tools/ubench/valu_rate.hip measures one fp64 FMA per 4.5 cycles and wave)
+DUMP_LIMIT = 48 << 20            # --dump-outputs: bytes written at most, all ranks together
 
 
 def main():
@@ -53,6 +58,10 @@ def main():
     ap.add_argument("--refine", type=float, default=None, help="stiffness threshold of the solve refinement (dojo_set_refinement); default: the library's")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1: nccl (= RCCL, production) or gloo "
                     "(plumbing check of the N > 1 path on a box with fewer GPUs than ranks: ranks share devices, the gather goes through the host)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also the joined-per-step leg, the one-launch-per-kernel roofline leg, "
+                    "the parity leg, the CPU baseline and the ranks' devices / slices; off: only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed path's outputs of its last step as DIR/<name>.npy "
+                    "(float32 / float64; a fixed, seeded sample of the environments where all of them would exceed %d MiB over all ranks)" % (DUMP_LIMIT >> 20))
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher: spawn the N ranks here (one process per GPU; the same command line under
@@ -201,12 +210,55 @@ def main():
     ok_frac = float((status == 0).float().mean().item())          # of the timed region's last step
     mean_iters = float(iters.float().mean().item())
     z = traj[K - 1].clone()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"next_state": z, "status": status, "iters": iters, "dz": dz, "du": du}, DUMP_LIMIT // world)
     if args.timed_only:
         if rank == 0:
             print(json.dumps({"metric": "differentiable env-steps/sec (fwd+grad) at batch=4096; grad inf-err vs CPU", "value": world * B * K / el, "unit": "env-steps/s", "n_gpus": world,
                               "steps": K, "warmup": W, "ms_per_step": 1e3 * el / K, "note": "--timed-only: warmup + timed region (profiling runs)"}), flush=True)
         if world > 1:
             dist.destroy_process_group()
+        return
+
+    def headline(extra_config=None):
+        """the result line of the timed region: its figure and what it was measured on (extra_config: entries of the --full legs)"""
+        res = {
+            "metric": "differentiable env-steps/sec (fwd+grad) at batch=4096; grad inf-err vs CPU" if grad else "env-steps/sec (fwd only)",
+            "value": world * B * K / el, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": 1e3 * el / K, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": (("BASELINE.json configs[2]: Ant (13 bodies as built by the reference, 8 revolute+limits, 4 fixed, 4 foot contacts), "
+                                     if args.config == 3 else "BASELINE.json configs[%d]: %s (%d bodies, %d contacts), " % (args.config - 1, spec.name, spec.Nb, len(spec.contacts)))
+                                    + ("total batch %d sharded over %d GPU(s) = %d per GPU (strong scaling), " % (world * B, world, B) if strong else "batch=%d per GPU, " % B)
+                                    + "%s, closed-loop rollout with random controls" % ("fwd + IFT gradients" if grad else "forward only")),
+                       "per_rank_batch": B, "total_batch": world * B,
+                       "input_distribution": args.distribution + (" (BASELINE.md section 3: height U(0, 0.3), rotation N(0, 0.1), velocities N(0, 0.5), joints +-0.2)" if args.distribution == "baseline"
+                                                                   else " (Atlas: around the reference's standing pose, dojo_amd.coords._SYNTH_STANDING; other mechanisms as baseline)"),
+                       "io_dtype": args.io_dtype, "arithmetic": "fp64 state/residual/factorization, %s buffers at the ABI" % args.io_dtype,
+                       "solver_options": "reference defaults (rtol 1e-6, btol 1e-4, max_iter 50, max_ls 10)",
+                       "parallelism": "batch-sharded x%d, no data-path collective; per GPU ONE handle, dojo_step_dev steps its batch as %d environment groups on internal HIP streams (asynchronous, one join per rollout%s)" % (world, NCH, "; pipelined: a group's IFT kernel of step k next to its step kernel of step k + 1" if args.pipeline else ""),
+                       "dispatch_order": {0: "batch order", 1: "library default: joined steps (the sync_per_step and single_launch legs) hand out the previous step's longest solves first; the asynchronous timed region runs in batch order", 2: "longest solves of the previous step first, in every leg"}[args.dispatch_order],
+                       "iteration_cap": "off (library default; dojo_set_iteration_cap: measured gain only at per-GPU batches <= 2048, DESIGN.md section 6)" if args.iter_cap <= 0 else args.iter_cap,
+                       "converged_fraction_last_step": ok_frac, "mean_newton_iters_last_step": mean_iters,
+                       **(extra_config or {}),
+                       "build": build_info()},
+        }
+        if world > 1:
+            res["config"]["trajectory_gather"] = {"what": "the timed rollout's states [K=%d, B=%d, 13 Nb=%d] of every rank, once, inside the timed region" % (K, B, 13 * spec.Nb),
+                                                 "bytes_received_per_rank": gathered_bytes,
+                                                 "through": "dojo_allgather_dev (the library's RCCL communicator)" if lib_gather else "torch.distributed all_gather (RCCL)"}
+        return res
+
+    def leave():
+        if world > 1:
+            if lib_stuck:                            # a thread is still inside the library's communicator set-up: leave without the teardown that would wait for it
+                sys.stdout.flush(); sys.stderr.flush(); os._exit(0)
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        leave()
         return
     rank_devices = None
     if world > 1:                                 # which device every rank ran on (rank 0 prints it)
@@ -312,29 +364,9 @@ def main():
                              "region's K steps replayed after it (same states, same controls); the HBM roofline the contract asks for is the `hbm` member")}
         if any(r_.get("warning") for r_ in parts):
             roofline["warning"] = next(r_["warning"] for r_ in parts if r_.get("warning"))
-        res = {
-            "metric": "differentiable env-steps/sec (fwd+grad) at batch=4096; grad inf-err vs CPU" if grad else "env-steps/sec (fwd only)",
-            "value": world * B * K / el, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": 1e3 * el / K, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": (("BASELINE.json configs[2]: Ant (13 bodies as built by the reference, 8 revolute+limits, 4 fixed, 4 foot contacts), "
-                                     if args.config == 3 else "BASELINE.json configs[%d]: %s (%d bodies, %d contacts), " % (args.config - 1, spec.name, spec.Nb, len(spec.contacts)))
-                                    + ("total batch %d sharded over %d GPU(s) = %d per GPU (strong scaling), " % (world * B, world, B) if strong else "batch=%d per GPU, " % B)
-                                    + "%s, closed-loop rollout with random controls" % ("fwd + IFT gradients" if grad else "forward only")),
-                       "per_rank_batch": B, "total_batch": world * B,
-                       "input_distribution": args.distribution + (" (BASELINE.md section 3: height U(0, 0.3), rotation N(0, 0.1), velocities N(0, 0.5), joints +-0.2)" if args.distribution == "baseline"
-                                                                   else " (Atlas: around the reference's standing pose, dojo_amd.coords._SYNTH_STANDING; other mechanisms as baseline)"),
-                       "io_dtype": args.io_dtype, "arithmetic": "fp64 state/residual/factorization, %s buffers at the ABI" % args.io_dtype,
-                       "solver_options": "reference defaults (rtol 1e-6, btol 1e-4, max_iter 50, max_ls 10)",
-                       "parallelism": "batch-sharded x%d, no data-path collective; per GPU ONE handle, dojo_step_dev steps its batch as %d environment groups on internal HIP streams (asynchronous, one join per rollout%s)" % (world, NCH, "; pipelined: a group's IFT kernel of step k next to its step kernel of step k + 1" if args.pipeline else ""),
-                       "dispatch_order": {0: "batch order", 1: "library default: joined steps (the sync_per_step and single_launch legs) hand out the previous step's longest solves first; the asynchronous timed region runs in batch order", 2: "longest solves of the previous step first, in every leg"}[args.dispatch_order],
-                       "iteration_cap": "off (library default; dojo_set_iteration_cap: measured gain only at per-GPU batches <= 2048, DESIGN.md section 6)" if args.iter_cap <= 0 else args.iter_cap,
-                       "converged_fraction_last_step": ok_frac, "mean_newton_iters_last_step": mean_iters,
-                       "sync_per_step_value": world * B * K / el_sync, "sync_per_step_ms": 1e3 * el_sync / K,
-                       "sync_per_step_note": "%d more steps of the rollout (the same controls again, from the timed region's end state) with the environment groups joined into the caller's stream after every step (a barrier per step); `value` is the asynchronous rollout (one join at the end)" % K,
-                       "build": build_info()},
-            "roofline": roofline,
-        }
+        res = headline({"sync_per_step_value": world * B * K / el_sync, "sync_per_step_ms": 1e3 * el_sync / K,
+                        "sync_per_step_note": "%d more steps of the rollout (the same controls again, from the timed region's end state) with the environment groups joined into the caller's stream after every step (a barrier per step); `value` is the asynchronous rollout (one join at the end)" % K})
+        res["roofline"] = roofline
         if grad and not args.no_parity and world == 1:
             res["grad_inf_err_vs_cpu"] = pv = parity_vs_cpu(spec, B, local, args.distribution)
             # the norm the metric's second half is claimed in, at the top level: RELATIVE per-environment inf-norm, the absolute one next to it
@@ -369,16 +401,32 @@ def main():
                                                      "executed: the reference's generic small-matrix products cost several times the flops of the device's closed forms, so this ratio is an UPPER "
                                                      "estimate of the useful share (the device's redundancy -- four lanes evaluate every joint -- is in the denominator, its cheaper formulas are not in the numerator)"}
         if world > 1:
-            res["config"]["trajectory_gather"] = {"what": "the timed rollout's states [K=%d, B=%d, 13 Nb=%d] of every rank, once, inside the timed region" % (K, B, 13 * spec.Nb),
-                                                 "bytes_received_per_rank": gathered_bytes,
-                                                 "through": "dojo_allgather_dev (the library's RCCL communicator)" if lib_gather else "torch.distributed all_gather (RCCL)"}
             res["config"]["rank_devices"] = rank_devices
             res["config"]["rank_slices"] = rank_slices        # (strong scaling: rank r = environments [r B, (r + 1) B) of the one batch_total-environment batch)
         print(json.dumps(res), flush=True)
-    if world > 1:
-        if lib_stuck:                            # a thread is still inside the library's communicator set-up: leave without the teardown that would wait for it
-            sys.stdout.flush(); sys.stderr.flush(); os._exit(0)
-        dist.destroy_process_group()
+    leave()
+
+
+def dump_outputs(dirname, rank, arrays, limit):
+    """--dump-outputs: the timed path's outputs of its last step, one DIR/<name>.npy each (rank r > 0: <name>.rank<r>.npy).  Every
+    array has the batch as its leading axis; floating arrays keep the ABI's dtype, integer ones (status, iterations) become float64.
+    Where the rank's whole batch would exceed `limit` bytes (its share of DUMP_LIMIT), every array holds the same fixed, seeded
+    sample of environments, in batch order, and envs.npy lists them."""
+    import numpy as np
+    import torch
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    arrays = {k: (v if v.is_floating_point() else v.to(torch.float64)) for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    per_env = sum(v[0].numel() * v.element_size() for v in arrays.values())
+    idx = None
+    if B * per_env > limit:
+        n = max(1, limit // per_env)
+        idx = np.sort(np.random.default_rng(20241008).choice(B, n, replace=False))
+        arrays = {k: v[torch.as_tensor(idx, device=v.device)] for k, v in arrays.items()}
+        arrays["envs"] = torch.as_tensor(idx, dtype=torch.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + (".rank%d" % rank if rank else "") + ".npy"), v.cpu().numpy())
 
 
 def spawn_ranks(n, backend):
