@@ -66,6 +66,32 @@ struct DevBuf {
     DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
 };
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return DOJO_ERR_DEVICE; } } while (0)
+#define TRY(x) do { int rc_ = (x); if (rc_ != DOJO_OK) return rc_; } while (0)      // (a failing call of the library's own has set the error text)
+
+// A step with the iteration cap in force (dojo_set_iteration_cap) is launched in phases: the step kernel of every environment group
+// (PH_MAIN), each followed on its stream by the IFT kernel of the workgroups it finished (PH_GRAD); behind the step kernels of ALL groups,
+// on a stream of its own, the continuation of the listed workgroups and their IFT (PH_CONT, once over the whole batch).  PH_ALL = no cap:
+// step kernel + IFT kernel in one go.
+enum { PH_ALL = 0, PH_MAIN = 1, PH_GRAD = 2, PH_CONT = 3 };
+// What a launch of the step (and IFT) kernels is told: the caller's batch-level device buffers (null = not wanted; the solution buffers are the handle's),
+// the environments [env0, env0 + nenv) and their stream (env0: a multiple of the environments per wavefront), and how the kernels are run
+struct StepIO { const void *z, *u; void* z_next; int *status, *iters; void *dz, *du, *dc, *storage; };
+struct Span { size_t env0; int nenv; hipStream_t stream; };
+struct Mode {
+    int phase;
+    int* slot;                         // timed launches: where a PH_ALL / PH_MAIN launch puts the timing slot it took, and the PH_GRAD launch of the same group finds it; null = not timed
+    bool cap_lists, chained;           // phased launches: with the iteration cap's lists (pipelined groups launch the two kernels apart without them); one of a group's steps launched back to back (rollout_core)
+    size_t groups; int rec;            // environment groups of the step this launch belongs to; the step -> IFT hand-off record in use (DojoSim::sol_cur: state between calls -- a launch is told it)
+    Mode with(int phase_, int* slot_) const { Mode m = *this; m.phase = phase_; m.slot = slot_; return m; }
+};
+// the environment groups of a batch: NG groups of `per` environments (a multiple of 64: whole wavefronts for every mapping), the last ones shorter or empty
+struct Partition {
+    size_t B, NG, per;
+    explicit Partition(size_t B_ = 0, size_t NG_ = 1) : B(B_), NG(NG_), per(((B_ + NG_ - 1) / NG_ + 63) / 64 * 64) {}
+    size_t groups() const { return std::min(NG, (B + per - 1) / per); }      // the non-empty ones
+    Span span(size_t gi, hipStream_t st) const { return Span{gi * per, (int)std::min(per, B - gi * per), st}; }
+    bool operator!=(const Partition& o) const { return NG != o.NG || per != o.per; }
+};
 
 } // namespace
 
@@ -93,8 +119,8 @@ struct DojoSim {
     int async = 0; bool pending = false;   // dojo_set_async: 1 = dojo_step_dev returns without joining the groups into the caller's stream; 2 = ... and the IFT of a
                                         // group's step runs on a second stream of the group, next to its NEXT step kernel (two hand-off records in turn)
     std::vector<hipStream_t> gstreams2; std::vector<hipEvent_t> gevents2, grad_done[2];   // pipelined groups: the IFT streams, their join events, "IFT that read record p is through"
-    void* d_sol2 = nullptr; int sol_cur = 0; bool plain_phases = false;                   // the second hand-off record; the one in use; phased launches without the iteration cap's lists
-    size_t last_NG = 0, last_per = 0;      // environment-group partition of the last grouped dojo_step_dev (per-group chaining assumes it repeats)
+    void* d_sol2 = nullptr; int sol_cur = 0;                                              // the second hand-off record; the one in use
+    Partition last_part;                   // environment-group partition of the last grouped dojo_step_dev (per-group chaining assumes it repeats)
     void* d_sol = nullptr;              // step kernel -> IFT kernel hand-off (converged solution, fp64)
     void* d_fac = nullptr;              // ... and the final supernode factors (quad mapping; explicit-inverse consumers only)
     void* d_lu = nullptr;               // the IFT kernel's LU-form factors between its phases (quad mapping)
@@ -112,11 +138,11 @@ struct DojoSim {
     hipStream_t cstream = nullptr; hipEvent_t cont_event = nullptr, allmain_event = nullptr; std::vector<hipEvent_t> main_events;   // the continuation's stream; "step kernel done" per group
     // dispatch order of the step kernel (dojo_set_dispatch_order): 0 off, 1 where a launch has more workgroups than the GPU holds at once and the step is
     // joined into the caller's stream (the step then waits for its last wavefront), 2 always
-    int dispatch_mode = 1, sm_count = 0; size_t step_groups = 1; bool chained_now = false;      // step_groups: groups of the dojo_step_dev in progress;      // chained_now: launches of rollout_core (one group's steps back to back)
+    int dispatch_mode = 1, sm_count = 0;
     int *d_dispatch = nullptr, *d_liters = nullptr;        // [workgroups of the batch] the permutations, one segment per launch; [B] iteration counts when the caller passes no buffer
     std::map<size_t, int> dispatch_have;                   // first workgroup of a segment -> environments of the launch whose permutation it holds
-    int phase_slot = -1;                // timing slot of the phased launch in progress (PH_MAIN -> PH_GRAD of the same group)
-    std::vector<int> group_slot;        // ... per environment group
+    std::vector<int> group_slot;        // timing slot of the phased launches of an environment group (PH_MAIN -> PH_GRAD)
+    std::vector<void*> owned;           // device memory of this handle (ensure), freed by dojo_destroy
     bool have_grad = false, have_solution = false, have_u = false;
     std::string err; std::mutex err_m;  // text of the last failure of a call on this handle (dojo_handle_error)
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;   // RCCL communicator of this handle's process group (dojo_comm_init)
@@ -371,6 +397,15 @@ __global__ void __launch_bounds__(1024) dispatch_order_kernel(const int* iters, 
 }
 } // namespace ckern
 
+// device memory of the handle, allocated on first use and freed with the handle
+int ensure(DojoSim* s, void** p, size_t bytes) {
+    if (*p) return DOJO_OK;
+    HIPCHK(hipMalloc(p, bytes ? bytes : 8));
+    s->owned.push_back(*p);
+    return DOJO_OK;
+}
+#define ENSURE(p, ...) TRY(ensure(s, (void**)&(p), (__VA_ARGS__)))
+
 template <class T>
 int upload_tables(DojoSim* s) {   // tables are stored in the state precision (fp64)
     std::vector<dj::NodeP<T>> nodes; for (auto& n : s->M.nodes) nodes.push_back(dj::cast_node<T>(n));
@@ -379,42 +414,37 @@ int upload_tables(DojoSim* s) {   // tables are stored in the state precision (f
     { dj::NodeP<T> idle = nodes[0]; idle.ncontact = 0; for (int i = 0; i < 8; ++i) idle.contact[i] = 0; nodes.push_back(idle); }
     std::vector<dj::ContactP<T>> contacts; for (auto& c : s->M.contacts) contacts.push_back(dj::cast_contact<T>(c));
     if (contacts.empty()) contacts.push_back(dj::ContactP<T>());
-    HIPCHK(hipMalloc(&s->d_nodes, nodes.size() * sizeof(dj::NodeP<T>)));
-    HIPCHK(hipMalloc(&s->d_contacts, contacts.size() * sizeof(dj::ContactP<T>)));
+    ENSURE(s->d_nodes, nodes.size() * sizeof(dj::NodeP<T>));
+    ENSURE(s->d_contacts, contacts.size() * sizeof(dj::ContactP<T>));
     HIPCHK(hipMemcpy(s->d_nodes, nodes.data(), nodes.size() * sizeof(dj::NodeP<T>), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->d_contacts, contacts.data(), contacts.size() * sizeof(dj::ContactP<T>), hipMemcpyHostToDevice));
     if (s->M.has_tsd) {
         std::vector<dj::TraSD<T>> tsd;
         for (auto& a : s->M.tsd) { dj::TraSD<T> b; b.spring = T(a.spring); b.damper = T(a.damper); for (int i = 0; i < 3; ++i) b.off[i] = T(a.off[i]); b.lim_lo = T(a.lim_lo); b.lim_hi = T(a.lim_hi); b.nlim = a.nlim; tsd.push_back(b); }
-        HIPCHK(hipMalloc(&s->d_tsd, tsd.size() * sizeof(dj::TraSD<T>)));
+        ENSURE(s->d_tsd, tsd.size() * sizeof(dj::TraSD<T>));
         HIPCHK(hipMemcpy(s->d_tsd, tsd.data(), tsd.size() * sizeof(dj::TraSD<T>), hipMemcpyHostToDevice));
     }
     if (s->M.has_cut) {
         std::vector<dj::NodeP<T>> cn; for (auto& n_ : s->M.cuts) cn.push_back(dj::cast_node<T>(n_));
-        HIPCHK(hipMalloc(&s->d_cuts, cn.size() * sizeof(dj::NodeP<T>)));
+        ENSURE(s->d_cuts, cn.size() * sizeof(dj::NodeP<T>));
         HIPCHK(hipMemcpy(s->d_cuts, cn.data(), cn.size() * sizeof(dj::NodeP<T>), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc(&s->d_cutws, (size_t)s->B * dj::CUTWS * sizeof(T)));
+        ENSURE(s->d_cutws, (size_t)s->B * dj::CUTWS * sizeof(T));
     }
     if (s->M.has_mlim) {
         std::vector<dj::MLimP<T>> ml;
         for (auto& a : s->M.mlim) { dj::MLimP<T> b; b.nt = a.nt; b.nr = a.nr; for (int i = 0; i < 6; ++i) { b.lo[i] = T(a.lo[i]); b.hi[i] = T(a.hi[i]); } ml.push_back(b); }
-        HIPCHK(hipMalloc(&s->d_mlim, ml.size() * sizeof(dj::MLimP<T>)));
+        ENSURE(s->d_mlim, ml.size() * sizeof(dj::MLimP<T>));
         HIPCHK(hipMemcpy(s->d_mlim, ml.data(), ml.size() * sizeof(dj::MLimP<T>), hipMemcpyHostToDevice));
     }
     std::vector<int> order;
     for (int lev = 0; lev <= s->M.maxlevel; ++lev) for (int b = 0; b < s->M.Nb; ++b) if (s->M.nodes[b].level == lev) order.push_back(b);
-    HIPCHK(hipMalloc((void**)&s->d_order, order.size() * sizeof(int)));
+    ENSURE(s->d_order, order.size() * sizeof(int));
     HIPCHK(hipMemcpy(s->d_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
     return DOJO_OK;
 }
 
 int mapping_waves(const dj::HostModel& M);
 bool quad_mapping_of(const DojoSim* s);
-// A step with the iteration cap in force (dojo_set_iteration_cap) is launched in phases: the step kernel of every environment group
-// (PH_MAIN), each followed on its stream by the IFT kernel of the workgroups it finished (PH_GRAD); behind the step kernels of ALL groups,
-// on a stream of its own, the continuation of the listed workgroups and their IFT (PH_CONT, once over the whole batch).  PH_ALL = no cap:
-// step kernel + IFT kernel in one go.
-enum { PH_ALL = 0, PH_MAIN = 1, PH_GRAD = 2, PH_CONT = 3 };
 // wavefronts per workgroup of the quad mapping for this mechanism; 0 = lane mapping
 int mapping_waves(const dj::HostModel& M) {
     // translational springs / dampers / limits: the quad builds that carry them are the single-wavefront ones with <= 4 contacts per body;
@@ -521,7 +551,7 @@ int ensure_pipe(DojoSim* s, size_t NG) {
     while (s->grad_done[0].size() < NG)
         for (int p = 0; p < 2; ++p) { hipEvent_t dev_; HIPCHK(hipEventCreateWithFlags(&dev_, hipEventDisableTiming)); s->grad_done[p].push_back(dev_); }
     while (s->main_events.size() < NG) { hipEvent_t ev_; HIPCHK(hipEventCreateWithFlags(&ev_, hipEventDisableTiming)); s->main_events.push_back(ev_); }
-    if (!s->d_sol2) HIPCHK(hipMalloc(&s->d_sol2, (size_t)s->B * s->M.S * dj::sol_record<8, true>() * sizeof(double)));
+    ENSURE(s->d_sol2, (size_t)s->B * s->M.S * dj::sol_record<8, true>() * sizeof(double));
     return DOJO_OK;
 }
 // the caller's stream waits for everything the environment groups have in flight
@@ -558,211 +588,316 @@ int begin_capped_step(DojoSim* s, size_t NG, hipStream_t st) {
     if (!s->allmain_event) HIPCHK(hipEventCreateWithFlags(&s->allmain_event, hipEventDisableTiming));
     if (!s->cont_event) HIPCHK(hipEventCreateWithFlags(&s->cont_event, hipEventDisableTiming));
     while (s->main_events.size() < NG) { hipEvent_t ev_; HIPCHK(hipEventCreateWithFlags(&ev_, hipEventDisableTiming)); s->main_events.push_back(ev_); }
-    if (!s->d_cont_list) {
-        const int NW = mapping_waves(s->M), E = 64 * NW / (s->M.S * 4);
-        HIPCHK(hipMalloc((void**)&s->d_cont_list, (((size_t)s->B + E - 1) / E + 1) * sizeof(int))); HIPCHK(hipMalloc((void**)&s->d_cont_count, sizeof(int)));
-    }
+    const int NW = mapping_waves(s->M), E = 64 * NW / (s->M.S * 4);
+    ENSURE(s->d_cont_list, (((size_t)s->B + E - 1) / E + 1) * sizeof(int)); ENSURE(s->d_cont_count, sizeof(int));
     HIPCHK(hipMemsetAsync(s->d_cont_count, 0, sizeof(int), st));
     return DOJO_OK;
 }
 
-// Launches the step (and IFT) kernels for the environments [env0, env0 + nenv) of the batch; all pointers are the
-// batch-level buffers.  env0 must be a multiple of the environments per wavefront.
-template <class TIO, class T, class TL>
-int launch(DojoSim* s, const void* z, const void* u, void* zn, int* status, int* iters, void* vel, void* jimp, void* csg,
-           void* dz, void* du, hipStream_t st, bool timed, size_t env0 = 0, int nenv = -1, void* dc = nullptr, void* storage = nullptr, int phase = PH_ALL) {
-    if (nenv < 0) nenv = s->B;
-    const size_t Nb = s->M.Nb, nu = s->M.nu, nx = 12 * Nb;
+// One step launch, by job: refusals, the kernel build, workspaces, kernel arguments, timing, the kernels behind the step.  First what the kernels do not
+// compute: it depends on the handle and on what is asked for (dz / du, or dc), not on the environments of a launch -- an entry point asks once, before it enqueues anything.
+int refuse_unsupported(const DojoSim* s, bool want_dz, bool want_dc) {
+    const size_t Nb = s->M.Nb, nu = s->M.nu;
+    const bool g = want_dz || want_dc, quad = quad_mapping_of(s);
+    if (g && (s->M.has_ss || s->M.has_cc)) { g_err = "gradients are not available for mechanisms with a body-body contact"; return DOJO_ERR_UNSUPPORTED; }
+    if (g && s->M.contact_model != 0) {   // the reference has no data Jacobians for ImpactContact / LinearContact either (src/gradients/data.jl:152-192 are NonlinearContact methods)
+        g_err = "gradients are not available for ImpactContact / LinearContact mechanisms"; return DOJO_ERR_UNSUPPORTED;
+    }
+    if (g && quad && std::max<size_t>(2 * Nb + (nu + 5) / 6, want_dc ? (size_t)s->M.Nc : 0) > 128) {
+        // (dojo_device.hpp, gradient_columns_quad: the branch schedule keeps batch sets in two 64-bit words; unreachable with <= 32 bodies -- 2 x 32 + 32 --
+        //  but a mapping change must not turn it into silently aliased batches)
+        g_err = "the IFT sweeps support at most 128 column batches per environment"; return DOJO_ERR_UNSUPPORTED;
+    }
+    if (want_dc && s->M.Nc > 64) {  // the sweeps' batch masks hold one bit per contact of the environment (dojo_device.hpp, sweep_masks)
+        g_err = "contact-data gradients support at most 64 contacts per environment"; return DOJO_ERR_UNSUPPORTED;
+    }
+    if (want_dc && !quad) { g_err = "contact-data gradients need the quad mapping (<= 32 bodies)"; return DOJO_ERR_UNSUPPORTED; }
+    return DOJO_OK;
+}
+
+// The kernel builds (one object file of dojo_kernels.hip each): family x contacts-per-body bound (MAXC) x mapping (wavefronts per workgroup of the quad
+// mapping, 0 = lane mapping), the launchers of both ABI types as [f64, f32].  sol_rec: doubles per supernode of the build's step -> IFT hand-off record.
+typedef int (*launcher_t)(const void*, int, void*, int, void*); typedef int (*claunch_t)(const void*, int, void*);
+enum { FAM_PLAIN, FAM_TSD, FAM_GEN, FAM_LIN, FAM_SS };
+struct Variant { int family, maxc, waves; launcher_t step[2]; claunch_t cgrad[2]; size_t sol_rec; };
+#define DJ_V(fam, pre, mc, nw, rec) {fam, mc, nw, {dojo_launch_##pre##double_##mc##_##nw, dojo_launch_##pre##float_##mc##_##nw}, {nullptr, nullptr}, (size_t)rec}
+#define DJ_VC(fam, pre, mc, nw) {fam, mc, nw, {dojo_launch_##pre##double_##mc##_##nw, dojo_launch_##pre##float_##mc##_##nw}, \
+                                 {dojo_launch_cgrad_##pre##double_##mc##_##nw, dojo_launch_cgrad_##pre##float_##mc##_##nw}, (size_t)dj::sol_record<mc>()}
+const Variant g_variants[] = {        // (rows of one family and mapping: MAXC ascending)
+    DJ_VC(FAM_PLAIN, , 1, 1), DJ_VC(FAM_PLAIN, , 4, 1), DJ_VC(FAM_PLAIN, , 8, 1), DJ_VC(FAM_PLAIN, , 1, 2), DJ_VC(FAM_PLAIN, , 4, 2), DJ_V(FAM_PLAIN, , 4, 0, dj::sol_record<4>()), DJ_V(FAM_PLAIN, , 8, 0, dj::sol_record<8>()),
+    DJ_VC(FAM_TSD, tsd_, 1, 1), DJ_VC(FAM_TSD, tsd_, 4, 1), DJ_V(FAM_TSD, tsd_, 4, 0, dj::sol_record<4>()), DJ_V(FAM_TSD, tsd_, 8, 0, dj::sol_record<8>()),
+    DJ_V(FAM_GEN, gen_, 4, 0, (dj::sol_record<4, true>())), DJ_V(FAM_GEN, gen_, 8, 0, (dj::sol_record<8, true>())),
+    DJ_V(FAM_LIN, lin_, 1, 1, dj::sol_record<1>()), DJ_V(FAM_LIN, lin_, 4, 1, dj::sol_record<4>()), DJ_V(FAM_LIN, lin_, 4, 0, dj::sol_record<4>()), DJ_V(FAM_LIN, lin_, 8, 0, dj::sol_record<8>()),
+    DJ_V(FAM_SS, ss_, 1, 1, dj::sol_record<1>())};
+// the build that serves a mechanism under the mapping NW (mapping_waves): of its family and mapping, the smallest MAXC that holds its contacts per body
+// (the largest where none does); null: no such build
+const Variant* variant_of(const dj::HostModel& M, int NW) {
+    const int fam = (M.has_ss && M.contact_model != 2) ? FAM_SS : M.contact_model == 2 ? FAM_LIN : (M.has_mlim || M.has_cut) ? FAM_GEN : M.has_tsd ? FAM_TSD : FAM_PLAIN;
+    const Variant* v = nullptr;
+    for (const Variant& r : g_variants) if (r.family == fam && r.waves == NW && (!v || v->maxc < M.maxc)) v = &r;
+    return v;
+}
+
+// How a span maps onto workgroups.  Four lanes per supernode when the mechanism has <= 16 bodies (one Ant per wavefront) or <= 32 bodies (one Atlas per
+// two-wavefront workgroup; contact rows pooled per contact: <= 16 contacts, <= 4 per body); else one lane per supernode.
+struct Geometry {
+    int NW; bool quad; int E; size_t lanes;     // wavefronts per workgroup (0: lane mapping); environments and lanes per workgroup
+    size_t grid, waves_total, wave0;            // workgroups of the span, of the batch, in front of the span
+    long long ypark_stride, msg_stride;         // elements per workgroup / per environment of the IFT's parking and message buffers (0: not used)
+};
+Geometry geometry_of(const DojoSim* s, const Span& sp, bool g) {
+    const int NW = mapping_waves(s->M), E = 64 * (NW > 0 ? NW : 1) / (s->M.S * (NW > 0 ? 4 : 1));
+    Geometry ge{NW, NW > 0, E, (size_t)64 * NW, (size_t)(sp.nenv + E - 1) / E, ((size_t)s->B + E - 1) / E, sp.env0 / E, 0, 0};
+    if (g && ge.quad) {                         // (dojo_device.hpp, gradient_columns_quad)
+        const size_t batches = std::max<size_t>(2 * s->M.Nb + (s->M.nu + 5) / 6, (size_t)s->M.Nc);     // state + control batches | contact batches (dojo_cgrad_kernel)
+        if (s->w < sizeof(double)) ge.ypark_stride = (long long)(batches * 18 * ge.lanes);      // fp32 ABI: all four roles park (LU-form sweeps)
+        size_t ntops = 0; for (auto& n_ : s->M.nodes) if (n_.level <= 1) ++ntops;      // one block per level-1 supernode (messages) and per root (its Δv, Δω)
+        ge.msg_stride = (long long)(ntops * batches * 36 + 8);      // what the children of a root post to its body rows (+ a trash slot for the stores of columns that do not exist)
+    }
+    return ge;
+}
+
+// the handle's workspaces a launch uses, allocated on first use (all in the arithmetic type of the kernels, fp64)
+int ensure_workspaces(DojoSim* s, const StepIO& io, const Mode& m, const Geometry& ge, bool g, bool reorder) {
+    const size_t B = s->B, wT = sizeof(double), sol_bytes = B * s->M.S * dj::sol_record<8, true>() * wT;       // (the hand-off: sized for the largest record)
+    if (g) {
+        ENSURE(s->d_sol, sol_bytes);
+        if (ge.quad) { ENSURE(s->d_fac, ge.waves_total * dj::FAC_PER_LANE * ge.lanes * wT); ENSURE(s->d_lu, ge.waves_total * dj::LU_PER_LANE * ge.lanes * wT); }
+        if (ge.ypark_stride) ENSURE(s->d_ypark, ge.waves_total * (size_t)ge.ypark_stride * wT);
+        if (ge.msg_stride) ENSURE(s->d_msg, B * (size_t)ge.msg_stride * wT);
+    }
+    if (m.phase != PH_ALL) { ENSURE(s->d_sol, sol_bytes); ENSURE(s->d_resume, B * dj::CARRY_PER_ENV * wT); if (!io.status) ENSURE(s->d_cstat, B * sizeof(int)); }
+    if (reorder) { ENSURE(s->d_dispatch, (ge.waves_total + 1) * sizeof(int)); if (!io.iters) ENSURE(s->d_liters, B * sizeof(int)); }
+    // the refining kernels follow the plain ones (dojo_kernels.hip)
+    if (ge.quad && std::isfinite(refine_threshold(s))) { ENSURE(s->d_blk, ge.waves_total * 90 * ge.lanes * wT); ENSURE(s->d_flag, B * sizeof(int)); }
+    return DOJO_OK;
+}
+
+// the arguments of the kernels of one launch: the batch-level buffers moved to the span's first environment / workgroup
+template <class TIO, class T>
+dj::KernelArgs<TIO, T> kernel_args(const DojoSim* s, const StepIO& io, const Span& sp, const Mode& m, const Geometry& ge, const Variant& v, bool reorder) {
+    const size_t Nb = s->M.Nb, nu = s->M.nu, nx = 12 * Nb, env0 = sp.env0, wave0 = ge.wave0;
+    const bool g = io.dz != nullptr || io.dc != nullptr, quad = ge.quad, step = io.dc == nullptr;      // (contact-data columns only: the step's solution is not written again)
     auto off = [&](const void* p, size_t per_env) -> TIO* { return p ? (TIO*)p + env0 * per_env : (TIO*)nullptr; };
     dj::KernelArgs<TIO, T> A;
-    const double rw_ = refine_threshold(s);
-    A.G = dj::make_globals<T>(s->M, s->opts, s->grad_mode, rw_);
-    A.nodes = (const dj::NodeP<T>*)s->d_nodes; A.contacts = (const dj::ContactP<T>*)s->d_contacts; A.B = nenv;
-    A.z = off(z, 13 * Nb); A.u = off(u, nu); A.z_next = off(zn, 13 * Nb); A.fext = off(s->fext, 6 * Nb);
-    A.status = status ? status + env0 : nullptr; A.iters = iters ? iters + env0 : nullptr;
-    A.vel = off(vel, 6 * Nb); A.joint_imp = off(jimp, s->M.n_joint_imp); A.contact_sg = off(csg, csg_per(s) * s->M.Nc);
-    A.dz = off(dz, nx * nx); A.du = off(du, nx * nu); A.dc = off(dc, nx * 5 * s->M.Nc);
-    A.res = storage ? off(s->d_res, 6 * Nb) : (TIO*)nullptr;
+    A.G = dj::make_globals<T>(s->M, s->opts, s->grad_mode, refine_threshold(s));
+    if (ge.NW == 1 || ge.NW == 2) dj::set_row_passes(A.G, s->M);             // the factorization's level passes in the row layout (dojo_device.hpp, factorize_rows), where they pay
+    A.nodes = (const dj::NodeP<T>*)s->d_nodes; A.contacts = (const dj::ContactP<T>*)s->d_contacts; A.B = sp.nenv;
+    A.z = off(io.z, 13 * Nb); A.u = off(io.u, nu); A.z_next = off(io.z_next, 13 * Nb); A.fext = off(s->fext, 6 * Nb);
+    A.status = io.status ? io.status + env0 : nullptr; A.iters = io.iters ? io.iters + env0 : nullptr;
+    A.vel = off(step ? s->d_vel : nullptr, 6 * Nb); A.joint_imp = off(step ? s->d_jimp : nullptr, s->M.n_joint_imp); A.contact_sg = off(step ? s->d_csg : nullptr, csg_per(s) * s->M.Nc);
+    A.dz = off(io.dz, nx * nx); A.du = off(io.du, nx * nu); A.dc = off(io.dc, nx * 5 * s->M.Nc);
+    A.res = io.storage ? off(s->d_res, 6 * Nb) : (TIO*)nullptr;
     A.tsd = s->M.has_tsd ? (const dj::TraSD<T>*)s->d_tsd : nullptr;
     A.mlim = s->M.has_mlim ? (const dj::MLimP<T>*)s->d_mlim : nullptr;
     A.cuts = s->M.has_cut ? (const dj::NodeP<T>*)s->d_cuts : nullptr; A.ncut = (int)s->M.cuts.size();
     A.cutws = s->M.has_cut ? (T*)s->d_cutws + env0 * (size_t)dj::CUTWS : nullptr;
     A.mu_out = s->d_mu ? (T*)s->d_mu + env0 : nullptr;
-    A.diag_out = (s->d_diag && quad_mapping_of(s)) ? (T*)s->d_diag + 2 * env0 : nullptr;
-    // mapping: four lanes per supernode when the mechanism has <= 16 bodies (one Ant per wavefront) or <= 32 bodies
-    // (one Atlas per two-wavefront workgroup; contact rows pooled per contact: <= 16 contacts, <= 4 per body);
-    // else one lane per supernode
-    const int NW = mapping_waves(s->M);
-    const bool quad = NW > 0;
-    if (NW == 1 || NW == 2) dj::set_row_passes(A.G, s->M);             // the factorization's level passes in the row layout (dojo_device.hpp, factorize_rows), where they pay
-    int E = 64 * (quad ? NW : 1) / (s->M.S * (quad ? 4 : 1));
-    dim3 grid((nenv + E - 1) / E);
-    const size_t waves_total = (s->B + E - 1) / E, wave0 = env0 / E;        // workgroups, each 64 * NW lanes
-    const int g = (dz != nullptr) || (dc != nullptr);
-    // (refusals first: a timing slot taken before them would never be marked used)
-    if (g && (s->M.has_ss || s->M.has_cc)) { g_err = "gradients are not available for mechanisms with a body-body contact"; return DOJO_ERR_UNSUPPORTED; }
-    if (g && s->M.contact_model != 0) {   // the reference has no data Jacobians for ImpactContact / LinearContact either (src/gradients/data.jl:152-192 are NonlinearContact methods)
-        g_err = "gradients are not available for ImpactContact / LinearContact mechanisms"; return DOJO_ERR_UNSUPPORTED;
-    }
-    if (g && quad && std::max<size_t>(2 * Nb + (nu + 5) / 6, dc != nullptr ? (size_t)s->M.Nc : 0) > 128) {
-        // (dojo_device.hpp, gradient_columns_quad: the branch schedule keeps batch sets in two 64-bit words; unreachable with <= 32 bodies -- 2 x 32 + 32 --
-        //  but a mapping change must not turn it into silently aliased batches)
-        g_err = "the IFT sweeps support at most 128 column batches per environment"; return DOJO_ERR_UNSUPPORTED;
-    }
-    if (dc != nullptr && s->M.Nc > 64) {  // the sweeps' batch masks hold one bit per contact of the environment (dojo_device.hpp, sweep_masks)
-        g_err = "contact-data gradients support at most 64 contacts per environment"; return DOJO_ERR_UNSUPPORTED;
-    }
-    int slot = -1;
-    if (phase == PH_CONT) timed = false;
-    if (timed && phase == PH_GRAD) slot = s->phase_slot;
-    else if (timed) { int rc_ = acquire_slot(s, &slot); if (rc_ != DOJO_OK) return rc_; HIPCHK(hipEventRecord(s->ring[slot].a, st)); s->phase_slot = slot; }
-    A.sol = nullptr;
-    // doubles per supernode of the step -> IFT hand-off record in the kernels that serve this mechanism (the launcher selection below: MAXC by mapping)
-    const int vmaxc = !quad ? (s->M.maxc <= 4 ? 4 : 8) : NW == 2 ? (s->M.maxc <= 1 ? 1 : 4) : (s->M.maxc <= 1 ? 1 : s->M.maxc <= 4 ? 4 : 8);
-    const size_t sol_rec = (s->M.has_mlim || s->M.has_cut) ? (vmaxc == 4 ? dj::sol_record<4, true>() : dj::sol_record<8, true>())
-                                         : vmaxc == 1 ? dj::sol_record<1>() : vmaxc == 4 ? dj::sol_record<4>() : dj::sol_record<8>();
-    if (g) {
-        if (!s->d_sol) HIPCHK(hipMalloc(&s->d_sol, (size_t)s->B * s->M.S * dj::sol_record<8, true>() * sizeof(T)));   // sized for the largest record
-        A.sol = (T*)((s->sol_cur && s->d_sol2) ? s->d_sol2 : s->d_sol) + env0 * s->M.S * sol_rec;   // (the record size of the kernels of this mechanism: a launch over the whole batch
-                                                                            //  -- the continuation -- must find the records where the groups' launches put them)
-        if (quad && !s->d_fac) HIPCHK(hipMalloc(&s->d_fac, waves_total * dj::FAC_PER_LANE * 64 * NW * sizeof(T)));
-        if (quad && !s->d_lu) HIPCHK(hipMalloc(&s->d_lu, waves_total * dj::LU_PER_LANE * 64 * NW * sizeof(T)));
-    }
+    A.diag_out = (s->d_diag && quad) ? (T*)s->d_diag + 2 * env0 : nullptr;
+    // (the record size of the kernels of this mechanism: a launch over the whole batch -- the continuation -- must find the records where the groups' launches put them)
+    A.sol = (g || m.phase != PH_ALL) ? (T*)(m.rec ? s->d_sol2 : s->d_sol) + env0 * s->M.S * v.sol_rec : nullptr;
     // the explicit inverses of the Newton loop travel only when somebody reads them: the refining IFT kernel
-    const bool want_fac = A.G.refine_w < INFINITY;
-    A.fac = (g && quad && want_fac) ? (T*)s->d_fac + wave0 * dj::FAC_PER_LANE * 64 * NW : nullptr;
-    A.lu = (g && quad) ? (T*)s->d_lu + wave0 * dj::LU_PER_LANE * 64 * NW : nullptr;
-    A.ypark = nullptr; A.ypark_stride = 0;
-    if (g && quad && sizeof(TIO) < sizeof(T)) {          // (dojo_device.hpp, gradient_columns_quad)
-        const size_t batches = std::max<size_t>(2 * Nb + (nu + 5) / 6, (size_t)s->M.Nc);     // state + control batches | contact batches (dojo_cgrad_kernel)
-        A.ypark_stride = (long long)(batches * 18 * (64 * NW));      // all four roles park (LU-form sweeps)
-        if (!s->d_ypark) HIPCHK(hipMalloc(&s->d_ypark, waves_total * (size_t)A.ypark_stride * sizeof(T)));
-        A.ypark = (T*)s->d_ypark + wave0 * (size_t)A.ypark_stride;
-    }
-    A.msg = nullptr; A.msg_stride = 0;
-    if (g && quad) {                                       // (dojo_device.hpp, gradient_columns_quad: what the children of a root post to its body rows)
-        size_t ntops = 0; for (auto& n_ : s->M.nodes) if (n_.level <= 1) ++ntops;      // one block per level-1 supernode (messages) and per root (its Δv, Δω)
-        const size_t batches = std::max<size_t>(2 * Nb + (nu + 5) / 6, (size_t)s->M.Nc);
-        A.msg_stride = (long long)(ntops * batches * 36 + 8);      // (+ a trash slot for the stores of columns that do not exist)
-        if (A.msg_stride > 0) {
-            if (!s->d_msg) HIPCHK(hipMalloc(&s->d_msg, (size_t)s->B * (size_t)A.msg_stride * sizeof(T)));
-            A.msg = (T*)s->d_msg + env0 * (size_t)A.msg_stride;
-        }
-    }
+    A.fac = (g && quad && A.G.refine_w < INFINITY) ? (T*)s->d_fac + wave0 * dj::FAC_PER_LANE * ge.lanes : nullptr;
+    A.lu = (g && quad) ? (T*)s->d_lu + wave0 * dj::LU_PER_LANE * ge.lanes : nullptr;
+    A.ypark_stride = ge.ypark_stride; A.ypark = ge.ypark_stride ? (T*)s->d_ypark + wave0 * (size_t)ge.ypark_stride : nullptr;
+    A.msg_stride = ge.msg_stride; A.msg = ge.msg_stride ? (T*)s->d_msg + env0 * (size_t)ge.msg_stride : nullptr;
     // Iteration cap (phased launches only; dojo_step_dev has checked that it applies and has zeroed the list's count): the solves that are
     // unfinished after `cap` Newton iterations leave the step kernel and go on in the continuation kernel (PH_CONT)
     A.G.iter_cap = 0;
-    if (phase != PH_ALL) {
-        if (!s->d_sol) HIPCHK(hipMalloc(&s->d_sol, (size_t)s->B * s->M.S * dj::sol_record<8, true>() * sizeof(T)));
-        if (!s->d_resume) HIPCHK(hipMalloc(&s->d_resume, (size_t)s->B * dj::CARRY_PER_ENV * sizeof(T)));
-        if (!status && !s->d_cstat) HIPCHK(hipMalloc((void**)&s->d_cstat, (size_t)s->B * sizeof(int)));
-        A.sol = (T*)((s->sol_cur && s->d_sol2) ? s->d_sol2 : s->d_sol) + env0 * s->M.S * sol_rec;
-        if (!s->plain_phases) {                               // (pipelined groups launch the two kernels apart without the cap's lists)
+    if (m.phase != PH_ALL) {
+        if (m.cap_lists) {
             A.G.iter_cap = effective_cap(s);
             A.resume = (T*)s->d_resume + env0 * dj::CARRY_PER_ENV;
             A.cont_list = s->d_cont_list; A.cont_count = s->d_cont_count; A.wave_base = (int)wave0;
         }
-        if (!status) A.status = s->d_cstat + env0;
+        if (!io.status) A.status = s->d_cstat + env0;
     }
-    // Dispatch order (dojo_set_dispatch_order): this launch's step kernel hands its workgroups out by the permutation the previous launch over the same
-    // environments left behind; the permutation for the next one is made behind this launch's kernels, from this step's iteration counts.
-    bool reorder = false;
-    if (phase == PH_ALL && dc == nullptr && s->dispatch_mode != 0) {
-        // (mode 1: the order only matters when the GPU cannot hold the batch's workgroups at once)
-        // (... and its launches are not chained next to other groups' -- an asynchronous handle of several groups, a rollout: a single launch per step
-        //  waits for its last wavefront on an asynchronous handle too)
-        reorder = s->dispatch_mode == 2 || ((!s->async || s->step_groups <= 1) && !s->chained_now && several_rounds(s));
-    }
+    // Dispatch order: this launch's step kernel hands its workgroups out by the permutation the previous launch over the same environments left behind
     if (reorder) {
-        if (!s->d_dispatch) HIPCHK(hipMalloc((void**)&s->d_dispatch, (waves_total + 1) * sizeof(int)));
-        if (!A.iters) {
-            if (!s->d_liters) HIPCHK(hipMalloc((void**)&s->d_liters, (size_t)s->B * sizeof(int)));
-            A.iters = s->d_liters + env0;
-        }
+        if (!A.iters) A.iters = s->d_liters + env0;
         auto it_ = s->dispatch_have.find(wave0);
-        if (it_ != s->dispatch_have.end() && it_->second == nenv) A.dispatch = s->d_dispatch + wave0;
+        if (it_ != s->dispatch_have.end() && it_->second == sp.nenv) A.dispatch = s->d_dispatch + wave0;
     }
     A.blk = nullptr; A.flag = nullptr;
-    if (quad && A.G.refine_w < INFINITY) {                  // the refining kernels follow the plain ones (dojo_kernels.hip)
-        if (!s->d_blk) HIPCHK(hipMalloc(&s->d_blk, waves_total * 90 * 64 * NW * sizeof(T)));
-        if (!s->d_flag) HIPCHK(hipMalloc((void**)&s->d_flag, (size_t)s->B * sizeof(int)));
-        A.blk = (T*)s->d_blk + wave0 * 90 * 64 * NW;
-        A.flag = s->d_flag + env0;
-    }
-    // Test hook (tests/conftest.py sets it for the GPU tier): the Jacobian buffers are filled with NaN bit patterns before the IFT kernels run, so that
-    // an entry the device fails to write comes back as NaN instead of whatever the allocation held (the kernels must write every entry).
-    static const bool poison_ = getenv("DOJO_POISON_OUTPUTS") != nullptr;
-    if (poison_ && g && (phase == PH_ALL || phase == (s->plain_phases ? PH_GRAD : PH_MAIN))) {    // (pipelined: on the IFT's stream, behind the previous step's IFT)
-        if (dc != nullptr) HIPCHK(hipMemsetAsync(A.dc, 0xFF, (size_t)nenv * nx * 5 * s->M.Nc * sizeof(TIO), st));
-        else {
-            if (A.dz) HIPCHK(hipMemsetAsync(A.dz, 0xFF, (size_t)nenv * nx * nx * sizeof(TIO), st));
-            if (A.du && nu > 0) HIPCHK(hipMemsetAsync(A.du, 0xFF, (size_t)nenv * nx * nu * sizeof(TIO), st));
-        }
-    }
-    typedef int (*launcher_t)(const void*, int, void*, int, void*);
-    const bool f32 = sizeof(TIO) == 4;
-    if (dc != nullptr) {                   // contact-data columns only: the hand-off of the last differentiable step is re-used
-        if (!quad) { g_err = "contact-data gradients need the quad mapping (<= 32 bodies)"; return DOJO_ERR_UNSUPPORTED; }
-        typedef int (*claunch_t)(const void*, int, void*);
-        claunch_t cf = s->M.has_tsd ? (s->M.maxc <= 1 ? (f32 ? dojo_launch_cgrad_tsd_float_1_1 : dojo_launch_cgrad_tsd_double_1_1)
-                                                      : (f32 ? dojo_launch_cgrad_tsd_float_4_1 : dojo_launch_cgrad_tsd_double_4_1))
-                     : NW == 2 ? (s->M.maxc <= 1 ? (f32 ? dojo_launch_cgrad_float_1_2 : dojo_launch_cgrad_double_1_2) : (f32 ? dojo_launch_cgrad_float_4_2 : dojo_launch_cgrad_double_4_2))
-                     : s->M.maxc <= 1 ? (f32 ? dojo_launch_cgrad_float_1_1 : dojo_launch_cgrad_double_1_1)
-                     : s->M.maxc <= 4 ? (f32 ? dojo_launch_cgrad_float_4_1 : dojo_launch_cgrad_double_4_1)
-                                      : (f32 ? dojo_launch_cgrad_float_8_1 : dojo_launch_cgrad_double_8_1);
-        int lrc_ = cf(&A, (int)grid.x, (void*)st);
-        if (lrc_ != 0) { g_err = std::string("kernel launch: ") + hipGetErrorString((hipError_t)lrc_); return DOJO_ERR_DEVICE; }
-        HIPCHK(hipGetLastError());
-        if (timed) { DojoSim::Ev3& e = s->ring[slot]; HIPCHK(hipEventRecord(e.b, st)); e.has_mid = false; e.n = 1; e.used = true; s->last_slot = slot; }
-        return DOJO_OK;
-    }
-    launcher_t fn;
-    if (s->M.has_ss && s->M.contact_model != 2) fn = f32 ? dojo_launch_ss_float_1_1 : dojo_launch_ss_double_1_1;
-    else if (s->M.contact_model == 2 && !quad) fn = s->M.maxc <= 4 ? (f32 ? dojo_launch_lin_float_4_0 : dojo_launch_lin_double_4_0) : (f32 ? dojo_launch_lin_float_8_0 : dojo_launch_lin_double_8_0);
-    else if (s->M.contact_model == 2) fn = s->M.maxc <= 1 ? (f32 ? dojo_launch_lin_float_1_1 : dojo_launch_lin_double_1_1) : (f32 ? dojo_launch_lin_float_4_1 : dojo_launch_lin_double_4_1);
-    else if (s->M.has_mlim || s->M.has_cut) fn = s->M.maxc <= 4 ? (f32 ? dojo_launch_gen_float_4_0 : dojo_launch_gen_double_4_0) : (f32 ? dojo_launch_gen_float_8_0 : dojo_launch_gen_double_8_0);
-    else if (s->M.has_tsd && !quad) fn = s->M.maxc <= 4 ? (f32 ? dojo_launch_tsd_float_4_0 : dojo_launch_tsd_double_4_0)
-                                                       : (f32 ? dojo_launch_tsd_float_8_0 : dojo_launch_tsd_double_8_0);
-    else if (s->M.has_tsd) fn = s->M.maxc <= 1 ? (f32 ? dojo_launch_tsd_float_1_1 : dojo_launch_tsd_double_1_1)
-                                          : (f32 ? dojo_launch_tsd_float_4_1 : dojo_launch_tsd_double_4_1);
-    else if (NW == 2) fn = s->M.maxc <= 1 ? (f32 ? dojo_launch_float_1_2 : dojo_launch_double_1_2) : (f32 ? dojo_launch_float_4_2 : dojo_launch_double_4_2);
-    else if (quad) fn = s->M.maxc <= 1 ? (f32 ? dojo_launch_float_1_1 : dojo_launch_double_1_1)
-                 : s->M.maxc <= 4 ? (f32 ? dojo_launch_float_4_1 : dojo_launch_double_4_1)
-                                  : (f32 ? dojo_launch_float_8_1 : dojo_launch_double_8_1);
-    else      fn = s->M.maxc <= 4 ? (f32 ? dojo_launch_float_4_0 : dojo_launch_double_4_0)
-                                  : (f32 ? dojo_launch_float_8_0 : dojo_launch_double_8_0);
-    const int phases = phase == PH_ALL ? (1 | (g ? 2 : 0)) : phase == PH_MAIN ? 1 : phase == PH_GRAD ? 2 : (4 | (g ? 8 : 0));
-    const int lgrid = phase == PH_CONT ? (int)std::min<size_t>(waves_total, 128) : (int)grid.x;     // (a continuation workgroup takes a whole CU's LDS and loops over the list)
-    int lrc = fn(&A, lgrid, (void*)st, phases, (timed && g && (phases & 1)) ? (void*)s->ring[slot].m : nullptr);
-    if (lrc != 0) { g_err = std::string("kernel launch: ") + hipGetErrorString((hipError_t)lrc); return DOJO_ERR_DEVICE; }
-    HIPCHK(hipGetLastError());
-    if (timed && (phase == PH_ALL || phase == PH_GRAD || (phase == PH_MAIN && !g))) {
-        DojoSim::Ev3& e = s->ring[slot]; HIPCHK(hipEventRecord(e.b, st)); e.has_mid = g != 0; e.n = 1; e.used = true; s->last_slot = slot;
-    }
-    if (reorder) {
-        // (segments of another partition of the batch that overlap this one hold permutations of other ranges: forgotten before this one is written)
-        for (auto it_ = s->dispatch_have.begin(); it_ != s->dispatch_have.end();) {
-            const size_t a_ = it_->first, b_ = a_ + ((size_t)it_->second + E - 1) / E;
-            if (a_ < wave0 + grid.x && wave0 < b_) it_ = s->dispatch_have.erase(it_); else ++it_;
-        }
-        hipLaunchKernelGGL(ckern::dispatch_order_kernel, dim3(1), dim3(1024), 0, st, (const int*)A.iters, nenv, E, (int)grid.x, s->d_dispatch + wave0);
-        HIPCHK(hipGetLastError());
-        s->dispatch_have[wave0] = nenv;
-    }
-    if (storage) {                         // record: the Storage rows of the environments of this launch
-        const long long n = (long long)nenv * Nb; const int T_ = 128;
-        hipLaunchKernelGGL((ckern::storage_kernel<TIO>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, st, (const dj::NodeP<double>*)s->d_nodes,
-                           (const dj::ContactP<double>*)s->d_contacts, (int)Nb, s->M.Nc, s->M.contact_model, (int)csg_per(s), s->M.dt, (int)env0, nenv,
-                           (const TIO*)z, (const TIO*)vel, (const TIO*)csg, (const TIO*)s->d_res, (const TIO*)s->fext, (TIO*)storage);
-        HIPCHK(hipGetLastError());
-    }
+    if (quad && A.G.refine_w < INFINITY) { A.blk = (T*)s->d_blk + wave0 * 90 * ge.lanes; A.flag = s->d_flag + env0; }
+    return A;
+}
+
+// Timed launches: a slot of the ring, its begin event in front of the first kernel ...
+int begin_timing(DojoSim* s, int* slot, hipStream_t st) {
+    TRY(acquire_slot(s, slot)); HIPCHK(hipEventRecord(s->ring[*slot].a, st));
+    return DOJO_OK;
+}
+// ... and its end event behind the last one; the slot then stands for n steps (has_mid: the launcher put the slot's middle event between step and IFT kernel)
+int end_timing(DojoSim* s, int slot, bool has_mid, int n, hipStream_t st) {
+    DojoSim::Ev3& e = s->ring[slot]; HIPCHK(hipEventRecord(e.b, st));
+    e.has_mid = has_mid; e.n = n; e.used = true; s->last_slot = slot;
     return DOJO_OK;
 }
 
-int launch_any(DojoSim* s, const void* z, const void* u, void* zn, int* status, int* iters, void* vel, void* jimp, void* csg,
-               void* dz, void* du, hipStream_t st, bool timed, size_t env0 = 0, int nenv = -1, void* dc = nullptr, void* storage = nullptr, int phase = PH_ALL) {
-    if (s->dtype == DOJO_DTYPE_F32) return launch<float, double, double>(s, z, u, zn, status, iters, vel, jimp, csg, dz, du, st, timed, env0, nenv, dc, storage, phase);
-    return launch<double, double, double>(s, z, u, zn, status, iters, vel, jimp, csg, dz, du, st, timed, env0, nenv, dc, storage, phase);
+// Dispatch order, behind a launch's kernels: the permutation for the next launch over these environments, from this step's iteration counts
+int launch_dispatch_order(DojoSim* s, const int* iters, const Span& sp, const Geometry& ge) {
+    // (segments of another partition of the batch that overlap this one hold permutations of other ranges: forgotten before this one is written)
+    for (auto it_ = s->dispatch_have.begin(); it_ != s->dispatch_have.end();) {
+        const size_t a_ = it_->first, b_ = a_ + ((size_t)it_->second + ge.E - 1) / ge.E;
+        if (a_ < ge.wave0 + ge.grid && ge.wave0 < b_) it_ = s->dispatch_have.erase(it_); else ++it_;
+    }
+    hipLaunchKernelGGL(ckern::dispatch_order_kernel, dim3(1), dim3(1024), 0, sp.stream, iters, sp.nenv, ge.E, (int)ge.grid, s->d_dispatch + ge.wave0);
+    HIPCHK(hipGetLastError());
+    s->dispatch_have[ge.wave0] = sp.nenv;
+    return DOJO_OK;
+}
+// record: the Storage rows of the environments of a launch
+template <class TIO>
+int launch_storage(const DojoSim* s, const StepIO& io, const Span& sp) {
+    const size_t Nb = s->M.Nb; const long long n = (long long)sp.nenv * Nb; const int T_ = 128;
+    hipLaunchKernelGGL((ckern::storage_kernel<TIO>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, sp.stream, (const dj::NodeP<double>*)s->d_nodes,
+                       (const dj::ContactP<double>*)s->d_contacts, (int)Nb, s->M.Nc, s->M.contact_model, (int)csg_per(s), s->M.dt, (int)sp.env0, sp.nenv,
+                       (const TIO*)io.z, (const TIO*)s->d_vel, (const TIO*)s->d_csg, (const TIO*)s->d_res, (const TIO*)s->fext, (TIO*)io.storage);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
+
+// Launches the step (and IFT) kernels for the environments of `sp`; all pointers of `io` are the batch-level buffers.
+template <class TIO, class T, class TL>
+int launch(DojoSim* s, const StepIO& io, const Span& sp, const Mode& m) {
+    const hipStream_t st = sp.stream;
+    const bool g = io.dz != nullptr || io.dc != nullptr, f32 = sizeof(TIO) == 4, timed = m.slot != nullptr && m.phase != PH_CONT;
+    const Geometry ge = geometry_of(s, sp, g);
+    const Variant* v = variant_of(s->M, ge.NW);
+    if (!v || (io.dc && !v->cgrad[f32])) { g_err = "no kernel build serves this mechanism"; return DOJO_ERR_UNSUPPORTED; }
+    // Dispatch order (dojo_set_dispatch_order): the permutation for the next launch is made behind this launch's kernels.
+    // (mode 1: the order only matters when the GPU cannot hold the batch's workgroups at once)
+    // (... and its launches are not chained next to other groups' -- an asynchronous handle of several groups, a rollout: a single launch per step
+    //  waits for its last wavefront on an asynchronous handle too)
+    const bool reorder = m.phase == PH_ALL && io.dc == nullptr && s->dispatch_mode != 0
+                         && (s->dispatch_mode == 2 || ((!s->async || m.groups <= 1) && !m.chained && several_rounds(s)));
+    TRY(ensure_workspaces(s, io, m, ge, g, reorder));
+    const dj::KernelArgs<TIO, T> A = kernel_args<TIO, T>(s, io, sp, m, ge, *v, reorder);
+    if (timed && m.phase != PH_GRAD) TRY(begin_timing(s, m.slot, st));      // (PH_GRAD: the slot of the group's PH_MAIN)
+    // Test hook (tests/conftest.py sets it for the GPU tier): the Jacobian buffers are filled with NaN bit patterns before the IFT kernels run, so that
+    // an entry the device fails to write comes back as NaN instead of whatever the allocation held (the kernels must write every entry).
+    static const bool poison_ = getenv("DOJO_POISON_OUTPUTS") != nullptr;
+    if (poison_ && g && (m.phase == PH_ALL || m.phase == (m.cap_lists ? PH_MAIN : PH_GRAD))) {    // (pipelined: on the IFT's stream, behind the previous step's IFT)
+        const size_t nx = 12 * s->M.Nb, nu = s->M.nu, n = (size_t)sp.nenv;
+        if (A.dc) HIPCHK(hipMemsetAsync(A.dc, 0xFF, n * nx * 5 * s->M.Nc * sizeof(TIO), st));
+        if (!A.dc && A.dz) HIPCHK(hipMemsetAsync(A.dz, 0xFF, n * nx * nx * sizeof(TIO), st));
+        if (!A.dc && A.du && nu > 0) HIPCHK(hipMemsetAsync(A.du, 0xFF, n * nx * nu * sizeof(TIO), st));
+    }
+    const int phases = m.phase == PH_ALL ? (1 | (g ? 2 : 0)) : m.phase == PH_MAIN ? 1 : m.phase == PH_GRAD ? 2 : (4 | (g ? 8 : 0));
+    const int lgrid = m.phase == PH_CONT ? (int)std::min<size_t>(ge.waves_total, 128) : (int)ge.grid;     // (a continuation workgroup takes a whole CU's LDS and loops over the list)
+    const int lrc = io.dc ? v->cgrad[f32](&A, (int)ge.grid, (void*)st)      // contact-data columns only: the hand-off of the last differentiable step is re-used
+                          : v->step[f32](&A, lgrid, (void*)st, phases, (timed && g && (phases & 1)) ? (void*)s->ring[*m.slot].m : nullptr);
+    if (lrc != 0) { g_err = std::string("kernel launch: ") + hipGetErrorString((hipError_t)lrc); return DOJO_ERR_DEVICE; }
+    HIPCHK(hipGetLastError());
+    if (timed && (m.phase == PH_ALL || m.phase == PH_GRAD || (m.phase == PH_MAIN && !g))) TRY(end_timing(s, *m.slot, g && !io.dc, 1, st));
+    if (reorder) TRY(launch_dispatch_order(s, A.iters, sp, ge));
+    if (io.storage) TRY(launch_storage<TIO>(s, io, sp));
+    return DOJO_OK;
+}
+
+int launch_any(DojoSim* s, const StepIO& io, const Span& sp, const Mode& m) {
+    return s->dtype == DOJO_DTYPE_F32 ? launch<float, double, double>(s, io, sp, m) : launch<double, double, double>(s, io, sp, m);
+}
+Mode step_mode(const DojoSim* s, size_t NG, bool cap_lists = false, bool chained = false) { return Mode{PH_ALL, nullptr, cap_lists, chained, NG, s->sol_cur}; }
+Span whole_batch(const DojoSim* s, hipStream_t st) { return Span{0, s->B, st}; }
+
+// A failure after the fork: what is already running on the internal streams must be ordered before the caller's stream all the same.  Armed where a step forks off the caller's
+// stream; every return that does not go through done() marks the handle pending and joins the groups' streams -- and the continuation's, once its end event is recorded -- into it.
+struct ForkGuard {
+    DojoSim* s; hipStream_t st; bool armed = true, cont_recorded = false;
+    ~ForkGuard() { if (!armed) return; s->pending = true; (void)join_groups(s, st); if (cont_recorded) (void)hipStreamWaitEvent(st, s->cont_event, 0); }
+    int done() { armed = false; return DOJO_OK; }
+};
+
+// The three ways dojo_step_dev steps a batch, each its stream choreography.  One launch on the caller's stream:
+int step_single(DojoSim* s, const StepIO& io, hipStream_t st, bool capped) {
+    int slot = -1; TRY(join_groups(s, st));
+    const Mode m = step_mode(s, 1, capped);
+    if (!capped) return launch_any(s, io, whole_batch(s, st), m.with(PH_ALL, &slot));
+    // (the continuation is enqueued before the IFT of the finished workgroups and on a stream of higher priority: its workgroups need a
+    //  whole CU's LDS each, which they only find before the IFT's wavefronts have spread over the GPU)
+    TRY(launch_any(s, io, whole_batch(s, st), m.with(PH_MAIN, &slot)));
+    ForkGuard guard{s, st};
+    HIPCHK(hipEventRecord(s->main_events[0], st));
+    HIPCHK(hipStreamWaitEvent(s->cstream, s->main_events[0], 0));
+    TRY(launch_any(s, io, whole_batch(s, s->cstream), m.with(PH_CONT, nullptr)));
+    HIPCHK(hipEventRecord(s->cont_event, s->cstream)); guard.cont_recorded = true;
+    if (io.dz) TRY(launch_any(s, io, whole_batch(s, st), m.with(PH_GRAD, &slot)));
+    HIPCHK(hipStreamWaitEvent(st, s->cont_event, 0));
+    return guard.done();
+}
+
+// fork: the step kernel of every group, each followed by the IFT of what it finished; behind ALL step kernels the continuation, once
+// over the batch, on its own stream; join: the groups and the continuation into the caller's stream
+int step_capped_groups(DojoSim* s, const StepIO& io, hipStream_t st, size_t NG) {
+    TRY(ensure_groups(s, NG));
+    const Partition P(s->B, NG); s->last_part = P;
+    if (s->group_slot.size() < NG) s->group_slot.resize(NG, -1);
+    const Mode m = step_mode(s, NG, true);
+    ForkGuard guard{s, st};
+    HIPCHK(hipEventRecord(s->fork_event, st));
+    for (size_t gi = 0; gi < P.groups(); ++gi) {
+        const Span sp = P.span(gi, s->gstreams[gi]);
+        HIPCHK(hipStreamWaitEvent(sp.stream, s->fork_event, 0));
+        TRY(launch_any(s, io, sp, m.with(PH_MAIN, &s->group_slot[gi])));
+        HIPCHK(hipEventRecord(s->main_events[gi], sp.stream));
+        HIPCHK(hipStreamWaitEvent(s->cstream, s->main_events[gi], 0));
+    }
+    // The continuation first: its workgroups take a whole CU's LDS each, which they only find while the GPU is empty -- so the groups' IFT
+    // kernels wait until every step kernel is done as well (they would otherwise start behind their own group's step kernel, fill the CUs as
+    // these drain, and keep the continuation out until they are through: measured, +1.2 ms per step), and the continuation's stream has
+    // the higher priority.  The IFT kernels (1.2 ms of work) then run next to the continuation (2-3 ms on a few CUs).
+    HIPCHK(hipEventRecord(s->allmain_event, s->cstream));
+    TRY(launch_any(s, io, whole_batch(s, s->cstream), m.with(PH_CONT, nullptr)));
+    HIPCHK(hipEventRecord(s->cont_event, s->cstream)); guard.cont_recorded = true;
+    for (size_t gi = 0; gi < P.groups() && io.dz; ++gi) {
+        const Span sp = P.span(gi, s->gstreams[gi]);
+        HIPCHK(hipStreamWaitEvent(sp.stream, s->allmain_event, 0));
+        TRY(launch_any(s, io, sp, m.with(PH_GRAD, &s->group_slot[gi])));
+    }
+    s->pending = true;
+    TRY(join_groups(s, st));
+    HIPCHK(hipStreamWaitEvent(st, s->cont_event, 0));
+    return guard.done();
+}
+
+// fork: every group waits for what the caller's stream holds (the inputs); group g of this call runs behind group g of
+// the previous call on the same internal stream.  join: the caller's stream waits for all groups -- unless the handle
+// is asynchronous (dojo_set_async), where consecutive calls chain per group and dojo_join() does it once.
+int step_plain_groups(DojoSim* s, const StepIO& io, hipStream_t st, size_t NG) {
+    TRY(ensure_groups(s, NG));
+    const Partition P(s->B, NG);
+    // per-group chaining needs the same partition as the call still in flight: group g must cover the environments group g
+    // covered.  Options, refinement or the group count may have changed it -- then everything in flight is joined first.
+    if (s->pending && s->last_part != P) TRY(join_groups(s, st));
+    s->last_part = P;
+    ForkGuard guard{s, st};
+    HIPCHK(hipEventRecord(s->fork_event, st));
+    // Pipelined groups (dojo_set_async(h, 2), plain solves): the IFT kernel of a group's step k goes onto the group's SECOND stream, behind its
+    // step kernel and next to the step kernel of step k + 1 -- both depend on step k alone.  Step k + 1 writes the other hand-off record; step
+    // k + 2 re-uses record k's and waits for IFT k.  What this buys: while a group's step kernel drains (its launch lasts as long as its slowest
+    // wavefront) the group has another kernel ready for the SIMDs that fall idle -- with 16 groups x 64 wavefronts = 1024 SIMDs there is no other
+    // work to fill them.  The caller's inputs of un-joined calls stay untouched (the asynchronous contract): the IFT of step k reads z, u of step k.
+    const bool piped = s->async == 2 && io.dz != nullptr && !std::isfinite(refine_threshold(s));
+    if (piped) { TRY(ensure_pipe(s, NG)); s->sol_cur ^= 1; }
+    const Mode m = step_mode(s, NG);
+    for (size_t gi = 0; gi < P.groups(); ++gi) {
+        const Span sp = P.span(gi, s->gstreams[gi]);
+        int slot = -1;
+        HIPCHK(hipStreamWaitEvent(sp.stream, s->fork_event, 0));
+        if (!piped) { TRY(launch_any(s, io, sp, m.with(PH_ALL, &slot))); continue; }
+        HIPCHK(hipStreamWaitEvent(sp.stream, s->grad_done[m.rec][gi], 0));      // (the IFT that read this record two calls ago)
+        TRY(launch_any(s, io, sp, m.with(PH_MAIN, &slot)));
+        HIPCHK(hipEventRecord(s->main_events[gi], sp.stream));
+        const Span sp2{sp.env0, sp.nenv, s->gstreams2[gi % s->gstreams2.size()]};
+        HIPCHK(hipStreamWaitEvent(sp2.stream, s->main_events[gi], 0));
+        TRY(launch_any(s, io, sp2, m.with(PH_GRAD, &slot)));
+        HIPCHK(hipEventRecord(s->grad_done[m.rec][gi], sp2.stream));
+    }
+    s->pending = true;
+    if (!s->async) TRY(join_groups(s, st));
+    return guard.done();      // (a failure: the groups already launched stay ordered before the caller's stream)
 }
 
 // RCCL, opened on first use (dojo_comm_*)
@@ -790,12 +925,6 @@ bool load() {
     return true;
 }
 const char* why(int rc) { return get_error_string ? get_error_string(rc) : "RCCL error"; }
-}
-
-int ensure(void** p, size_t bytes) {
-    if (*p) return DOJO_OK;
-    HIPCHK(hipMalloc(p, bytes ? bytes : 8));
-    return DOJO_OK;
 }
 
 } // namespace
@@ -849,10 +978,7 @@ int dojo_create(const DojoTopology* topo, int32_t batch, int32_t dtype, int32_t 
 void dojo_destroy(DojoHandle s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    void* ps[] = {s->d_tsd, s->d_mlim, s->d_cuts, s->d_cutws, s->d_sol2, s->d_fext, s->d_res, s->d_nodes, s->d_contacts, s->d_z, s->d_u, s->d_zn, s->d_vel, s->d_jimp, s->d_csg, s->d_dz, s->d_du, s->d_status, s->d_iters, s->d_sol, s->d_fac, s->d_lu, s->d_blk, s->d_ypark, s->d_msg, (void*)s->d_flag, s->d_cz, s->d_jf, (void*)s->d_mu, (void*)s->d_diag, s->d_order, s->d_x, s->d_xn, s->d_jm, s->d_jt, s->d_jb};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    void* pc[] = {s->d_resume, (void*)s->d_cont_list, (void*)s->d_cont_count, (void*)s->d_cstat, (void*)s->d_dispatch, (void*)s->d_liters};
-    for (void* p : pc) if (p) (void)hipFree(p);
+    for (void* p : s->owned) (void)hipFree(p);
     if (s->cstream) (void)hipStreamDestroy(s->cstream);
     if (s->cont_event) (void)hipEventDestroy(s->cont_event);
     if (s->allmain_event) (void)hipEventDestroy(s->allmain_event);
@@ -897,8 +1023,7 @@ int dojo_set_external_force(DojoHandle s, const void* fext) {
     if (!fext) { s->fext = nullptr; return DOJO_OK; }
     HIPCHK(hipSetDevice(s->device));
     const size_t bytes = (size_t)s->B * 6 * s->M.Nb * s->w;
-    int rc;
-    if ((rc = ensure(&s->d_fext, bytes))) return rc;
+    ENSURE(s->d_fext, bytes);
     HIPCHK(hipDeviceSynchronize());                          // steps still in flight read the previous forces
     HIPCHK(hipMemcpy(s->d_fext, fext, bytes, hipMemcpyHostToDevice));
     s->fext = s->d_fext;
@@ -975,120 +1100,21 @@ int dojo_step_dev(DojoHandle s, const void* z, const void* u, void* z_next, int3
     if ((dz == nullptr) != (du == nullptr) && s->M.nu > 0) { g_err = "dojo_step_dev: dz and du must both be given or both be NULL"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w;
-    int rc;
-    if ((rc = ensure(&s->d_vel, B * 6 * s->M.Nb * w))) return rc;
-    if ((rc = ensure(&s->d_jimp, B * (s->M.n_joint_imp + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w))) return rc;
-    if ((rc = ensure((void**)&s->d_mu, B * sizeof(double)))) return rc;
+    ENSURE(s->d_vel, B * 6 * s->M.Nb * w); ENSURE(s->d_jimp, B * (s->M.n_joint_imp + 1) * w);
+    ENSURE(s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w);
+    ENSURE(s->d_mu, B * sizeof(double));
+    TRY(refuse_unsupported(s, dz != nullptr, false));
+    const StepIO io{z, u, z_next, status, iters, dz, du, nullptr, nullptr};
     hipStream_t st = (hipStream_t)stream;
     const size_t NG = group_count(s, true, true);
-    s->step_groups = NG;
     // Iteration cap (dojo_set_iteration_cap): in force for steps that are joined into the caller's stream -- there the step waits for its longest
     // solve.  An asynchronous handle chains its groups' steps without a barrier and hides that tail behind the other groups' kernels.
     const bool capped = !s->async && effective_cap(s) > 0;
     if (capped) {
-        if ((rc = join_groups(s, st))) return rc;                  // (asynchronous steps still in flight)
-        if ((rc = begin_capped_step(s, std::max<size_t>(NG, 1), st))) return rc;
+        TRY(join_groups(s, st));                  // (asynchronous steps still in flight)
+        TRY(begin_capped_step(s, std::max<size_t>(NG, 1), st));
     }
-    if (NG <= 1) {
-        if ((rc = join_groups(s, st))) return rc;
-        if (capped) {
-            // (the continuation is enqueued before the IFT of the finished workgroups and on a stream of higher priority: its workgroups need a
-            //  whole CU's LDS each, which they only find before the IFT's wavefronts have spread over the GPU)
-            if ((rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, st, true, 0, -1, nullptr, nullptr, PH_MAIN))) return rc;
-            HIPCHK(hipEventRecord(s->main_events[0], st));
-            HIPCHK(hipStreamWaitEvent(s->cstream, s->main_events[0], 0));
-            if ((rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, s->cstream, false, 0, -1, nullptr, nullptr, PH_CONT))) return rc;
-            HIPCHK(hipEventRecord(s->cont_event, s->cstream));
-            if (dz && (rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, st, true, 0, -1, nullptr, nullptr, PH_GRAD))) return rc;
-            HIPCHK(hipStreamWaitEvent(st, s->cont_event, 0));
-        } else
-        rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, st, true);
-    } else if (capped) {
-        // fork: the step kernel of every group, each followed by the IFT of what it finished; behind ALL step kernels the continuation, once
-        // over the batch, on its own stream; join: the groups and the continuation into the caller's stream
-        if ((rc = ensure_groups(s, NG))) return rc;
-        const size_t per = ((B + NG - 1) / NG + 63) / 64 * 64;
-        s->last_NG = NG; s->last_per = per;
-        bool cont_recorded = false;
-        // a failure after the fork: what is already running on the internal streams must be ordered before the caller's stream all the same
-        auto unwind = [&](int rc_) { s->pending = true; (void)join_groups(s, st); if (cont_recorded) (void)hipStreamWaitEvent(st, s->cont_event, 0); return rc_; };
-        HIPCHK(hipEventRecord(s->fork_event, st));
-        for (size_t gi = 0; gi < NG; ++gi) {
-            const size_t env0 = gi * per;
-            if (env0 >= B) break;
-            const int ne = (int)std::min(per, B - env0);
-            HIPCHK(hipStreamWaitEvent(s->gstreams[gi], s->fork_event, 0));
-            if ((rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, s->gstreams[gi], true, env0, ne, nullptr, nullptr, PH_MAIN))) return unwind(rc);
-            HIPCHK(hipEventRecord(s->main_events[gi], s->gstreams[gi]));
-            HIPCHK(hipStreamWaitEvent(s->cstream, s->main_events[gi], 0));
-            if (s->group_slot.size() <= gi) s->group_slot.resize(gi + 1, -1);
-            s->group_slot[gi] = s->phase_slot;
-        }
-        // The continuation first: its workgroups take a whole CU's LDS each, which they only find while the GPU is empty -- so the groups' IFT
-        // kernels wait until every step kernel is done as well (they would otherwise start behind their own group's step kernel, fill the CUs as
-        // these drain, and keep the continuation out until they are through: measured, +1.2 ms per step), and the continuation's stream has
-        // the higher priority.  The IFT kernels (1.2 ms of work) then run next to the continuation (2-3 ms on a few CUs).
-        HIPCHK(hipEventRecord(s->allmain_event, s->cstream));
-        if ((rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, s->cstream, false, 0, -1, nullptr, nullptr, PH_CONT))) return unwind(rc);
-        HIPCHK(hipEventRecord(s->cont_event, s->cstream)); cont_recorded = true;
-        for (size_t gi = 0; gi < NG && dz; ++gi) {
-            const size_t env0 = gi * per;
-            if (env0 >= B) break;
-            HIPCHK(hipStreamWaitEvent(s->gstreams[gi], s->allmain_event, 0));
-            s->phase_slot = s->group_slot[gi];
-            if ((rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, s->gstreams[gi], true, env0, (int)std::min(per, B - env0), nullptr, nullptr, PH_GRAD))) return unwind(rc);
-        }
-        s->pending = true;
-        if ((rc = join_groups(s, st))) return rc;
-        HIPCHK(hipStreamWaitEvent(st, s->cont_event, 0));
-    } else {
-        // fork: every group waits for what the caller's stream holds (the inputs); group g of this call runs behind group g of
-        // the previous call on the same internal stream.  join: the caller's stream waits for all groups -- unless the handle
-        // is asynchronous (dojo_set_async), where consecutive calls chain per group and dojo_join() does it once.
-        if ((rc = ensure_groups(s, NG))) return rc;
-        const size_t per = ((B + NG - 1) / NG + 63) / 64 * 64;       // multiple of 64: whole wavefronts for every mapping
-        // per-group chaining needs the same partition as the call still in flight: group g must cover the environments group g
-        // covered.  Options, refinement or the group count may have changed it -- then everything in flight is joined first.
-        if (s->pending && (s->last_NG != NG || s->last_per != per) && (rc = join_groups(s, st))) return rc;
-        s->last_NG = NG; s->last_per = per;
-        HIPCHK(hipEventRecord(s->fork_event, st));
-        // Pipelined groups (dojo_set_async(h, 2), plain solves): the IFT kernel of a group's step k goes onto the group's SECOND stream, behind its
-        // step kernel and next to the step kernel of step k + 1 -- both depend on step k alone.  Step k + 1 writes the other hand-off record; step
-        // k + 2 re-uses record k's and waits for IFT k.  What this buys: while a group's step kernel drains (its launch lasts as long as its slowest
-        // wavefront) the group has another kernel ready for the SIMDs that fall idle -- with 16 groups x 64 wavefronts = 1024 SIMDs there is no other
-        // work to fill them.  The caller's inputs of un-joined calls stay untouched (the asynchronous contract): the IFT of step k reads z, u of step k.
-        const bool piped = s->async == 2 && dz != nullptr && !std::isfinite(refine_threshold(s));
-        if (piped) {
-            if ((rc = ensure_pipe(s, NG))) return rc;
-            s->sol_cur ^= 1; s->plain_phases = true;
-            if (s->group_slot.size() < NG) s->group_slot.resize(NG, -1);
-        }
-        for (size_t gi = 0; gi < NG; ++gi) {
-            const size_t env0 = gi * per;
-            if (env0 >= B) break;
-            const int ne = (int)std::min(per, B - env0);
-            HIPCHK(hipStreamWaitEvent(s->gstreams[gi], s->fork_event, 0));
-            if (piped) {
-                HIPCHK(hipStreamWaitEvent(s->gstreams[gi], s->grad_done[s->sol_cur][gi], 0));      // (the IFT that read this record two calls ago)
-                rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, s->gstreams[gi], true, env0, ne, nullptr, nullptr, PH_MAIN);
-                if (rc == DOJO_OK) {
-                    s->group_slot[gi] = s->phase_slot;
-                    HIPCHK(hipEventRecord(s->main_events[gi], s->gstreams[gi]));
-                    hipStream_t st2 = s->gstreams2[gi % s->gstreams2.size()];
-                    HIPCHK(hipStreamWaitEvent(st2, s->main_events[gi], 0));
-                    s->phase_slot = s->group_slot[gi];
-                    rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, st2, true, env0, ne, nullptr, nullptr, PH_GRAD);
-                    if (rc == DOJO_OK) HIPCHK(hipEventRecord(s->grad_done[s->sol_cur][gi], st2));
-                }
-            } else
-            rc = launch_any(s, z, u, z_next, status, iters, s->d_vel, s->d_jimp, s->d_csg, dz, du, s->gstreams[gi], true, env0, ne);
-            if (rc != DOJO_OK) { s->plain_phases = false; s->pending = true; (void)join_groups(s, st); return rc; }      // (the groups already launched stay ordered before the caller's stream)
-        }
-        s->plain_phases = false;
-        s->pending = true;
-        if (!s->async && (rc = join_groups(s, st))) return rc;
-    }
+    const int rc = NG <= 1 ? step_single(s, io, st, capped) : capped ? step_capped_groups(s, io, st, NG) : step_plain_groups(s, io, st, NG);
     if (rc == DOJO_OK) s->have_solution = true;
     return rc;
 }
@@ -1136,15 +1162,10 @@ int dojo_step(DojoHandle s, const void* z, const void* u, void* z_next, int32_t*
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu;
     int rc;
-    if ((rc = ensure(&s->d_z, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_zn, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_u, B * (nu + 1) * w))) return rc;
-    if ((rc = ensure((void**)&s->d_status, B * sizeof(int)))) return rc;
-    if ((rc = ensure((void**)&s->d_iters, B * sizeof(int)))) return rc;
-    if (with_gradient) {
-        if ((rc = ensure(&s->d_dz, B * nx * nx * w))) return rc;
-        if ((rc = ensure(&s->d_du, B * nx * (nu + 1) * w))) return rc;
-    }
+    ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
+    ENSURE(s->d_u, B * (nu + 1) * w);
+    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
+    if (with_gradient) { ENSURE(s->d_dz, B * nx * nx * w); ENSURE(s->d_du, B * nx * (nu + 1) * w); }
     HIPCHK(hipMemcpy(s->d_z, z, B * nz * w, hipMemcpyHostToDevice));
     if (u && nu) HIPCHK(hipMemcpy(s->d_u, u, B * nu * w, hipMemcpyHostToDevice));
     rc = dojo_step_dev(s, s->d_z, (u && nu) ? s->d_u : nullptr, s->d_zn, s->d_status, s->d_iters,
@@ -1169,11 +1190,9 @@ int dojo_step_impulses(DojoHandle s, const void* z, const void* jf, void* z_next
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nf = 6 * s->M.Nb;
     int rc;
-    if ((rc = ensure(&s->d_z, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_zn, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_jf, 2 * B * nf * w))) return rc;               // [raw impulses | folded forces]
-    if ((rc = ensure((void**)&s->d_status, B * sizeof(int)))) return rc;
-    if ((rc = ensure((void**)&s->d_iters, B * sizeof(int)))) return rc;
+    ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
+    ENSURE(s->d_jf, 2 * B * nf * w);               // [raw impulses | folded forces]
+    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(s->d_z, z, B * nz * w, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->d_jf, jf, B * nf * w, hipMemcpyHostToDevice));
@@ -1227,7 +1246,7 @@ int dojo_get_diagnostics(DojoHandle s, double* diag) {
     if (!s) { g_err = "dojo_get_diagnostics: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     if (!s->d_diag) {
-        HIPCHK(hipMalloc((void**)&s->d_diag, (size_t)s->B * 2 * sizeof(double)));
+        ENSURE(s->d_diag, (size_t)s->B * 2 * sizeof(double));
         HIPCHK(hipMemset(s->d_diag, 0, (size_t)s->B * 2 * sizeof(double)));
     }
     HIPCHK(hipDeviceSynchronize());
@@ -1262,54 +1281,39 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
     if (!s || !z0 || H < 1) { g_err = "dojo_rollout_dev: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu;
-    int rc;
-    if ((rc = ensure(&s->d_z, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_zn, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_vel, B * 6 * s->M.Nb * w))) return rc;
-    if ((rc = ensure(&s->d_jimp, B * (s->M.n_joint_imp + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w))) return rc;
-    if (storage && (rc = ensure(&s->d_res, B * 6 * s->M.Nb * w))) return rc;
+    ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
+    ENSURE(s->d_vel, B * 6 * s->M.Nb * w); ENSURE(s->d_jimp, B * (s->M.n_joint_imp + 1) * w);
+    ENSURE(s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w);
+    if (storage) ENSURE(s->d_res, B * 6 * s->M.Nb * w);
     hipStream_t st = (hipStream_t)stream;
-    const char* cur = (const char*)z0;
-    int slot = -1;
-    { int rc_ = acquire_slot(s, &slot); if (rc_ != DOJO_OK) return rc_; }
-    HIPCHK(hipEventRecord(s->ring[slot].a, st));
+    const char* cur = (const char*)z0;      // the state a group's next step starts from; behind the loops: the last state (the same buffer for every group)
+    int slot = -1; TRY(begin_timing(s, &slot, st));
     // Environments are independent, so the batch is rolled out as NG groups on internal streams: a group whose step
     // contains an environment that runs into max_iter (one wavefront, ~5x the mean step time) delays only itself while
     // the other groups' launches keep the GPU busy.  (ROCm runs at most GPU_MAX_HW_QUEUES streams concurrently.)
-    if ((rc = join_groups(s, st))) return rc;                  // (asynchronous steps still in flight)
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight)
     const size_t NG = group_count(s, H >= 2);
-    size_t per = ((B + NG - 1) / NG + 63) / 64 * 64;            // group size: multiple of 64 (and so of the environments per wave)
-    if (NG > 1) {
-        if ((rc = ensure_groups(s, NG))) return rc;
-        HIPCHK(hipEventRecord(s->fork_event, st));
-    }
-    const char* last = cur;
-    for (size_t gi = 0; gi < NG; ++gi) {
-        const size_t env0 = gi * per;
-        if (env0 >= B) break;
-        const int nenv = (int)std::min(per, B - env0);
-        hipStream_t gs = NG > 1 ? s->gstreams[gi] : st;
-        if (NG > 1) HIPCHK(hipStreamWaitEvent(gs, s->fork_event, 0));
-        const char* c = (const char*)z0;
+    const Partition P(B, NG);
+    const Mode m = step_mode(s, NG, false, true);
+    ForkGuard guard{s, st, NG > 1};
+    if (NG > 1) { TRY(ensure_groups(s, NG)); HIPCHK(hipEventRecord(s->fork_event, st)); }
+    for (size_t gi = 0; gi < P.groups(); ++gi) {
+        const Span sp = P.span(gi, NG > 1 ? s->gstreams[gi] : st);
+        if (NG > 1) HIPCHK(hipStreamWaitEvent(sp.stream, s->fork_event, 0));
+        cur = (const char*)z0;
         for (int k = 0; k < H; ++k) {
             char* nxt = Z ? (char*)Z + (size_t)k * B * nz * w : (char*)((k & 1) ? s->d_z : s->d_zn);
             const char* uk = (U && nu) ? (const char*)U + (size_t)k * B * nu * w : nullptr;
             void* sk = storage ? (char*)storage + (size_t)k * B * 25 * s->M.Nb * w : nullptr;
-            s->chained_now = true;
-            rc = launch_any(s, c, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, s->d_vel, s->d_jimp, s->d_csg, nullptr, nullptr, gs, false, env0, nenv, nullptr, sk);
-            s->chained_now = false;
-            if (rc != DOJO_OK) return rc;
-            c = nxt;
+            TRY(launch_any(s, StepIO{cur, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, nullptr, nullptr, nullptr, sk}, sp, m));
+            cur = nxt;
         }
-        last = c;
-        if (NG > 1) { HIPCHK(hipEventRecord(s->gevents[gi], gs)); HIPCHK(hipStreamWaitEvent(st, s->gevents[gi], 0)); }
+        if (NG > 1) { HIPCHK(hipEventRecord(s->gevents[gi], sp.stream)); HIPCHK(hipStreamWaitEvent(st, s->gevents[gi], 0)); }
     }
-    cur = last;
-    { DojoSim::Ev3& e = s->ring[slot]; HIPCHK(hipEventRecord(e.b, st)); e.has_mid = false; e.n = H; e.used = true; s->last_slot = slot; }
+    TRY(end_timing(s, slot, false, H, st));
     if (!Z && cur != (const char*)s->d_zn) HIPCHK(hipMemcpyAsync(s->d_zn, cur, B * nz * w, hipMemcpyDeviceToDevice, st));
     s->have_solution = true; s->have_grad = false;
-    return DOJO_OK;
+    return guard.done();
 }
 
 int dojo_rollout_dev(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* stream) {
@@ -1374,8 +1378,11 @@ int dojo_contact_gradients_dev(DojoHandle s, const void* z, const void* u, void*
     if (!s->d_sol) { g_err = "dojo_contact_gradients_dev: no differentiable step (dz/du requested) has been run on this handle"; return DOJO_ERR_INVALID; }
     if (s->M.Nc == 0) return DOJO_OK;
     HIPCHK(hipSetDevice(s->device));
-    { int rcj = join_groups(s, (hipStream_t)stream); if (rcj != DOJO_OK) return rcj; }
-    return launch_any(s, z, u, s->d_zn ? s->d_zn : (void*)z, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, true, 0, -1, dc);
+    int slot = -1;
+    TRY(refuse_unsupported(s, false, true));
+    TRY(join_groups(s, (hipStream_t)stream));
+    const StepIO io{z, u, s->d_zn ? s->d_zn : (void*)z, nullptr, nullptr, nullptr, nullptr, dc, nullptr};
+    return launch_any(s, io, whole_batch(s, (hipStream_t)stream), step_mode(s, 1).with(PH_ALL, &slot));
 }
 int dojo_contact_gradients(DojoHandle s, void* dc) {
     Enter enter_(s);
@@ -1469,8 +1476,7 @@ int dojo_step_minimal_dev(DojoHandle s, const void* x, const void* u, void* x_ne
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb;
     int rc;
-    if ((rc = ensure(&s->d_z, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_zn, B * nz * w))) return rc;
+    ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
     // (asynchronous handle: environment groups of the previous call may still read d_z / write d_zn, and the kernels that follow
     //  the step on `stream` read what its groups write -- both sides of the step are joined into the caller's stream here)
     if ((rc = join_groups(s, (hipStream_t)stream))) return rc;
@@ -1495,13 +1501,10 @@ int dojo_minimal_gradients_dev(DojoHandle s, const void* x, const void* u, void*
     const size_t B = s->B, w = s->w, Nb = s->M.Nb, nz = 13 * Nb, nx = 12 * Nb, nu = s->M.nu, nm = 2 * nu;
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if ((rc = ensure(&s->d_z, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_zn, B * nz * w))) return rc;
-    if ((rc = ensure(&s->d_dz, B * nx * nx * w))) return rc;
-    if ((rc = ensure(&s->d_du, B * nx * (nu + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_jm, B * nx * (nm + 1) * sizeof(double)))) return rc;
-    if ((rc = ensure(&s->d_jt, B * nx * (nm + 1) * sizeof(double)))) return rc;
-    if ((rc = ensure(&s->d_jb, B * Nb * 12 * 24 * sizeof(double)))) return rc;
+    ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
+    ENSURE(s->d_dz, B * nx * nx * w); ENSURE(s->d_du, B * nx * (nu + 1) * w);
+    ENSURE(s->d_jm, B * nx * (nm + 1) * sizeof(double)); ENSURE(s->d_jt, B * nx * (nm + 1) * sizeof(double));
+    ENSURE(s->d_jb, B * Nb * 12 * 24 * sizeof(double));
     if ((rc = join_groups(s, st))) return rc;              // (asynchronous handle: see dojo_step_minimal_dev)
     if ((rc = dojo_minimal_to_maximal_dev(s, x, s->d_z, stream))) return rc;
     if ((rc = dojo_step_dev(s, s->d_z, u, s->d_zn, status, iters, s->d_dz, s->d_du, stream))) return rc;
@@ -1533,11 +1536,9 @@ int dojo_minimal_gradients(DojoHandle s, const void* x, const void* u, void* x_n
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nu = s->M.nu, nm = 2 * nu;
     int rc;
-    if ((rc = ensure(&s->d_x, B * (nm + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_xn, B * (nm + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_u, B * (nu + 1) * w))) return rc;
-    if ((rc = ensure((void**)&s->d_status, B * sizeof(int)))) return rc;
-    if ((rc = ensure((void**)&s->d_iters, B * sizeof(int)))) return rc;
+    ENSURE(s->d_x, B * (nm + 1) * w); ENSURE(s->d_xn, B * (nm + 1) * w);
+    ENSURE(s->d_u, B * (nu + 1) * w);
+    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
     DevBuf bjx, bju;
     HIPCHK(bjx.alloc(B * nm * nm * w)); HIPCHK(bju.alloc(B * nm * (nu + 1) * w));
     void *d_jx = bjx.p, *d_ju = bju.p;
@@ -1560,8 +1561,8 @@ static int coords_host(DojoHandle s, const void* in, void* out, size_t n_in, siz
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w;
     int rc;
-    if ((rc = ensure(&s->d_x, B * (2 * s->M.nu + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_cz, B * 13 * s->M.Nb * w))) return rc;       // not d_z: that is the state dojo_contact_gradients re-linearizes at
+    ENSURE(s->d_x, B * (2 * s->M.nu + 1) * w);
+    ENSURE(s->d_cz, B * 13 * s->M.Nb * w);       // not d_z: that is the state dojo_contact_gradients re-linearizes at
     void* din = to_max ? s->d_x : s->d_cz; void* dout = to_max ? s->d_cz : s->d_x;
     HIPCHK(hipMemcpy(din, in, B * n_in * w, hipMemcpyHostToDevice));
     rc = to_max ? dojo_minimal_to_maximal_dev(s, din, dout, nullptr) : dojo_maximal_to_minimal_dev(s, din, dout, nullptr);
@@ -1615,11 +1616,9 @@ int dojo_step_minimal(DojoHandle s, const void* x, const void* u, void* x_next, 
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nm = 2 * s->M.nu, nu = s->M.nu;
     int rc;
-    if ((rc = ensure(&s->d_x, B * (nm + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_xn, B * (nm + 1) * w))) return rc;
-    if ((rc = ensure(&s->d_u, B * (nu + 1) * w))) return rc;
-    if ((rc = ensure((void**)&s->d_status, B * sizeof(int)))) return rc;
-    if ((rc = ensure((void**)&s->d_iters, B * sizeof(int)))) return rc;
+    ENSURE(s->d_x, B * (nm + 1) * w); ENSURE(s->d_xn, B * (nm + 1) * w);
+    ENSURE(s->d_u, B * (nu + 1) * w);
+    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
     HIPCHK(hipMemcpy(s->d_x, x, B * nm * w, hipMemcpyHostToDevice));
     if (u && nu) HIPCHK(hipMemcpy(s->d_u, u, B * nu * w, hipMemcpyHostToDevice));
     rc = dojo_step_minimal_dev(s, s->d_x, (u && nu) ? s->d_u : nullptr, s->d_xn, s->d_status, s->d_iters, nullptr);
