@@ -1,0 +1,177 @@
+// dojo_adjoint.hpp -- reverse sweep over the recorded IFT Jacobians of a rollout (dojo_rollout_adjoint_dev; no counterpart in the reference,
+// which differentiates one step at a time: src/gradients/state.jl:69-126).
+//
+// Per environment b, with g_k the cotangent of the loss w.r.t. the state after step k (tangent coordinates [x; v; phi; omega] per body):
+//
+//     lambda <- g_{H-1}
+//     for k = H-1 .. 0:   failed step (status[k][b] != 0):  gU[k][b] <- 0,                    lambda <- 0      (by select: its Jacobians are never read)
+//                         else:                             gU[k][b] <- DU_k[b]^T lambda,     lambda <- DZ_k[b]^T lambda
+//                         if k > 0: lambda <- lambda + g_{k-1}
+//     gz[b] <- lambda
+//
+// The Jacobians are in the device layout of dojo_step_dev: column-major per environment, DZ[k][b][c][r] = d x_{k+1}[r] / d x_k[c], so that a
+// COLUMN is contiguous and (DZ^T lambda)[c] is the dot product of that column with lambda.  The job is H transposed mat-vecs over matrices that
+// are read exactly once: HBM streaming with a serial dependency through lambda.
+//
+// Mapping: one workgroup of 256 lanes per environment, one launch for all H steps.  lambda lives in LDS as fp64, double-buffered, and so does the
+// cotangent g_k that joins it (4 nx doubles in all; g_{k-1} is fetched while step k runs); one barrier per step.  Sixteen lanes (a DPP row) share a column: lane j of the row takes the 16-byte pieces j, j + 16, ... of it (nx = 12 Nb: every
+// column starts 16-byte aligned and holds whole pieces in both dtypes), multiplies them in fp64 with its rows of lambda, and the row's sixteen
+// partial sums meet in four DPP rotations.  A row keeps COLS columns in flight; the work of a step is a flat list of (column group, piece) items and
+// the loads of item i + 1 are issued before the arithmetic of item i -- across the barrier too: the first loads of step k - 1 leave before step k ends.
+// The summation order is fixed by (nx, dtype) alone: no atomics, results are bit-identical from run to run and do not depend on the batch size or on
+// where in the batch an environment sits.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "dojo_math.hpp"
+
+namespace dj {
+namespace adjoint {
+
+template <class TIO> struct Args {
+    const TIO* DZ;          // [H][B][nx][nx]
+    const TIO* DU;          // [H][B][nu][nx] (unused when gU is null)
+    const TIO* G;           // [H][B][nx] (cot_space 0) or [H][B][13 Nb] (cot_space 1)
+    const TIO* Z;           // [H][B][13 Nb], cot_space 1 only
+    const int* status;      // [H][B] or null
+    TIO* gU;                // [H][B][nu] or null
+    TIO* gz;                // [B][nx] or null
+    int H, B, nx, nu, cot_space;
+};
+
+constexpr int THREADS = 256, ROW = 16, COLS = 4, TEAMS = THREADS / ROW;     // lanes per workgroup, per column, columns in flight per row, rows
+inline size_t lds_bytes(int nx) { return (size_t)4 * nx * sizeof(double); }     // lambda and g, double-buffered
+
+#if defined(__HIPCC__)
+template <class TIO> struct Piece;                                          // the 16 bytes a lane loads at once
+template <> struct Piece<float>  { typedef float4 type;  static constexpr int N = 4; };
+template <> struct Piece<double> { typedef double2 type; static constexpr int N = 2; };
+__device__ __forceinline__ void unpack(const float4& v, double (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+__device__ __forceinline__ void unpack(const double2& v, double (&o)[2]) { o[0] = v.x; o[1] = v.y; }
+
+template <int CTRL> __device__ __forceinline__ double dpp(double v) {
+    return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true), __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true));
+}
+// sum over the 16 lanes of a DPP row; every lane ends with the same bits (each stage adds the two halves of a period, in either order)
+__device__ __forceinline__ double row_sum(double v) {
+    v += dpp<0x128>(v);     // row_ror:8
+    v += dpp<0x124>(v);     // row_ror:4
+    v += dpp<0x122>(v);     // row_ror:2
+    v += dpp<0x121>(v);     // row_ror:1
+    return v;
+}
+
+// g_k[c] of environment b in tangent coordinates.  cot_space 1: the cotangent is given w.r.t. the state (x, v, q, omega) and pulled back through
+// dq = q (x) (0, phi) (dojo_math.hpp: LVᵀmat), i.e. g_phi = vector part of conj(q) (x) g_q; x, v, omega are copied.  A 4-byte state stands for
+// q / |q| (as the step kernels read it).
+template <class TIO> __device__ __forceinline__ double cotangent(const Args<TIO>& A, const TIO* G, const TIO* Z, int k, int b, int c) {
+    const size_t kb = (size_t)k * A.B + b;
+    if (A.cot_space == 0) return (double)G[kb * A.nx + c];
+    const int body = c / 12, i = c % 12;
+    const size_t o = (kb * (size_t)(A.nx / 12) + body) * 13;
+    if (i < 6) return (double)G[o + i];
+    if (i >= 9) return (double)G[o + i + 1];
+    double q[4], g[4];
+    for (int n = 0; n < 4; ++n) { q[n] = (double)Z[o + 6 + n]; g[n] = (double)G[o + 6 + n]; }
+    if (sizeof(TIO) < sizeof(double)) {
+        const double iq = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        for (int n = 0; n < 4; ++n) q[n] *= iq;
+    }
+    // conj(q) (x) g = (s gs + v.gv, s gv - gs v - v x gv)
+    const int a = i - 6, a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+    return q[0] * g[1 + a] - g[0] * q[1 + a] - (q[1 + a1] * g[1 + a2] - q[1 + a2] * g[1 + a1]);
+}
+
+template <class TIO>
+__global__ void __launch_bounds__(THREADS) rollout_adjoint_kernel(const Args<TIO> A) {
+    typedef typename Piece<TIO>::type P;
+    constexpr int V = Piece<TIO>::N;
+    extern __shared__ __align__(16) double lds_[];                          // lambda [2][nx] | g [2][nx]
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x, team = tid / ROW, j = tid % ROW;
+    const int H = A.H, B = A.B, nx = A.nx, nu = A.gU ? A.nu : 0;
+    const int nM = (nx + ROW * V - 1) / (ROW * V);                          // pieces of a column per lane
+    const TIO* const DZ = DJ_GLOBAL_PTR(const TIO, A.DZ); const TIO* const DU = DJ_GLOBAL_PTR(const TIO, A.DU);
+    const TIO* const G = DJ_GLOBAL_PTR(const TIO, A.G);   const TIO* const Z = DJ_GLOBAL_PTR(const TIO, A.Z);
+    const int* const status = DJ_GLOBAL_PTR(const int, A.status);
+    TIO* const gU = DJ_GLOBAL_PTR(TIO, A.gU); TIO* const gz = DJ_GLOBAL_PTR(TIO, A.gz);
+    double* const lam_ = lds_; double* const g_ = lds_ + 2 * nx;
+
+    // the columns of step k: [c0, nx) of DZ (lambda; step 0 feeds gz alone), then the nu columns of DU (gU).  All of it is uniform over the workgroup.
+    auto first_col = [&](int k) { return (k == 0 && !gz) ? nx : 0; };
+    auto failed = [&](int k) { return status != nullptr && status[(size_t)k * B + b] != 0; };
+    // (an even number: the two piece buffers below take turns, and every step starts in the first; the odd one out is an item past the last group, whose
+    //  lanes re-read one cached piece and write nothing)
+    auto items_of = [&](int k) { return (k < 0 || failed(k)) ? 0 : ((nx + nu - first_col(k) + TEAMS * COLS - 1) / (TEAMS * COLS) * nM + 1) / 2 * 2; };
+    // loads of item `it` of step k: this lane's piece m of its row's COLS columns of group g.  Always COLS loads, so that the wait in front of the
+    // arithmetic can count them: a lane whose piece or column does not exist reads the first piece of the step's first column instead (and drops it).
+    auto issue = [&](int k, int it, P (&v)[COLS]) {
+        const int g = it / nM, m = it - g * nM, r0 = (m * ROW + j) * V, cb = first_col(k) + g * TEAMS * COLS + team;
+        const size_t kb = (size_t)k * B + b;
+#pragma unroll
+        for (int i = 0; i < COLS; ++i) {
+            const bool ok = cb + i * TEAMS < nx + nu && r0 < nx;
+            const int c = ok ? cb + i * TEAMS : first_col(k), r = ok ? r0 : 0;
+            const TIO* col = c < nx ? DZ + (kb * nx + c) * nx : DU + (kb * A.nu + (c - nx)) * nx;
+            v[i] = *reinterpret_cast<const P*>(col + r);
+        }
+    };
+
+    for (int c = tid; c < nx; c += THREADS) { lam_[c] = 0.0; g_[((H - 1) & 1) * nx + c] = cotangent(A, G, Z, H - 1, b, c); }
+    // Two piece buffers take turns: a copy from "next" to "current" would have to wait for the loads it is meant to leave in flight.
+    int p = 0, nit = items_of(H - 1);
+    P buf0[COLS], buf1[COLS];
+    if (nit) issue(H - 1, 0, buf0);
+    __syncthreads();
+    for (int k = H - 1; k >= 0; --k) {
+        // lambda_k = (what step k + 1 left) + g_k, formed where it is read; g_{k-1} goes to LDS for the next step meanwhile
+        const double* lam = lam_ + p * nx; const double* gk = g_ + (k & 1) * nx; double* lam_next = lam_ + (p ^ 1) * nx;
+        const int nit_next = items_of(k - 1), c0 = first_col(k);
+        const size_t kb = (size_t)k * B + b;
+        if (k > 0) for (int c = tid; c < nx; c += THREADS) g_[((k - 1) & 1) * nx + c] = cotangent(A, G, Z, k - 1, b, c);
+        double acc[COLS];
+#pragma unroll
+        for (int i = 0; i < COLS; ++i) acc[i] = 0.0;
+        auto stage = [&](int it, const P (&cur)[COLS], P (&nxt)[COLS]) {
+            // the next item: of this step, else the first of step k - 1 -- else this one again, so that a wait always has COLS younger loads to count
+            const bool more = it + 1 < nit;
+            issue((more || !nit_next) ? k : k - 1, more ? it + 1 : nit_next ? 0 : it, nxt);
+            const int g = it / nM, m = it - g * nM, r0 = (m * ROW + j) * V;
+            const bool have = r0 < nx;
+            const int rl = have ? r0 : 0;
+            double l[V];
+#pragma unroll
+            for (int n = 0; n < V; ++n) l[n] = lam[rl + n] + gk[rl + n];
+#pragma unroll
+            for (int i = 0; i < COLS; ++i) {
+                double x[V]; unpack(cur[i], x);
+#pragma unroll
+                for (int n = 0; n < V; ++n) acc[i] = fma(have ? x[n] : 0.0, have ? l[n] : 0.0, acc[i]);
+            }
+            if (m == nM - 1) {                                              // the group's columns are complete: lane i of the row writes column i
+                double mine = 0.0;
+#pragma unroll
+                for (int i = 0; i < COLS; ++i) { const double s_ = row_sum(acc[i]); if (j == i) mine = s_; acc[i] = 0.0; }
+                const int c = c0 + g * TEAMS * COLS + team + j * TEAMS;
+                if (j < COLS && c < nx + nu) {
+                    if (c >= nx) gU[kb * A.nu + (c - nx)] = (TIO)mine;
+                    else if (k > 0) lam_next[c] = mine;
+                    else gz[(size_t)b * nx + c] = (TIO)mine;
+                }
+            }
+        };
+        for (int it = 0; it < nit; it += 2) { stage(it, buf0, buf1); stage(it + 1, buf1, buf0); }
+        if (failed(k)) {                                                    // nothing flows through a failed step
+            for (int c = tid; c < nx; c += THREADS) {
+                if (k > 0) lam_next[c] = 0.0;
+                else if (gz) gz[(size_t)b * nx + c] = (TIO)0.0;
+            }
+            for (int c = tid; c < nu; c += THREADS) gU[kb * A.nu + c] = (TIO)0.0;
+            if (nit_next) issue(k - 1, 0, buf0);
+        }
+        __syncthreads();
+        p ^= 1; nit = nit_next;
+    }
+}
+#endif
+
+}  // namespace adjoint
+}  // namespace dj

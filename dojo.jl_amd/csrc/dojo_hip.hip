@@ -9,7 +9,9 @@
 #include <hip/hip_runtime.h>
 #include "dojo_host.hpp"
 #include "dojo_coords.hpp"
+#include "dojo_adjoint.hpp"
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -927,6 +929,15 @@ bool load() {
 const char* why(int rc) { return get_error_string ? get_error_string(rc) : "RCCL error"; }
 }
 
+// dojo_rollout_adjoint_dev: the reverse sweep over recorded Jacobians (dojo_adjoint.hpp), one workgroup per environment, one launch
+template <class TIO>
+int launch_adjoint(const DojoSim* s, int H, const void* DZ, const void* DU, const void* G, int cot_space, const void* Z, const int* status, void* gU, void* gz, hipStream_t st) {
+    const dj::adjoint::Args<TIO> A{(const TIO*)DZ, (const TIO*)DU, (const TIO*)G, (const TIO*)Z, status, (TIO*)gU, (TIO*)gz, H, s->B, 12 * s->M.Nb, (int)s->M.nu, cot_space};
+    hipLaunchKernelGGL((dj::adjoint::rollout_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::adjoint::THREADS), dj::adjoint::lds_bytes(A.nx), st, A);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1277,10 +1288,11 @@ int dojo_gradients(DojoHandle s, void* dz, void* du) {
 
 // simulate! with pre-sampled controls (src/simulation/simulate.jl:16-37): H steps, each fed with the previous step's
 // internal next state; storage != null records save_to_storage! rows [H][B][Nb][25] of every solved step
-static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* storage, void* stream) {
+// DZ / DU != null: the IFT Jacobians of every step as well, [H][B][nx][nx] / [H][B][nu][nx] in the device layout of dojo_step_dev (dojo_rollout_record_dev)
+static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* storage, void* stream, void* DZ = nullptr, void* DU = nullptr) {
     if (!s || !z0 || H < 1) { g_err = "dojo_rollout_dev: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu;
+    size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, nx = 12 * s->M.Nb;
     ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
     ENSURE(s->d_vel, B * 6 * s->M.Nb * w); ENSURE(s->d_jimp, B * (s->M.n_joint_imp + 1) * w);
     ENSURE(s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w);
@@ -1305,7 +1317,9 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
             char* nxt = Z ? (char*)Z + (size_t)k * B * nz * w : (char*)((k & 1) ? s->d_z : s->d_zn);
             const char* uk = (U && nu) ? (const char*)U + (size_t)k * B * nu * w : nullptr;
             void* sk = storage ? (char*)storage + (size_t)k * B * 25 * s->M.Nb * w : nullptr;
-            TRY(launch_any(s, StepIO{cur, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, nullptr, nullptr, nullptr, sk}, sp, m));
+            void* dzk = DZ ? (char*)DZ + (size_t)k * B * nx * nx * w : nullptr;
+            void* duk = (DU && nu) ? (char*)DU + (size_t)k * B * nx * nu * w : nullptr;
+            TRY(launch_any(s, StepIO{cur, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, dzk, duk, nullptr, sk}, sp, m));
             cur = nxt;
         }
         if (NG > 1) { HIPCHK(hipEventRecord(s->gevents[gi], sp.stream)); HIPCHK(hipStreamWaitEvent(st, s->gevents[gi], 0)); }
@@ -1325,6 +1339,87 @@ int dojo_simulate_dev(DojoHandle s, const void* z0, const void* U, int32_t H, vo
     Enter enter_(s);
     if (!storage) { g_err = "dojo_simulate_dev: storage must not be NULL (use dojo_rollout_dev for record = false)"; return DOJO_ERR_INVALID; }
     return rollout_core(s, z0, U, H, Z, status, storage, stream);
+}
+
+// dojo_rollout_dev plus the IFT Jacobians of every step, left on the device for dojo_rollout_adjoint_dev
+int dojo_rollout_record_dev(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* DZ, void* DU, void* stream) {
+    Enter enter_(s);
+    if (!s || !z0 || H < 1 || !Z || !DZ || (!DU && s->M.nu > 0)) { g_err = "dojo_rollout_record_dev: bad argument (z0, Z, DZ and -- with nu > 0 -- DU are required, H >= 1)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_unsupported(s, true, false));
+    return rollout_core(s, z0, U, H, Z, status, nullptr, stream, DZ, DU);
+}
+
+int dojo_rollout_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void* DU, const void* G, int32_t cot_space, const void* Z, const int32_t* status,
+                             void* gU, void* gz, void* stream) {
+    Enter enter_(s);
+    if (!s) { g_err = "dojo_rollout_adjoint_dev: bad argument"; return DOJO_ERR_INVALID; }
+    if (H < 1) { g_err = "dojo_rollout_adjoint_dev: H must be >= 1"; return DOJO_ERR_INVALID; }
+    if (!DZ || !G) { g_err = "dojo_rollout_adjoint_dev: DZ and G must not be NULL"; return DOJO_ERR_INVALID; }
+    if (cot_space != 0 && cot_space != 1) { g_err = "dojo_rollout_adjoint_dev: cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
+    if (cot_space == 1 && !Z) { g_err = "dojo_rollout_adjoint_dev: cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
+    if (s->M.nu == 0) gU = nullptr;
+    if (gU && !DU) { g_err = "dojo_rollout_adjoint_dev: gU needs DU"; return DOJO_ERR_INVALID; }
+    if ((((uintptr_t)DZ) | (gU ? (uintptr_t)DU : (uintptr_t)0)) & 15) { g_err = "dojo_rollout_adjoint_dev: DZ and DU must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
+    if (dj::adjoint::lds_bytes(12 * s->M.Nb) > 65536) { g_err = "dojo_rollout_adjoint_dev: supports at most 170 bodies (lambda is kept in LDS)"; return DOJO_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the Jacobians)
+    if (!gU && !gz) return DOJO_OK;
+    return s->dtype == DOJO_DTYPE_F32 ? launch_adjoint<float>(s, H, DZ, DU, G, cot_space, Z, status, gU, gz, st)
+                                      : launch_adjoint<double>(s, H, DZ, DU, G, cot_space, Z, status, gU, gz, st);
+}
+
+// host pointers: upload, record on the device, reverse sweep, download -- the Jacobians never cross PCIe
+int dojo_rollout_gradients(DojoHandle s, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space, void* Z, int32_t* status, void* gU, void* gz) {
+    Enter enter_(s);
+    if (!s || !z0 || !G || H < 1 || (cot_space != 0 && cot_space != 1)) { g_err = "dojo_rollout_gradients: bad argument"; return DOJO_ERR_INVALID; }
+    TRY(refuse_unsupported(s, true, false));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
+    const size_t record = HB * nx * (nx + nu) * w;
+    // everything this call allocates: the buffers below (each rounded up as the allocator does) and the workspaces rollout_core and the
+    // differentiable step launches take on first use (ensure_workspaces: sized for the whole batch, so one group's geometry gives them all)
+    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
+    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + up(HB * nu * w) + up(B * nx * w)
+                  + ((U && nu) ? up(HB * nu * w) : 0);
+    {
+        const Geometry ge = geometry_of(s, whole_batch(s, nullptr), true);
+        const size_t wT = sizeof(double);
+        if (!s->d_z) need += up(B * nz * w);
+        if (!s->d_zn) need += up(B * nz * w);
+        if (!s->d_vel) need += up(B * 6 * s->M.Nb * w);
+        if (!s->d_jimp) need += up(B * (s->M.n_joint_imp + 1) * w);
+        if (!s->d_csg) need += up(B * (csg_per(s) * s->M.Nc + 1) * w);
+        if (!s->d_sol) need += up(B * s->M.S * dj::sol_record<8, true>() * wT);
+        if (ge.quad && !s->d_fac) need += up(ge.waves_total * dj::FAC_PER_LANE * ge.lanes * wT);
+        if (ge.quad && !s->d_lu) need += up(ge.waves_total * dj::LU_PER_LANE * ge.lanes * wT);
+        if (ge.ypark_stride && !s->d_ypark) need += up(ge.waves_total * (size_t)ge.ypark_stride * wT);
+        if (ge.msg_stride && !s->d_msg) need += up(B * (size_t)ge.msg_stride * wT);
+        if (ge.quad && std::isfinite(refine_threshold(s))) { if (!s->d_blk) need += up(ge.waves_total * 90 * ge.lanes * wT); if (!s->d_flag) need += up(B * sizeof(int)); }
+    }
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b) {
+        g_err = "dojo_rollout_gradients: the record of " + std::to_string(record) + " bytes (H B nx (nx + nu) scalars; " + std::to_string(need) + " bytes with the other buffers of the call) does not fit into the "
+                + std::to_string(free_b) + " bytes of free device memory";
+        return DOJO_ERR_INVALID;
+    }
+    DevBuf dz0, dU, dG, dZ, dS, dDZ, dDU, dgU, dgz;
+    HIPCHK(dz0.alloc(B * nz * w)); HIPCHK(dG.alloc(HB * ng * w)); HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
+    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w)); HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w));
+    HIPCHK(hipMemcpy(dz0.p, z0, B * nz * w, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dG.p, G, HB * ng * w, hipMemcpyHostToDevice));
+    if (U && nu) { HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(hipMemcpy(dU.p, U, HB * nu * w, hipMemcpyHostToDevice)); }
+    TRY(rollout_core(s, dz0.p, dU.p, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p));
+    TRY(dojo_rollout_adjoint_dev(s, H, dDZ.p, dDU.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, dgU.p, dgz.p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
+    if (gU && nu) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
+    return DOJO_OK;
 }
 
 static int rollout_host(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, void* storage, int32_t* status);

@@ -40,7 +40,8 @@ def lib():
                   "dojo_last_kernel_ms", "dojo_last_kernel_times", "dojo_kernel_time_totals",
                   "dojo_minimal_to_maximal", "dojo_maximal_to_minimal", "dojo_step_minimal",
                   "dojo_minimal_to_maximal_dev", "dojo_maximal_to_minimal_dev", "dojo_step_minimal_dev",
-                  "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev"):
+                  "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
+                  "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients"):
             getattr(L, f).restype = C.c_int
         L.dojo_destroy.restype = None
         _lib = L
@@ -54,7 +55,8 @@ EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error",
                     "dojo_minimal_to_maximal_dev", "dojo_maximal_to_minimal_dev", "dojo_step_minimal_dev",
                     "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
                     "dojo_simulate", "dojo_simulate_dev", "dojo_observe", "dojo_observe_dev",
-                    "dojo_set_external_force", "dojo_set_external_force_dev"]
+                    "dojo_set_external_force", "dojo_set_external_force_dev",
+                    "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients"]
 
 
 # columns of a Storage row (src/simulation/storage.jl:15-24)
@@ -223,6 +225,33 @@ class BatchedMechanism:
         st = np.empty((H, B), np.int32)
         _chk(lib().dojo_rollout(self.h, _p(z0), _p(U), H, _p(Z), _p(st)))
         return Z, st
+
+    def rollout_gradients(self, z0, U=None, G=None, steps=None, cot_space="tangent"):
+        """Reverse-mode rollout (dojo_rollout_gradients): the rollout of `rollout`, and the gradient of a trajectory loss w.r.t. the controls
+        and the initial state from the recorded IFT Jacobians, which stay on the device.  G [H,B,nx] (cot_space "tangent": the cotangent of
+        the loss w.r.t. the state after every step in the coordinates of dz, [x; v; phi; omega] per body) or [H,B,13Nb] ("state": w.r.t.
+        the state vector itself).  Returns (Z [H,B,13Nb], status [H,B], gU [H,B,nu], gz0 [B,nx] in tangent coordinates); nothing flows
+        through a failed step.  GRAD_CONSISTENT (set_gradient_mode) is the mode whose chain is the derivative of the rollout."""
+        B, s = self.batch, self.spec
+        z0 = self._arr(z0, (B, s.nz))
+        if cot_space not in ("tangent", "state", 0, 1):
+            raise ValueError("cot_space must be 'tangent' or 'state'")
+        cs = 1 if cot_space in ("state", 1) else 0
+        if G is None:
+            raise ValueError("rollout_gradients needs the cotangents G of the loss w.r.t. the state after every step")
+        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
+        if G.shape != (H, B, s.nz if cs else s.nx):
+            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
+        if steps is not None and int(steps) != H:
+            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
+        if U is not None and s.nu:
+            U = self._arr(U, (H, B, s.nu))
+        else:
+            U = None
+        Z = np.empty((H, B, s.nz), self.np_dtype); st = np.empty((H, B), np.int32)
+        gU = np.zeros((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
+        _chk(lib().dojo_rollout_gradients(self.h, _p(z0), _p(U), H, _p(G), cs, _p(Z), _p(st), _p(gU) if s.nu else None, _p(gz)))
+        return Z, st, gU, gz
 
     def set_external_force(self, fext):
         """set_external_force!(body; force, torque) for all bodies: fext [B, Nb, 6] = [Fext (world); τext (body frame)],

@@ -166,6 +166,22 @@ function Dojo.simulate!(bm::BatchedMechanism{T}, z0::Matrix{T}, U::Array{T,3}; o
     return Z, status
 end
 
+"""
+reverse-mode rollout (no counterpart in Dojo.jl): the rollout of `simulate!` and the gradient of a trajectory loss from the recorded IFT
+Jacobians, which stay on the device.  G is the cotangent of the loss w.r.t. the state after every step: [nx, B, H] in the coordinates of
+dz (`cot_space = :tangent`) or [nz, B, H] w.r.t. the state vector (`:state`).  -> Z[nz, B, H], status[B, H], gU[nu, B, H], gz0[nx, B]
+(tangent coordinates).  `set_gradient_mode!(bm, 1)` is the mode whose chain is the derivative of the rollout.
+"""
+function rollout_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, U::Array{T,3}, G::Array{T,3}; cot_space::Symbol=:tangent, opts=Dojo.SolverOptions{Float64}()) where T
+    set_options!(bm, opts)
+    H = size(G, 3)
+    Z = Array{T}(undef, bm.nz, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    gU = zeros(T, bm.nu, bm.batch, H); gz = Matrix{T}(undef, bm.nx, bm.batch)
+    check(@ccall $(fn(:dojo_rollout_gradients))(bm.handle::Ptr{Cvoid}, z0::Ptr{T}, (bm.nu > 0 ? pointer(U) : C_NULL)::Ptr{T}, H::Int32, G::Ptr{T},
+                                                Int32(cot_space === :state ? 1 : 0)::Int32, Z::Ptr{T}, status::Ptr{Int32}, gU::Ptr{T}, gz::Ptr{T})::Cint)
+    return Z, status, gU, gz
+end
+
 "which states the IFT data blocks are evaluated at: 0 = as the reference does after step! (post-update_state!), 1 = at the solved step (consistent)"
 set_gradient_mode!(bm::BatchedMechanism, mode::Integer) = check(@ccall $(fn(:dojo_set_gradient_mode))(bm.handle::Ptr{Cvoid}, Int32(mode)::Int32)::Cint)
 

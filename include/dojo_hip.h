@@ -335,6 +335,47 @@ int  dojo_simulate(DojoHandle h, const void* z0, const void* U, int32_t H, void*
 int  dojo_simulate_dev(DojoHandle h, const void* z0, const void* U, int32_t H, void* Z, void* storage,
                        int32_t* status, void* stream);
 
+/* Reverse-mode rollouts (no counterpart in the reference, which differentiates one step at a time: get_maximal_gradients!,
+ * src/gradients/state.jl:69-126): the gradient of a trajectory loss w.r.t. the control sequence and the initial state, from the IFT
+ * Jacobians of every step, which stay on the device.
+ *
+ * dojo_rollout_record_dev = dojo_rollout_dev plus the record: DZ [H][B][nx][nx] and DU [H][B][nu][nx] in the device layout of
+ * dojo_step_dev (column-major per environment: DZ[k][b][c][r] = d x_{k+1}[r] / d x_k[c]; DU is ignored when nu = 0).  Z is required
+ * (the reverse sweep may need it); status may be NULL.  Same environment groups and stream choreography as dojo_rollout_dev: joined into
+ * `stream` at the end, never pipelined.  The Jacobians are those of the handle's gradient mode (dojo_set_gradient_mode):
+ * DOJO_GRAD_CONSISTENT is the one whose chain is the derivative of the rollout (rows of step k and columns of step k + 1 then live in
+ * the same tangent coordinates [x; v; phi; omega] per body); DOJO_GRAD_REFERENCE chains the reference's literal blocks.  ImpactContact,
+ * LinearContact and body-body contact mechanisms: DOJO_ERR_UNSUPPORTED, nothing launched.
+ * Memory of the record: H * B * nx * (nx + nu) * w bytes (w = 8 or 4) -- Ant (nx 156, nu 14), fp32, B = 4096, H = 20: 8.7 GB.
+ *
+ * dojo_rollout_adjoint_dev: ONE kernel launch on `stream`, no synchronization; plain device buffers in the handle's dtype, from
+ * dojo_rollout_record_dev or from the caller's own dojo_step_dev loop (closed-loop policies).  With g_k the cotangent of the loss w.r.t.
+ * the state after step k (k = 0 .. H-1), per environment b:
+ *     lambda <- g_{H-1}
+ *     for k = H-1 .. 0:   if status && status[k][b] != 0:  gU[k][b] <- 0;                  lambda <- 0
+ *                         else:                            gU[k][b] <- DU_k[b]^T lambda;   lambda <- DZ_k[b]^T lambda
+ *                         if k > 0: lambda <- lambda + g_{k-1}
+ *     gz[b] <- lambda                                      (tangent coordinates, [B][nx])
+ * Nothing flows through a failed step, by select: its Jacobians need not be finite and are not read.
+ * cot_space 0: G [H][B][nx] is given in the tangent coordinates of dz; Z may be NULL.  cot_space 1: G [H][B][13Nb] is given in state
+ * coordinates and Z [H][B][13Nb] is required: per body g_x, g_v, g_omega are copied and g_phi = vector part of conj(q) (x) g_q (the
+ * transpose of dq/dphi = LV^T mat(q); fp32 handles use q / |q|, as the kernels do on load).
+ * status, gU [H][B][nu] and gz may each be NULL; gU is ignored when nu = 0.  Every product and sum is fp64, lambda stays fp64 between the
+ * steps, outputs are rounded once.  No atomics and a fixed summation order: results are bit-identical from run to run and do not depend
+ * on the batch size or on an environment's position in the batch.  DOJO_ERR_INVALID (text on the handle): H < 1, NULL DZ or G,
+ * cot_space = 1 without Z, gU without DU (nu > 0), DZ or DU not 16-byte aligned (the kernel reads them in 16-byte pieces; every
+ * environment's block and column then is, since nx = 12 Nb -- hipMalloc and torch allocations are aligned, an offset into one need not be).
+ *
+ * dojo_rollout_gradients (host pointers): uploads z0, U (NULL = zeros), G; allocates the record on the device, records, runs the reverse
+ * sweep, downloads Z [H][B][13Nb], status [H][B], gU [H][B][nu], gz [B][nx] (each may be NULL).  The Jacobians never cross PCIe.  A record
+ * that does not fit into the free device memory: DOJO_ERR_INVALID with the byte count in the text, before any launch. */
+int  dojo_rollout_record_dev(DojoHandle h, const void* z0, const void* U, int32_t H, void* Z, int32_t* status,
+                             void* DZ, void* DU, void* stream);
+int  dojo_rollout_adjoint_dev(DojoHandle h, int32_t H, const void* DZ, const void* DU, const void* G, int32_t cot_space,
+                              const void* Z, const int32_t* status, void* gU, void* gz, void* stream);
+int  dojo_rollout_gradients(DojoHandle h, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space,
+                            void* Z, int32_t* status, void* gU, void* gz);
+
 /* get_state(environment) of DojoEnvironments (environments.jl:100-102; quadruped_sampling.jl:67-72): the minimal state
  * of the mechanism, and with contact_forces != 0 the normal impulse of every contact of the last step clamped to
  * [-1, 1] behind it (get_state(::AntARS), ant_ars.jl:72-80).  obs [B, 2*nu (+ Nc)].
