@@ -98,6 +98,22 @@ template <class S> DJ_HD void mask_tS(S* o, const double* A, int n, const S* c) 
 }
 
 template <class S> struct PoseVel { S x[3], v[3], q[4], w[3]; };
+// a body's state out of a maximal state vector z [13 Nb] of the ABI type / the origin (the parent of a root joint)
+template <class S, class TIO> DJ_HD PoseVel<S> load_body(const TIO* z, int b) {
+    PoseVel<S> p;
+    for (int i = 0; i < 3; ++i) { p.x[i] = S((double)z[13 * b + i]); p.v[i] = S((double)z[13 * b + 3 + i]); p.w[i] = S((double)z[13 * b + 10 + i]); }
+    double q_[4];
+    for (int i = 0; i < 4; ++i) q_[i] = (double)z[13 * b + 6 + i];
+    if (sizeof(TIO) < sizeof(double)) {    // a narrower ABI type cannot hold a unit quaternion: the state it stands for is (x, v, q/|q|, ω), as in the step / IFT kernels (DJ_LANE_SETUP)
+        const double iq_ = 1.0 / sqrt(q_[0] * q_[0] + q_[1] * q_[1] + q_[2] * q_[2] + q_[3] * q_[3]);
+        for (int i = 0; i < 4; ++i) q_[i] *= iq_;
+    }
+    for (int i = 0; i < 4; ++i) p.q[i] = S(q_[i]);
+    return p;
+}
+template <class S> DJ_HD PoseVel<S> origin_body() {
+    PoseVel<S> p; for (int i = 0; i < 3; ++i) { p.x[i] = S(0.0); p.v[i] = S(0.0); p.w[i] = S(0.0); } p.q[0] = S(1.0); p.q[1] = S(0.0); p.q[2] = S(0.0); p.q[3] = S(0.0); return p;
+}
 
 // child body state from the parent's state and the joint's minimal coordinates / velocities (minimal.jl:205-232)
 template <class S>

@@ -10,6 +10,7 @@
 #include "dojo_host.hpp"
 #include "dojo_coords.hpp"
 #include "dojo_adjoint.hpp"
+#include "dojo_policy.hpp"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -132,6 +133,7 @@ struct DojoSim {
     int* d_flag = nullptr;              // [B] environments the plain step kernel deferred to the refining kernels
     double refine_w = -1.0;             // refine once max γ/s of an environment exceeds this (dojo_set_refinement); < 0: chosen from the tolerances
     int *d_status = nullptr, *d_iters = nullptr;
+    void* d_pu = nullptr;               // [B][nu] the controls of a closed-loop rollout whose caller records none (dojo_rollout_policy_dev)
     // iteration cap + continuation kernel (dojo_set_iteration_cap; dojo_device.hpp Globals::iter_cap)
     int iter_cap = -1;                  // < 0: automatic (DOJO_DEFAULT_ITERATION_CAP where the continuation kernel exists), 0: off, > 0: as given
     void* d_resume = nullptr;           // [B][CARRY_PER_ENV] loop scalars of the solves the step kernel left unfinished
@@ -167,21 +169,7 @@ void handle_set_error(::DojoSim* s, const std::string& m) { std::lock_guard<std:
 namespace ckern {
 using namespace dj;
 using namespace dj::coords;
-template <class S, class TIO> __device__ __forceinline__ PoseVel<S> load_body(const TIO* z, int b) {
-    PoseVel<S> p;
-    for (int i = 0; i < 3; ++i) { p.x[i] = S((double)z[13 * b + i]); p.v[i] = S((double)z[13 * b + 3 + i]); p.w[i] = S((double)z[13 * b + 10 + i]); }
-    double q_[4];
-    for (int i = 0; i < 4; ++i) q_[i] = (double)z[13 * b + 6 + i];
-    if (sizeof(TIO) < sizeof(double)) {    // a narrower ABI type cannot hold a unit quaternion: the state it stands for is (x, v, q/|q|, ω), as in the step / IFT kernels (DJ_LANE_SETUP)
-        const double iq_ = 1.0 / sqrt(q_[0] * q_[0] + q_[1] * q_[1] + q_[2] * q_[2] + q_[3] * q_[3]);
-        for (int i = 0; i < 4; ++i) q_[i] *= iq_;
-    }
-    for (int i = 0; i < 4; ++i) p.q[i] = S(q_[i]);
-    return p;
-}
-template <class S> __device__ __forceinline__ PoseVel<S> origin_body() {
-    PoseVel<S> p; for (int i = 0; i < 3; ++i) { p.x[i] = S(0.0); p.v[i] = S(0.0); p.w[i] = S(0.0); } p.q[0] = S(1.0); p.q[1] = S(0.0); p.q[2] = S(0.0); p.q[3] = S(0.0); return p;
-}
+// (load_body, origin_body: dojo_coords.hpp -- the policy kernel of dojo_policy.hpp reads bodies the same way)
 // get_next_state (src/mechanism/get.jl:126-134) of a body whose velocities are its solution: x + dt v, q (x) xi(w)
 template <class S> __device__ __forceinline__ void advance_body(PoseVel<S>& p, double dt) {
     for (int i = 0; i < 3; ++i) p.x[i] = p.x[i] + p.v[i] * dt;
@@ -938,6 +926,23 @@ int launch_adjoint(const DojoSim* s, int H, const void* DZ, const void* DU, cons
     return DOJO_OK;
 }
 
+// dojo_rollout_policy_dev: the controller between two steps of an environment group (dojo_policy.hpp) -- o = get_state of z, written to `obs` (null = not
+// recorded), u = U_ff + E (bias + W ((o - mean) .* scale)) written to `u` (null: the observation alone).  csg: the handle's [s; gamma] of the previous step, null = the neutral 1.0.
+// All pointers are batch-level; the launch covers the span's environments on the span's stream.
+template <class TIO>
+int launch_policy(const DojoSim* s, const DojoPolicy& p, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
+    const int Nc = p.contact_forces ? s->M.Nc : 0, nobs = 2 * s->M.nu + Nc;
+    const dj::policy::Args<TIO> A{(const dj::NodeP<double>*)s->d_nodes, (const TIO*)z, (const TIO*)csg, (const TIO*)p.W, (const TIO*)p.bias, (const TIO*)p.mean, (const TIO*)p.scale,
+                                  (const TIO*)uff, (TIO*)obs, (TIO*)u, (int)sp.env0, sp.nenv, s->M.Nb, s->M.nu, Nc, nobs, p.act_off, p.na, p.per_env ? 1 : 0, s->M.dt};
+    hipLaunchKernelGGL((dj::policy::rollout_policy_kernel<TIO>), dim3((unsigned)((sp.nenv + dj::policy::ENVS - 1) / dj::policy::ENVS)), dim3(dj::policy::THREADS),
+                       dj::policy::lds_bytes(nobs), sp.stream, A);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
+int launch_policy_any(const DojoSim* s, const DojoPolicy& p, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
+    return s->dtype == DOJO_DTYPE_F32 ? launch_policy<float>(s, p, z, csg, uff, obs, u, sp) : launch_policy<double>(s, p, z, csg, uff, obs, u, sp);
+}
+
 } // namespace
 
 extern "C" {
@@ -1289,7 +1294,10 @@ int dojo_gradients(DojoHandle s, void* dz, void* du) {
 // simulate! with pre-sampled controls (src/simulation/simulate.jl:16-37): H steps, each fed with the previous step's
 // internal next state; storage != null records save_to_storage! rows [H][B][Nb][25] of every solved step
 // DZ / DU != null: the IFT Jacobians of every step as well, [H][B][nx][nx] / [H][B][nu][nx] in the device layout of dojo_step_dev (dojo_rollout_record_dev)
-static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* storage, void* stream, void* DZ = nullptr, void* DU = nullptr) {
+// pol != null (dojo_rollout_policy_dev; checked by the caller): U is the feed-forward term and the controls of step k are made on the group's stream, directly in front of
+// the step, by the policy kernel -- into U_out[k] (null: one [B][nu] buffer of the handle, a group's launches being serial); OBS [H+1][B][nobs] or null records what it saw
+static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* storage, void* stream, void* DZ = nullptr, void* DU = nullptr,
+                        const DojoPolicy* pol = nullptr, void* OBS = nullptr, void* U_out = nullptr) {
     if (!s || !z0 || H < 1) { g_err = "dojo_rollout_dev: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, nx = 12 * s->M.Nb;
@@ -1297,6 +1305,8 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
     ENSURE(s->d_vel, B * 6 * s->M.Nb * w); ENSURE(s->d_jimp, B * (s->M.n_joint_imp + 1) * w);
     ENSURE(s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w);
     if (storage) ENSURE(s->d_res, B * 6 * s->M.Nb * w);
+    if (pol && !U_out) ENSURE(s->d_pu, B * nu * w);
+    const size_t nobs = pol ? 2 * nu + (pol->contact_forces ? (size_t)s->M.Nc : 0) : 0;
     hipStream_t st = (hipStream_t)stream;
     const char* cur = (const char*)z0;      // the state a group's next step starts from; behind the loops: the last state (the same buffer for every group)
     int slot = -1; TRY(begin_timing(s, &slot, st));
@@ -1316,12 +1326,18 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
         for (int k = 0; k < H; ++k) {
             char* nxt = Z ? (char*)Z + (size_t)k * B * nz * w : (char*)((k & 1) ? s->d_z : s->d_zn);
             const char* uk = (U && nu) ? (const char*)U + (size_t)k * B * nu * w : nullptr;
+            if (pol) {
+                char* upol = U_out ? (char*)U_out + (size_t)k * B * nu * w : (char*)s->d_pu;
+                TRY(launch_policy_any(s, *pol, cur, (k > 0 || pol->contact_init) ? s->d_csg : nullptr, uk, OBS ? (char*)OBS + (size_t)k * B * nobs * w : nullptr, upol, sp));
+                uk = upol;
+            }
             void* sk = storage ? (char*)storage + (size_t)k * B * 25 * s->M.Nb * w : nullptr;
             void* dzk = DZ ? (char*)DZ + (size_t)k * B * nx * nx * w : nullptr;
             void* duk = (DU && nu) ? (char*)DU + (size_t)k * B * nx * nu * w : nullptr;
             TRY(launch_any(s, StepIO{cur, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, dzk, duk, nullptr, sk}, sp, m));
             cur = nxt;
         }
+        if (pol && OBS) TRY(launch_policy_any(s, *pol, cur, s->d_csg, nullptr, (char*)OBS + (size_t)H * B * nobs * w, nullptr, sp));      // the observation of the final state
         if (NG > 1) { HIPCHK(hipEventRecord(s->gevents[gi], sp.stream)); HIPCHK(hipStreamWaitEvent(st, s->gevents[gi], 0)); }
     }
     TRY(end_timing(s, slot, false, H, st));
@@ -1347,6 +1363,60 @@ int dojo_rollout_record_dev(DojoHandle s, const void* z0, const void* U, int32_t
     if (!s || !z0 || H < 1 || !Z || !DZ || (!DU && s->M.nu > 0)) { g_err = "dojo_rollout_record_dev: bad argument (z0, Z, DZ and -- with nu > 0 -- DU are required, H >= 1)"; return DOJO_ERR_INVALID; }
     TRY(refuse_unsupported(s, true, false));
     return rollout_core(s, z0, U, H, Z, status, nullptr, stream, DZ, DU);
+}
+
+// Closed-loop rollouts: what is refused, before anything is launched or allocated
+static int refuse_policy(DojoHandle s, const void* z0, const DojoPolicy* p, int32_t H, const char* who) {
+    const std::string w_ = std::string(who) + ": ";
+    if (!s || !z0 || !p || !p->W) { g_err = w_ + "bad argument (handle, z0, policy and policy->W are required)"; return DOJO_ERR_INVALID; }
+    if (H < 1) { g_err = w_ + "H must be >= 1"; return DOJO_ERR_INVALID; }
+    if (s->M.nu == 0) { g_err = w_ + "the mechanism has no inputs"; return DOJO_ERR_INVALID; }
+    if (p->na < 1 || p->act_off < 0 || (long long)p->act_off + p->na > (long long)s->M.nu) { g_err = w_ + "the policy must drive inputs act_off .. act_off + na - 1 inside 0 .. nu - 1, na >= 1"; return DOJO_ERR_INVALID; }
+    if (p->contact_init && !s->have_solution) { g_err = w_ + "contact_init = 1 needs a step on this handle"; return DOJO_ERR_INVALID; }
+    if (s->M.has_loop) { g_err = w_ + "the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    if (p->contact_forces && s->M.contact_model == 2) { g_err = w_ + "contact forces are not available for LinearContact mechanisms"; return DOJO_ERR_UNSUPPORTED; }
+    if (dj::policy::lds_bytes(2 * s->M.nu + s->M.Nc) > 65536) { g_err = w_ + "supports at most 2048 observations per environment (they are kept in LDS)"; return DOJO_ERR_UNSUPPORTED; }
+    return DOJO_OK;
+}
+
+int dojo_rollout_policy_dev(DojoHandle s, const void* z0, const DojoPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, int32_t* status, void* stream) {
+    Enter enter_(s);
+    TRY(refuse_policy(s, z0, policy, H, "dojo_rollout_policy_dev"));
+    const DojoPolicy p = *policy;      // (the caller's struct is read during the call only)
+    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, nullptr, nullptr, &p, OBS, U_out);
+}
+
+// host pointers (the members of *policy too): upload, roll out on the device, download
+int dojo_rollout_policy(DojoHandle s, const void* z0, const DojoPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, int32_t* status) {
+    Enter enter_(s);
+    TRY(refuse_policy(s, z0, policy, H, "dojo_rollout_policy"));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, na = (size_t)policy->na, Bw = policy->per_env ? B : 1;
+    const size_t nobs = 2 * nu + (policy->contact_forces ? (size_t)s->M.Nc : 0);
+    DojoPolicy p = *policy;
+    DevBuf dz0, dW, db, dm, dsc, dUff, dZ, dO, dU, dS;
+    auto up = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
+        *dst = nullptr;
+        if (!src) return DOJO_OK;
+        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        *dst = d.p;
+        return DOJO_OK;
+    };
+    const void* z0d = nullptr;
+    TRY(up(dz0, z0, B * nz * w, &z0d)); TRY(up(dW, policy->W, Bw * na * nobs * w, &p.W)); TRY(up(db, policy->bias, Bw * na * w, &p.bias));
+    TRY(up(dm, policy->mean, nobs * w, &p.mean)); TRY(up(dsc, policy->scale, nobs * w, &p.scale)); TRY(up(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
+    if (Z) HIPCHK(dZ.alloc(HB * nz * w));
+    if (OBS) HIPCHK(dO.alloc((HB + B) * nobs * w));
+    if (U_out) HIPCHK(dU.alloc(HB * nu * w));
+    if (status) HIPCHK(dS.alloc(HB * sizeof(int)));
+    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, nullptr, nullptr, &p, dO.p, dU.p));
+    HIPCHK(hipDeviceSynchronize());
+    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
+    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
+    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
+    if (Z) HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
+    return DOJO_OK;
 }
 
 int dojo_rollout_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void* DU, const void* G, int32_t cot_space, const void* Z, const int32_t* status,

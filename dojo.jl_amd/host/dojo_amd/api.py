@@ -41,7 +41,7 @@ def lib():
                   "dojo_minimal_to_maximal", "dojo_maximal_to_minimal", "dojo_step_minimal",
                   "dojo_minimal_to_maximal_dev", "dojo_maximal_to_minimal_dev", "dojo_step_minimal_dev",
                   "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
-                  "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients"):
+                  "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients", "dojo_rollout_policy_dev", "dojo_rollout_policy"):
             getattr(L, f).restype = C.c_int
         L.dojo_destroy.restype = None
         _lib = L
@@ -56,7 +56,16 @@ EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error",
                     "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
                     "dojo_simulate", "dojo_simulate_dev", "dojo_observe", "dojo_observe_dev",
                     "dojo_set_external_force", "dojo_set_external_force_dev",
-                    "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients"]
+                    "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients",
+                    "dojo_rollout_policy_dev", "dojo_rollout_policy"]
+
+
+class DojoPolicy(C.Structure):
+    """include/dojo_hip.h `DojoPolicy`: u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale)); the members are device pointers for
+    dojo_rollout_policy_dev and host pointers for dojo_rollout_policy"""
+    _fields_ = [("W", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p), ("U_ff", C.c_void_p),
+                ("per_env", C.c_int32), ("act_off", C.c_int32), ("na", C.c_int32), ("contact_forces", C.c_int32), ("contact_init", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 # columns of a Storage row (src/simulation/storage.jl:15-24)
@@ -252,6 +261,33 @@ class BatchedMechanism:
         gU = np.zeros((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
         _chk(lib().dojo_rollout_gradients(self.h, _p(z0), _p(U), H, _p(G), cs, _p(Z), _p(st), _p(gU) if s.nu else None, _p(gz)))
         return Z, st, gU, gz
+
+    def rollout_policy(self, z0, W, steps, bias=None, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):
+        """Closed-loop rollout (dojo_rollout_policy): simulate! with the affine feedback policy u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale))
+        evaluated on the device between the steps, o_k = the observation (`observe`) of the state step k starts from.  W [na, nobs] (one policy
+        for all environments) or [B, na, nobs] (one per environment), bias [na] / [B, na], mean, scale [nobs], U_ff [steps, B, nu]; the policy
+        drives the inputs act_off .. act_off + na - 1.  Returns (Z [H,B,13Nb], OBS [H+1,B,nobs], U [H,B,nu], status [H,B]): OBS[k] is what the
+        policy saw at step k (OBS[H]: the final state's), U[k] what step k was given."""
+        B, s = self.batch, self.spec
+        H = int(steps)
+        z0 = self._arr(z0, (B, s.nz))
+        W = np.ascontiguousarray(W, dtype=self.np_dtype)
+        if W.ndim not in (2, 3):
+            raise ValueError("W must be [na, nobs] or [B, na, nobs]")
+        per_env = W.ndim == 3
+        na = W.shape[-2]
+        nobs = 2 * s.nu + (len(s.contacts) if contact_forces else 0)
+        W = self._arr(W, (B, na, nobs) if per_env else (na, nobs))
+        bias = None if bias is None else self._arr(bias, (B, na) if per_env else (na,))
+        mean = None if mean is None else self._arr(mean, (nobs,))
+        scale = None if scale is None else self._arr(scale, (nobs,))
+        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        pol = DojoPolicy(ptr(W), ptr(bias), ptr(mean), ptr(scale), ptr(U_ff), int(per_env), int(act_off), int(na), int(bool(contact_forces)), int(contact_init), 0)
+        Z = np.empty((max(H, 0), B, s.nz), self.np_dtype); OBS = np.empty((max(H, 0) + 1, B, nobs), self.np_dtype)
+        U = np.empty((max(H, 0), B, s.nu), self.np_dtype); st = np.empty((max(H, 0), B), np.int32)
+        _chk(lib().dojo_rollout_policy(self.h, _p(z0), C.byref(pol), H, _p(Z), _p(OBS), _p(U), _p(st)))
+        return Z, OBS, U, st
 
     def set_external_force(self, fext):
         """set_external_force!(body; force, torque) for all bodies: fext [B, Nb, 6] = [Fext (world); τext (body frame)],

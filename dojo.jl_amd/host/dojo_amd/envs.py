@@ -77,5 +77,39 @@ class BatchedEnvironment:
         api._chk(api.lib().dojo_observe_dev(self.mechanism.h, None, C.c_void_p(obs.data_ptr()), int(self.contact_forces), self._stream()))
         return obs
 
+    def rollout_policy(self, theta, horizon, mean=None, scale=None, U_ff=None):
+        """`horizon` steps under the linear policy action = theta ((observation - mean) .* scale) in ONE call (dojo_rollout_policy_dev): the policy is
+        evaluated on the device between the steps, the environment groups run chained on the library's streams and are joined into torch's current
+        stream at the end.  theta [na, nobs] (shared) or [B, na, nobs] (one policy per environment), na = nu - n_unactuated actions behind the
+        unactuated leading inputs; mean, scale [nobs] or None; U_ff [horizon, B, nu] or None (feed-forward term).  Starts from the minimal state of
+        `initialize()`.  Returns (OBS [horizon + 1, B, nobs], U [horizon, B, nu], status [horizon, B]) as device tensors, without synchronizing:
+        OBS[k] is get_state before step k (contact entries of OBS[0]: the neutral 1.0), OBS[horizon] that of the final state.
+
+        This is the reference's simulate!(mechanism, steps, storage, control!) (src/simulation/simulate.jl:16-37): the state is carried in MAXIMAL
+        coordinates from step to step.  The stepwise `step` re-projects through minimal coordinates at every step (step_minimal_coordinates!), as
+        DojoEnvironments' step! does; the two agree to the accuracy of the joint constraints, not bit for bit."""
+        import torch
+        B, nu = self.batch, self.spec.nu
+        H, na = int(horizon), nu - self.n_unactuated
+        dev = lambda t, shape: None if t is None else torch.as_tensor(t, device=self.device).to(self.torch_dtype).reshape(shape).contiguous()
+        theta = torch.as_tensor(theta, device=self.device).to(self.torch_dtype).contiguous()
+        per_env = theta.dim() == 3
+        if tuple(theta.shape) != ((B, na, self.nobs) if per_env else (na, self.nobs)):
+            raise ValueError("theta must be [%d, %d] or [%d, %d, %d], got %s" % (na, self.nobs, B, na, self.nobs, tuple(theta.shape)))
+        mean, scale, U_ff = dev(mean, (self.nobs,)), dev(scale, (self.nobs,)), dev(U_ff, (H, B, nu))
+        x0 = self._x.contiguous()
+        z0 = torch.empty(B, 13 * self.spec.Nb, dtype=self.torch_dtype, device=self.device)
+        L, h, ptr = api.lib(), self.mechanism.h, lambda t: None if t is None else t.data_ptr()
+        api._chk(L.dojo_minimal_to_maximal_dev(h, C.c_void_p(x0.data_ptr()), C.c_void_p(z0.data_ptr()), self._stream()))
+        OBS = torch.empty(H + 1, B, self.nobs, dtype=self.torch_dtype, device=self.device)
+        U = torch.empty(H, B, nu, dtype=self.torch_dtype, device=self.device)
+        status = torch.empty(H, B, dtype=torch.int32, device=self.device)
+        pol = api.DojoPolicy(ptr(theta), None, ptr(mean), ptr(scale), ptr(U_ff), int(per_env), self.n_unactuated, na, int(self.contact_forces), 0, 0)
+        api._chk(L.dojo_rollout_policy_dev(h, C.c_void_p(z0.data_ptr()), C.byref(pol), H, None, C.c_void_p(OBS.data_ptr()), C.c_void_p(U.data_ptr()),
+                                           C.c_void_p(status.data_ptr()), self._stream()))
+        self._keep = (x0, z0, theta, mean, scale, U_ff)          # inputs of kernels still in flight
+        self._stepped = True
+        return OBS, U, status
+
     def close(self):
         self.mechanism.close()

@@ -182,6 +182,36 @@ function rollout_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, U::Array{T,3}
     return Z, status, gU, gz
 end
 
+"mirror of `DojoPolicy` (include/dojo_hip.h): five pointers, six Int32"
+struct DojoPolicy
+    W::Ptr{Cvoid}; bias::Ptr{Cvoid}; mean::Ptr{Cvoid}; scale::Ptr{Cvoid}; U_ff::Ptr{Cvoid}
+    per_env::Int32; act_off::Int32; na::Int32; contact_forces::Int32; contact_init::Int32; reserved::Int32
+end
+
+"""
+closed-loop rollout: simulate!(mechanism, steps, storage, control!) with the affine feedback policy
+u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale)) evaluated on the device between the steps, o_k = get_state of the state step k starts from
+(minimal state, then the clamped contact impulses with `contact_forces`).  W[nobs, na] (one policy for all environments) or W[nobs, na, B] (one
+per environment; the transposes of the policy matrices: the ABI is row-major), bias[na] / [na, B], mean, scale[nobs], U_ff[nu, B, H]; the policy
+drives the inputs act_off + 1 : act_off + na.  -> Z[nz, B, H], OBS[nobs, B, H + 1], U[nu, B, H], status[B, H].
+"""
+function rollout_policy(bm::BatchedMechanism{T}, z0::Matrix{T}, W::Array{T}, H::Integer; bias::Union{Nothing,Array{T}}=nothing, mean::Union{Nothing,Vector{T}}=nothing,
+                        scale::Union{Nothing,Vector{T}}=nothing, U_ff::Union{Nothing,Array{T,3}}=nothing, act_off::Integer=0, contact_forces::Bool=false,
+                        contact_init::Integer=0, n_contacts::Integer=0, opts=Dojo.SolverOptions{Float64}()) where T
+    set_options!(bm, opts)
+    nobs = 2 * bm.nu + (contact_forces ? n_contacts : 0)
+    size(W, 1) == nobs || error("W must have nobs = $nobs rows (pass n_contacts with contact_forces)")
+    na = size(W, 2)
+    Z = Array{T}(undef, bm.nz, bm.batch, H); OBS = Array{T}(undef, nobs, bm.batch, H + 1)
+    U = Array{T}(undef, bm.nu, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve W bias mean scale U_ff begin
+        pol = Ref(DojoPolicy(p(W), p(bias), p(mean), p(scale), p(U_ff), Int32(ndims(W) == 3), Int32(act_off), Int32(na), Int32(contact_forces), Int32(contact_init), Int32(0)))
+        check(@ccall $(fn(:dojo_rollout_policy))(bm.handle::Ptr{Cvoid}, z0::Ptr{T}, pol::Ptr{DojoPolicy}, Int32(H)::Int32, Z::Ptr{T}, OBS::Ptr{T}, U::Ptr{T}, status::Ptr{Int32})::Cint)
+    end
+    return Z, OBS, U, status
+end
+
 "which states the IFT data blocks are evaluated at: 0 = as the reference does after step! (post-update_state!), 1 = at the solved step (consistent)"
 set_gradient_mode!(bm::BatchedMechanism, mode::Integer) = check(@ccall $(fn(:dojo_set_gradient_mode))(bm.handle::Ptr{Cvoid}, Int32(mode)::Int32)::Cint)
 

@@ -4,6 +4,10 @@ policies of one ARS iteration are the B environments of one `BatchedEnvironment`
 linear policy -> step -> reward stay on the device (dojo_step_minimal_dev + dojo_observe_dev, torch for the policy).
 
     python examples/ant_ars_device.py --iterations 5 --directions 256 --horizon 100
+
+--fused: the whole rollout of an iteration is ONE library call (BatchedEnvironment.rollout_policy -> dojo_rollout_policy_dev): the policy is evaluated
+by the library between the steps, on the streams of its environment groups, and rewards, health check and the normaliser update are one vectorised
+pass over the recorded observations and controls afterwards (`rollout_policy_fused`).
 """
 import argparse
 import os
@@ -66,7 +70,29 @@ def rollout_policy(theta, env, normalizer, horizon, observe=True):
     return rewards
 
 
-def train(iterations=5, directions=256, top=32, horizon=100, step_size=0.02, noise=0.03, dtype="f32", seed=0, log=print):
+def rollout_policy_fused(theta, env, normalizer, horizon, observe=True):
+    """`rollout_policy` with the loop on the device: one BatchedEnvironment.rollout_policy call, then rewards and the health check in one pass over
+    OBS [H+1, B, nobs] and U [H, B, nu].  The normaliser is FROZEN during the rollout (the stepwise loop updates it before every step) and updated
+    afterwards with the observations the policies saw while their environment was alive; the state is carried in maximal coordinates (simulate!),
+    not re-projected through minimal coordinates at every step."""
+    import torch
+    env.initialize()
+    dt, nx = env.spec.timestep, env.nx
+    var = (normalizer.m2 / normalizer.n.clamp(min=1.0)).clamp(min=1e-2)
+    OBS, U, _ = env.rollout_policy(theta, horizon, mean=normalizer.mean, scale=1.0 / var.sqrt())
+    before, after, action = OBS[:-1], OBS[1:], U[:, :, env.n_unactuated:]
+    forward_reward = 100.0 * (after[:, :, 0] - before[:, :, 0]) / dt
+    control_cost = 0.05 / 10.0 * (action * action).sum(dim=2)
+    contact_cost = 0.5e-3 * (after[:, :, nx:] ** 2).sum(dim=2)
+    reward = forward_reward - control_cost - contact_cost + 0.05
+    ok = torch.isfinite(after).all(dim=2) & (after[:, :, 2] >= 0.2) & (after[:, :, 2] <= 1.0)
+    alive = torch.cat([torch.ones_like(ok[:1]), torch.cumprod(ok[:-1].to(torch.int32), dim=0).bool()], dim=0)      # alive[k]: healthy after every step before k
+    if observe:
+        normalizer.observe(before[alive])
+    return torch.where(alive, reward, torch.zeros_like(reward)).sum(dim=0)
+
+
+def train(iterations=5, directions=256, top=32, horizon=100, step_size=0.02, noise=0.03, dtype="f32", seed=0, log=print, fused=False):
     """ARS-V2 update (examples/learning/ars.jl `train`): theta += step / (top * sigma_R) * sum_top (R+ - R-) delta."""
     import torch
     from dojo_amd.envs import BatchedEnvironment
@@ -81,7 +107,7 @@ def train(iterations=5, directions=256, top=32, horizon=100, step_size=0.02, noi
         t0 = time.time()
         delta = torch.randn(directions, na, nobs, dtype=env.torch_dtype, device=env.device, generator=gen)
         thetas = torch.cat([theta + noise * delta, theta - noise * delta], dim=0)
-        R = rollout_policy(thetas, env, normalizer, horizon)
+        R = (rollout_policy_fused if fused else rollout_policy)(thetas, env, normalizer, horizon)
         Rp, Rm = R[:directions], R[directions:]
         order = torch.argsort(torch.maximum(Rp, Rm), descending=True)[:top]
         sigma = R.std().clamp(min=1e-6)                               # σ_r = std(rewards) over all rollouts (ant_ars.jl:152)
@@ -101,5 +127,6 @@ if __name__ == "__main__":
     ap.add_argument("--top", type=int, default=32)
     ap.add_argument("--horizon", type=int, default=100)
     ap.add_argument("--dtype", default="f32")
+    ap.add_argument("--fused", action="store_true", help="one dojo_rollout_policy_dev call per iteration instead of the stepwise loop")
     a = ap.parse_args()
-    train(a.iterations, a.directions, a.top, a.horizon, dtype=a.dtype)
+    train(a.iterations, a.directions, a.top, a.horizon, dtype=a.dtype, fused=a.fused)

@@ -376,6 +376,50 @@ int  dojo_rollout_adjoint_dev(DojoHandle h, int32_t H, const void* DZ, const voi
 int  dojo_rollout_gradients(DojoHandle h, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space,
                             void* Z, int32_t* status, void* gU, void* gz);
 
+/* Closed-loop rollouts: simulate!(mechanism, steps, storage, control!) (src/simulation/simulate.jl:16-37) with a controller that looks at the
+ * state -- an affine feedback policy per environment, evaluated ON THE DEVICE between the steps (csrc/dojo_policy.hpp: observation, normalisation,
+ * policy and control assembly in one launch), so that the call keeps the choreography of dojo_rollout_dev: environment groups chained on internal
+ * streams, one join into `stream` at the end, no synchronization.  u = -K x (examples/control/cartpole_lqr.jl), the linear policy on normalised
+ * observations of examples/learning/ant_ars.jl:78-115 (per_env = 1: one perturbed policy per environment) and PD around a reference (U_ff) are
+ * all of this form:
+ *
+ *     u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale)),      o_k = get_state of the state step k starts from
+ *
+ * Per environment b and step k = 0 .. H-1, with z_0 = z0 and z_k = Z[k-1]:
+ *   1. o_k = [maximal_to_minimal(z_k) (2 nu); c_k (Nc, only with contact_forces)], c_k = the normal impulse of every contact of step k - 1 clamped
+ *      to [-1, 1] -- exactly dojo_observe_dev's vector; c_0 by contact_init.  o_k is rounded once to the handle dtype and written to OBS[k][b];
+ *      THE POLICY CONSUMES THE ROUNDED VALUE: what is recorded is what it saw, and U_out can be recomputed from OBS alone.
+ *   2. fp64: ohat_j = (o_j - mean_j) scale_j;  a_i = bias_i + sum_j W[i][j] ohat_j, in a summation order that depends on nobs alone.
+ *   3. u = U_ff[k][b] (or zeros); u[act_off + i] += a_i; rounded once to the handle dtype, written to U_out[k][b]; step k reads exactly that buffer.
+ *   4. step k, through the path of dojo_rollout_dev (external forces set on the handle stay in effect): Z[k], status[k].
+ * After the last step OBS[H] = the observation of the final state (a reward r(o_k, u_k, o_{k+1}) needs it).
+ * OBS [H+1][B][nobs], U_out [H][B][nu], Z [H][B][13Nb], status [H][B]: each may be NULL (with Z NULL the final state stays readable with
+ * dojo_get_state).  Results are bit-identical from run to run and do not depend on the number of environment groups, on an environment's position
+ * in the batch, or on per_env = 0 against the same W given B times.
+ * The struct is host memory, read during the call; its members are device pointers (dojo_rollout_policy_dev) or host pointers (dojo_rollout_policy).
+ * Refused before anything is launched, text on the handle -- DOJO_ERR_INVALID: NULL handle, z0, policy or W; H < 1; nu = 0; na < 1, act_off < 0 or
+ * act_off + na > nu; contact_init = 1 on a handle without a solution.  DOJO_ERR_UNSUPPORTED: a mechanism with a kinematic loop, contact_forces with
+ * LinearContact (both as dojo_observe_dev); more than 2048 observations.
+ * Not part of it: reverse mode through the policy (OBS and U_out are what such a sweep needs), non-affine policies, rewards / termination, running
+ * normaliser statistics, control clamping, re-projection to minimal coordinates between the steps (DojoEnvironments' step! does that; simulate! does not). */
+typedef struct DojoPolicy {
+    const void* W;        /* [Bw][na][nobs] row-major, handle dtype, device memory; required            */
+    const void* bias;     /* [Bw][na] or NULL (zeros)                                                   */
+    const void* mean;     /* [nobs] or NULL (zeros): shared by all environments                         */
+    const void* scale;    /* [nobs] or NULL (ones)                                                      */
+    const void* U_ff;     /* [H][B][nu] or NULL (zeros): feed-forward / exploration / PD reference term */
+    int32_t per_env;      /* 1: Bw = B (one policy per environment, ARS directions); 0: Bw = 1 (shared) */
+    int32_t act_off, na;  /* the policy drives inputs act_off .. act_off + na - 1 (E above)             */
+    int32_t contact_forces;/* nobs = 2 nu + (contact_forces ? Nc : 0), as dojo_observe_dev              */
+    int32_t contact_init; /* contact entries of o_0: 0 = the neutral 1.0 (a fresh ContactConstraint, what
+                             BatchedEnvironment.get_state returns before the first step), 1 = the handle's last solution */
+    int32_t reserved;
+} DojoPolicy;
+int  dojo_rollout_policy_dev(DojoHandle h, const void* z0, const DojoPolicy* policy, int32_t H,
+                             void* Z, void* OBS, void* U_out, int32_t* status, void* stream);
+int  dojo_rollout_policy(DojoHandle h, const void* z0, const DojoPolicy* policy, int32_t H,
+                         void* Z, void* OBS, void* U_out, int32_t* status);
+
 /* get_state(environment) of DojoEnvironments (environments.jl:100-102; quadruped_sampling.jl:67-72): the minimal state
  * of the mechanism, and with contact_forces != 0 the normal impulse of every contact of the last step clamped to
  * [-1, 1] behind it (get_state(::AntARS), ant_ars.jl:72-80).  obs [B, 2*nu (+ Nc)].
