@@ -81,45 +81,83 @@ template <class TIO> __device__ __forceinline__ double cotangent(const Args<TIO>
     return q[0] * g[1 + a] - g[0] * q[1 + a] - (q[1 + a1] * g[1 + a2] - q[1 + a2] * g[1 + a1]);
 }
 
+// ---- the column pipeline: what this sweep and the closed-loop one (dojo_policy_adjoint.hpp) stream DZ and DU with ----
+// The columns of a step are [c0, nx) of DZ followed by ncol - nx columns of DU; its work is a flat list of (column group, piece) items.
+template <class TIO> struct Columns {
+    const TIO *DZ, *DU;     // the record (global address space)
+    int B, nx, nu;          // nu: the columns of a DU block (the stride of the record, whether or not they are swept)
+    int ncol, nM;           // nx + the DU columns that are swept; pieces of a column per lane
+};
+template <class TIO> __device__ __forceinline__ Columns<TIO> columns(const TIO* DZ, const TIO* DU, int B, int nx, int nu, int nu_swept) {
+    return Columns<TIO>{DZ, DU, B, nx, nu, nx + nu_swept, (nx + ROW * Piece<TIO>::N - 1) / (ROW * Piece<TIO>::N)};
+}
+// items of a step whose columns start at c0 (an even number: the two piece buffers of a sweep take turns, and every step starts in the first; the odd one
+// out is an item past the last group, whose lanes re-read one cached piece and write nothing)
+template <class TIO> __device__ __forceinline__ int items(const Columns<TIO>& C, int c0) { return ((C.ncol - c0 + TEAMS * COLS - 1) / (TEAMS * COLS) * C.nM + 1) / 2 * 2; }
+// loads of item `it` of step k of environment b: this lane's piece m of its row's COLS columns of group g.  Always COLS loads, so that the wait in front of
+// the arithmetic can count them: a lane whose piece or column does not exist reads the first piece of the step's first column instead (and drops it).
+template <class TIO> __device__ __forceinline__ void issue(const Columns<TIO>& C, int k, int b, int c0, int it, int team, int j, typename Piece<TIO>::type (&v)[COLS]) {
+    typedef typename Piece<TIO>::type P;
+    constexpr int V = Piece<TIO>::N;
+    const int nx = C.nx, g = it / C.nM, m = it - g * C.nM, r0 = (m * ROW + j) * V, cb = c0 + g * TEAMS * COLS + team;
+    const size_t kb = (size_t)k * C.B + b;
+#pragma unroll
+    for (int i = 0; i < COLS; ++i) {
+        const bool ok = cb + i * TEAMS < C.ncol && r0 < nx;
+        const int c = ok ? cb + i * TEAMS : c0, r = ok ? r0 : 0;
+        const TIO* col = c < nx ? C.DZ + (kb * nx + c) * nx : C.DU + (kb * C.nu + (c - nx)) * nx;
+        v[i] = *reinterpret_cast<const P*>(col + r);
+    }
+}
+// arithmetic of item `it`: the loaded pieces times (lam + gk), accumulated per column; when the group's columns are complete the row's sixteen partial
+// sums meet (row_sum) and lane i of the row hands column i to put(column, value)
+template <class TIO, class Put>
+__device__ __forceinline__ void consume(const Columns<TIO>& C, int c0, int it, int team, int j, const double* lam, const double* gk,
+                                        const typename Piece<TIO>::type (&cur)[COLS], double (&acc)[COLS], Put&& put) {
+    constexpr int V = Piece<TIO>::N;
+    const int nx = C.nx, g = it / C.nM, m = it - g * C.nM, r0 = (m * ROW + j) * V;
+    const bool have = r0 < nx;
+    const int rl = have ? r0 : 0;
+    double l[V];
+#pragma unroll
+    for (int n = 0; n < V; ++n) l[n] = lam[rl + n] + gk[rl + n];
+#pragma unroll
+    for (int i = 0; i < COLS; ++i) {
+        double x[V]; unpack(cur[i], x);
+#pragma unroll
+        for (int n = 0; n < V; ++n) acc[i] = fma(have ? x[n] : 0.0, have ? l[n] : 0.0, acc[i]);
+    }
+    if (m == C.nM - 1) {                                                // the group's columns are complete: lane i of the row writes column i
+        double mine = 0.0;
+#pragma unroll
+        for (int i = 0; i < COLS; ++i) { const double s_ = row_sum(acc[i]); if (j == i) mine = s_; acc[i] = 0.0; }
+        const int c = c0 + g * TEAMS * COLS + team + j * TEAMS;
+        if (j < COLS && c < C.ncol) put(c, mine);
+    }
+}
+
 template <class TIO>
 __global__ void __launch_bounds__(THREADS) rollout_adjoint_kernel(const Args<TIO> A) {
     typedef typename Piece<TIO>::type P;
-    constexpr int V = Piece<TIO>::N;
     extern __shared__ __align__(16) double lds_[];                          // lambda [2][nx] | g [2][nx]
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, team = tid / ROW, j = tid % ROW;
     const int H = A.H, B = A.B, nx = A.nx, nu = A.gU ? A.nu : 0;
-    const int nM = (nx + ROW * V - 1) / (ROW * V);                          // pieces of a column per lane
-    const TIO* const DZ = DJ_GLOBAL_PTR(const TIO, A.DZ); const TIO* const DU = DJ_GLOBAL_PTR(const TIO, A.DU);
     const TIO* const G = DJ_GLOBAL_PTR(const TIO, A.G);   const TIO* const Z = DJ_GLOBAL_PTR(const TIO, A.Z);
     const int* const status = DJ_GLOBAL_PTR(const int, A.status);
     TIO* const gU = DJ_GLOBAL_PTR(TIO, A.gU); TIO* const gz = DJ_GLOBAL_PTR(TIO, A.gz);
+    const Columns<TIO> C = columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DU), B, nx, A.nu, nu);
     double* const lam_ = lds_; double* const g_ = lds_ + 2 * nx;
 
     // the columns of step k: [c0, nx) of DZ (lambda; step 0 feeds gz alone), then the nu columns of DU (gU).  All of it is uniform over the workgroup.
     auto first_col = [&](int k) { return (k == 0 && !gz) ? nx : 0; };
     auto failed = [&](int k) { return status != nullptr && status[(size_t)k * B + b] != 0; };
-    // (an even number: the two piece buffers below take turns, and every step starts in the first; the odd one out is an item past the last group, whose
-    //  lanes re-read one cached piece and write nothing)
-    auto items_of = [&](int k) { return (k < 0 || failed(k)) ? 0 : ((nx + nu - first_col(k) + TEAMS * COLS - 1) / (TEAMS * COLS) * nM + 1) / 2 * 2; };
-    // loads of item `it` of step k: this lane's piece m of its row's COLS columns of group g.  Always COLS loads, so that the wait in front of the
-    // arithmetic can count them: a lane whose piece or column does not exist reads the first piece of the step's first column instead (and drops it).
-    auto issue = [&](int k, int it, P (&v)[COLS]) {
-        const int g = it / nM, m = it - g * nM, r0 = (m * ROW + j) * V, cb = first_col(k) + g * TEAMS * COLS + team;
-        const size_t kb = (size_t)k * B + b;
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) {
-            const bool ok = cb + i * TEAMS < nx + nu && r0 < nx;
-            const int c = ok ? cb + i * TEAMS : first_col(k), r = ok ? r0 : 0;
-            const TIO* col = c < nx ? DZ + (kb * nx + c) * nx : DU + (kb * A.nu + (c - nx)) * nx;
-            v[i] = *reinterpret_cast<const P*>(col + r);
-        }
-    };
+    auto items_of = [&](int k) { return (k < 0 || failed(k)) ? 0 : items(C, first_col(k)); };
 
     for (int c = tid; c < nx; c += THREADS) { lam_[c] = 0.0; g_[((H - 1) & 1) * nx + c] = cotangent(A, G, Z, H - 1, b, c); }
     // Two piece buffers take turns: a copy from "next" to "current" would have to wait for the loads it is meant to leave in flight.
     int p = 0, nit = items_of(H - 1);
     P buf0[COLS], buf1[COLS];
-    if (nit) issue(H - 1, 0, buf0);
+    if (nit) issue(C, H - 1, b, first_col(H - 1), 0, team, j, buf0);
     __syncthreads();
     for (int k = H - 1; k >= 0; --k) {
         // lambda_k = (what step k + 1 left) + g_k, formed where it is read; g_{k-1} goes to LDS for the next step meanwhile
@@ -130,33 +168,17 @@ __global__ void __launch_bounds__(THREADS) rollout_adjoint_kernel(const Args<TIO
         double acc[COLS];
 #pragma unroll
         for (int i = 0; i < COLS; ++i) acc[i] = 0.0;
+        auto put = [&](int c, double mine) {
+            if (c >= nx) gU[kb * A.nu + (c - nx)] = (TIO)mine;
+            else if (k > 0) lam_next[c] = mine;
+            else gz[(size_t)b * nx + c] = (TIO)mine;
+        };
         auto stage = [&](int it, const P (&cur)[COLS], P (&nxt)[COLS]) {
             // the next item: of this step, else the first of step k - 1 -- else this one again, so that a wait always has COLS younger loads to count
             const bool more = it + 1 < nit;
-            issue((more || !nit_next) ? k : k - 1, more ? it + 1 : nit_next ? 0 : it, nxt);
-            const int g = it / nM, m = it - g * nM, r0 = (m * ROW + j) * V;
-            const bool have = r0 < nx;
-            const int rl = have ? r0 : 0;
-            double l[V];
-#pragma unroll
-            for (int n = 0; n < V; ++n) l[n] = lam[rl + n] + gk[rl + n];
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) {
-                double x[V]; unpack(cur[i], x);
-#pragma unroll
-                for (int n = 0; n < V; ++n) acc[i] = fma(have ? x[n] : 0.0, have ? l[n] : 0.0, acc[i]);
-            }
-            if (m == nM - 1) {                                              // the group's columns are complete: lane i of the row writes column i
-                double mine = 0.0;
-#pragma unroll
-                for (int i = 0; i < COLS; ++i) { const double s_ = row_sum(acc[i]); if (j == i) mine = s_; acc[i] = 0.0; }
-                const int c = c0 + g * TEAMS * COLS + team + j * TEAMS;
-                if (j < COLS && c < nx + nu) {
-                    if (c >= nx) gU[kb * A.nu + (c - nx)] = (TIO)mine;
-                    else if (k > 0) lam_next[c] = mine;
-                    else gz[(size_t)b * nx + c] = (TIO)mine;
-                }
-            }
+            const int kn = (more || !nit_next) ? k : k - 1;
+            issue(C, kn, b, first_col(kn), more ? it + 1 : nit_next ? 0 : it, team, j, nxt);
+            consume(C, c0, it, team, j, lam, gk, cur, acc, put);
         };
         for (int it = 0; it < nit; it += 2) { stage(it, buf0, buf1); stage(it + 1, buf1, buf0); }
         if (failed(k)) {                                                    // nothing flows through a failed step
@@ -165,7 +187,7 @@ __global__ void __launch_bounds__(THREADS) rollout_adjoint_kernel(const Args<TIO
                 else if (gz) gz[(size_t)b * nx + c] = (TIO)0.0;
             }
             for (int c = tid; c < nu; c += THREADS) gU[kb * A.nu + c] = (TIO)0.0;
-            if (nit_next) issue(k - 1, 0, buf0);
+            if (nit_next) issue(C, k - 1, b, first_col(k - 1), 0, team, j, buf0);
         }
         __syncthreads();
         p ^= 1; nit = nit_next;

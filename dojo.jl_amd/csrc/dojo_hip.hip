@@ -11,6 +11,7 @@
 #include "dojo_coords.hpp"
 #include "dojo_adjoint.hpp"
 #include "dojo_policy.hpp"
+#include "dojo_policy_adjoint.hpp"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -134,6 +135,10 @@ struct DojoSim {
     double refine_w = -1.0;             // refine once max γ/s of an environment exceeds this (dojo_set_refinement); < 0: chosen from the tolerances
     int *d_status = nullptr, *d_iters = nullptr;
     void* d_pu = nullptr;               // [B][nu] the controls of a closed-loop rollout whose caller records none (dojo_rollout_policy_dev)
+    int *d_touch_ptr = nullptr, *d_touch_ent = nullptr;    // per body, the (row, half) entries of the observation Jacobian that touch it (CSR; dojo_policy_adjoint.hpp)
+    void* d_pM = nullptr; size_t pM_bytes = 0;             // [H+1][B][2nu][24] fp64: the observation Jacobians of a closed-loop sweep whose caller passes none (grown on demand)
+    double* d_pacc = nullptr;                              // [B][na (nobs + 1)] fp64: per-environment gW / gbias of a shared policy, in front of the reduction
+    size_t pacc_bytes = 0;
     // iteration cap + continuation kernel (dojo_set_iteration_cap; dojo_device.hpp Globals::iter_cap)
     int iter_cap = -1;                  // < 0: automatic (DOJO_DEFAULT_ITERATION_CAP where the continuation kernel exists), 0: off, > 0: as given
     void* d_resume = nullptr;           // [B][CARRY_PER_ENV] loop scalars of the solves the step kernel left unfinished
@@ -425,6 +430,24 @@ int upload_tables(DojoSim* s) {   // tables are stored in the state precision (f
         for (auto& a : s->M.mlim) { dj::MLimP<T> b; b.nt = a.nt; b.nr = a.nr; for (int i = 0; i < 6; ++i) { b.lo[i] = T(a.lo[i]); b.hi[i] = T(a.hi[i]); } ml.push_back(b); }
         ENSURE(s->d_mlim, ml.size() * sizeof(dj::MLimP<T>));
         HIPCHK(hipMemcpy(s->d_mlim, ml.data(), ml.size() * sizeof(dj::MLimP<T>), hipMemcpyHostToDevice));
+    }
+    {   // the rows of the compact observation Jacobian that touch a body: those of its own joint (child half) and of every joint whose parent it is,
+        // as entries 2 row + half in ascending order (the summation order of the closed-loop sweep's M^T go)
+        const int Nb = s->M.Nb;
+        std::vector<int> tp(Nb + 1, 0), te;
+        for (int b = 0; b < Nb; ++b) {
+            std::vector<int> e;
+            for (int k = 0; k < Nb; ++k) {
+                const auto& n_ = s->M.nodes[k];
+                if (k != b && n_.parent != b) continue;
+                for (int l = 0; l < 2 * (n_.nu_t + n_.nu_r); ++l) e.push_back(2 * (2 * n_.u_off + l) + (k == b ? 1 : 0));
+            }
+            std::sort(e.begin(), e.end());
+            te.insert(te.end(), e.begin(), e.end()); tp[b + 1] = (int)te.size();
+        }
+        ENSURE(s->d_touch_ptr, tp.size() * sizeof(int)); ENSURE(s->d_touch_ent, (te.size() + 1) * sizeof(int));
+        HIPCHK(hipMemcpy(s->d_touch_ptr, tp.data(), tp.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (!te.empty()) HIPCHK(hipMemcpy(s->d_touch_ent, te.data(), te.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     std::vector<int> order;
     for (int lev = 0; lev <= s->M.maxlevel; ++lev) for (int b = 0; b < s->M.Nb; ++b) if (s->M.nodes[b].level == lev) order.push_back(b);
@@ -939,6 +962,46 @@ int launch_policy(const DojoSim* s, const DojoPolicy& p, const void* z, const vo
     HIPCHK(hipGetLastError());
     return DOJO_OK;
 }
+// dojo_observation_jacobian_dev: M [n][B][2nu][24] of the states (z_first; z_rest[0 .. n-2]), one launch over all (state, environment, joint) triples
+int launch_observation_jacobian(const DojoSim* s, const void* z_first, const void* z_rest, long long n, double* M, hipStream_t st) {
+    constexpr int T_ = dj::padjoint::JAC_THREADS;
+    const long long total = n * s->B * s->M.Nb;
+    const dim3 grid((unsigned)((total + T_ - 1) / T_));
+    const dj::NodeP<double>* nodes = (const dj::NodeP<double>*)s->d_nodes;
+    if (s->dtype == DOJO_DTYPE_F32) hipLaunchKernelGGL((dj::padjoint::observation_jacobian_kernel<float>), grid, dim3(T_), 0, st, nodes, s->M.Nb, (int)s->M.nu, s->M.dt, s->B, n, (const float*)z_first, (const float*)z_rest, M);
+    else hipLaunchKernelGGL((dj::padjoint::observation_jacobian_kernel<double>), grid, dim3(T_), 0, st, nodes, s->M.Nb, (int)s->M.nu, s->M.dt, s->B, n, (const double*)z_first, (const double*)z_rest, M);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
+// dojo_rollout_policy_adjoint_dev: the closed-loop reverse sweep (one workgroup per environment, one launch) and, for a shared policy, the reduction over the batch
+template <class TIO>
+int launch_policy_adjoint(const DojoSim* s, const DojoPolicy& p, int H, const DojoPolicyAdjoint& a, const double* M, double* acc, hipStream_t st) {
+    const int nx = 12 * s->M.Nb, nu = (int)s->M.nu, nobs = 2 * nu, na = p.na;
+    dj::padjoint::Args<TIO> A{};
+    A.DZ = (const TIO*)a.DZ; A.DU = (const TIO*)a.DU; A.OBS = (const TIO*)a.OBS; A.M = M; A.G = (const TIO*)a.G; A.Z = (const TIO*)a.Z;
+    A.G_u = (const TIO*)a.G_u; A.G_obs = (const TIO*)a.G_obs; A.status = a.status; A.W = (const TIO*)p.W; A.mean = (const TIO*)p.mean; A.scale = (const TIO*)p.scale;
+    A.touch = dj::padjoint::Touch{s->d_touch_ptr, s->d_touch_ent};
+    A.gW = acc ? nullptr : (TIO*)a.gW; A.gbias = acc ? nullptr : (TIO*)a.gbias; A.acc_out = acc; A.gU = (TIO*)a.gU; A.gz = (TIO*)a.gz;
+    A.H = H; A.B = s->B; A.nx = nx; A.nu = nu; A.nobs = nobs; A.act_off = p.act_off; A.na = na; A.per_env = p.per_env ? 1 : 0; A.cot_space = a.cot_space;
+    hipLaunchKernelGGL((dj::padjoint::rollout_policy_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::padjoint::THREADS), dj::padjoint::lds_bytes(nx, nu, nobs, na), st, A);
+    HIPCHK(hipGetLastError());
+    if (acc) {
+        const int nacc = na * (nobs + 1), per = dj::padjoint::THREADS / dj::adjoint::ROW;
+        hipLaunchKernelGGL((dj::padjoint::policy_reduce_kernel<TIO>), dim3((unsigned)((nacc + per - 1) / per)), dim3(dj::padjoint::THREADS), 0, st, (const double*)acc, s->B, nacc, na * nobs,
+                           (TIO*)a.gW, (TIO*)a.gbias);
+        HIPCHK(hipGetLastError());
+    }
+    return DOJO_OK;
+}
+// a workspace of the handle whose size depends on the call: kept while it is large enough, replaced (hipFree waits for the device) when it is not
+int ensure_at_least(DojoSim* s, void** p, size_t* have, size_t bytes) {
+    if (*p && *have >= bytes) return DOJO_OK;
+    if (*p) { s->owned.erase(std::remove(s->owned.begin(), s->owned.end(), *p), s->owned.end()); HIPCHK(hipFree(*p)); *p = nullptr; *have = 0; }
+    HIPCHK(hipMalloc(p, bytes ? bytes : 8));
+    s->owned.push_back(*p); *have = bytes;
+    return DOJO_OK;
+}
+
 int launch_policy_any(const DojoSim* s, const DojoPolicy& p, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
     return s->dtype == DOJO_DTYPE_F32 ? launch_policy<float>(s, p, z, csg, uff, obs, u, sp) : launch_policy<double>(s, p, z, csg, uff, obs, u, sp);
 }
@@ -1439,19 +1502,12 @@ int dojo_rollout_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void
                                       : launch_adjoint<double>(s, H, DZ, DU, G, cot_space, Z, status, gU, gz, st);
 }
 
-// host pointers: upload, record on the device, reverse sweep, download -- the Jacobians never cross PCIe
-int dojo_rollout_gradients(DojoHandle s, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space, void* Z, int32_t* status, void* gU, void* gz) {
-    Enter enter_(s);
-    if (!s || !z0 || !G || H < 1 || (cot_space != 0 && cot_space != 1)) { g_err = "dojo_rollout_gradients: bad argument"; return DOJO_ERR_INVALID; }
-    TRY(refuse_unsupported(s, true, false));
-    HIPCHK(hipSetDevice(s->device));
-    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
-    const size_t record = HB * nx * (nx + nu) * w;
-    // everything this call allocates: the buffers below (each rounded up as the allocator does) and the workspaces rollout_core and the
-    // differentiable step launches take on first use (ensure_workspaces: sized for the whole batch, so one group's geometry gives them all)
+// device memory the workspaces of rollout_core and of the differentiable step launches take on first use (ensure_workspaces: sized for the whole batch,
+// so one group's geometry gives them all), each rounded up as the allocator does: what a recording host entry adds to its own buffers
+static size_t record_workspaces(DojoHandle s) {
     auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
-    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + up(HB * nu * w) + up(B * nx * w)
-                  + ((U && nu) ? up(HB * nu * w) : 0);
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb;
+    size_t need = 0;
     {
         const Geometry ge = geometry_of(s, whole_batch(s, nullptr), true);
         const size_t wT = sizeof(double);
@@ -1467,6 +1523,23 @@ int dojo_rollout_gradients(DojoHandle s, const void* z0, const void* U, int32_t 
         if (ge.msg_stride && !s->d_msg) need += up(B * (size_t)ge.msg_stride * wT);
         if (ge.quad && std::isfinite(refine_threshold(s))) { if (!s->d_blk) need += up(ge.waves_total * 90 * ge.lanes * wT); if (!s->d_flag) need += up(B * sizeof(int)); }
     }
+    return need;
+}
+
+// host pointers: upload, record on the device, reverse sweep, download -- the Jacobians never cross PCIe
+int dojo_rollout_gradients(DojoHandle s, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space, void* Z, int32_t* status, void* gU, void* gz) {
+    Enter enter_(s);
+    if (!s || !z0 || !G || H < 1 || (cot_space != 0 && cot_space != 1)) { g_err = "dojo_rollout_gradients: bad argument"; return DOJO_ERR_INVALID; }
+    TRY(refuse_unsupported(s, true, false));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
+    const size_t record = HB * nx * (nx + nu) * w;
+    // everything this call allocates: the buffers below (each rounded up as the allocator does) and the workspaces rollout_core and the
+    // differentiable step launches take on first use (ensure_workspaces: sized for the whole batch, so one group's geometry gives them all)
+    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
+    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + up(HB * nu * w) + up(B * nx * w)
+                  + ((U && nu) ? up(HB * nu * w) : 0);
+    need += record_workspaces(s);
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -1487,6 +1560,154 @@ int dojo_rollout_gradients(DojoHandle s, const void* z0, const void* U, int32_t 
     if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
     if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
     if (gU && nu) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
+    return DOJO_OK;
+}
+
+// ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----
+int dojo_observation_jacobian_dev(DojoHandle s, const void* z, int32_t n, double* M, void* stream) {
+    Enter enter_(s);
+    if (!s || !z || !M || n < 1) { g_err = "dojo_observation_jacobian_dev: bad argument (handle, z and M are required, n >= 1)"; return DOJO_ERR_INVALID; }
+    if (s->M.nu == 0) { g_err = "dojo_observation_jacobian_dev: the mechanism has no inputs"; return DOJO_ERR_INVALID; }
+    if (s->M.has_loop) { g_err = "dojo_observation_jacobian_dev: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal: not supported"; return DOJO_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(s->device));
+    return launch_observation_jacobian(s, z, (const char*)z + (size_t)s->B * 13 * s->M.Nb * s->w, n, M, (hipStream_t)stream);
+}
+
+int dojo_observation_jacobian(DojoHandle s, const void* z, double* M) {
+    Enter enter_(s);
+    if (!s || !z || !M) { g_err = "dojo_observation_jacobian: bad argument (handle, z and M are required)"; return DOJO_ERR_INVALID; }
+    if (s->M.nu == 0) { g_err = "dojo_observation_jacobian: the mechanism has no inputs"; return DOJO_ERR_INVALID; }
+    if (s->M.has_loop) { g_err = "dojo_observation_jacobian: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal: not supported"; return DOJO_ERR_UNSUPPORTED; }
+    HIPCHK(hipSetDevice(s->device));
+    const size_t zb = (size_t)s->B * 13 * s->M.Nb * s->w, mb = (size_t)s->B * 2 * s->M.nu * 24 * sizeof(double);
+    DevBuf dz, dM;
+    HIPCHK(dz.alloc(zb)); HIPCHK(dM.alloc(mb));
+    HIPCHK(hipMemcpy(dz.p, z, zb, hipMemcpyHostToDevice));
+    TRY(launch_observation_jacobian(s, dz.p, nullptr, 1, (double*)dM.p, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(M, dM.p, mb, hipMemcpyDeviceToHost));
+    return DOJO_OK;
+}
+
+// what a recording entry refuses on top of refuse_policy: refuse_unsupported's text, with the entry point in front of it
+static int refuse_record(DojoHandle s, const char* who) {
+    const int rc = refuse_unsupported(s, true, false);
+    if (rc != DOJO_OK) g_err = std::string(who) + ": " + g_err.c_str();
+    return rc;
+}
+
+int dojo_rollout_policy_record_dev(DojoHandle s, const void* z0, const DojoPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, int32_t* status,
+                                   void* DZ, void* DU, void* stream) {
+    Enter enter_(s);
+    TRY(refuse_policy(s, z0, policy, H, "dojo_rollout_policy_record_dev"));
+    if (!Z || !OBS || !U_out || !DZ || !DU) { g_err = "dojo_rollout_policy_record_dev: Z, OBS, U_out, DZ and DU are required"; return DOJO_ERR_INVALID; }
+    TRY(refuse_record(s, "dojo_rollout_policy_record_dev"));
+    const DojoPolicy p = *policy;
+    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, DZ, DU, &p, OBS, U_out);
+}
+
+// everything the closed-loop sweep refuses, before anything is launched or allocated (z0 of refuse_policy: not this entry's -- the policy stands in)
+static int refuse_policy_adjoint(DojoHandle s, const DojoPolicy* p, int32_t H, const char* who) {
+    const std::string w_ = std::string(who) + ": ";
+    TRY(refuse_policy(s, p, p, H, who));
+    if (p->contact_forces) {
+        g_err = w_ + "contact_forces = 1 is not supported in reverse mode (the derivative of the previous step's impulses w.r.t. the state is not part of the record)";
+        return DOJO_ERR_UNSUPPORTED;
+    }
+    if (dj::padjoint::lds_bytes(12 * s->M.Nb, (int)s->M.nu, 2 * (int)s->M.nu, p->na) > 65536) {
+        g_err = w_ + "the sweep keeps 4 nx + nu + 2 nobs + na (nobs + 1) doubles in LDS, which exceeds 64 KB for this mechanism and policy"; return DOJO_ERR_UNSUPPORTED;
+    }
+    return DOJO_OK;
+}
+
+int dojo_rollout_policy_adjoint_dev(DojoHandle s, const DojoPolicy* policy, int32_t H, const DojoPolicyAdjoint* a_, void* stream) {
+    Enter enter_(s);
+    const char* who = "dojo_rollout_policy_adjoint_dev";
+    const std::string w_ = std::string(who) + ": ";
+    TRY(refuse_policy_adjoint(s, policy, H, who));
+    if (!a_) { g_err = w_ + "the argument record must not be NULL"; return DOJO_ERR_INVALID; }
+    const DojoPolicy p = *policy; const DojoPolicyAdjoint a = *a_;      // (the caller's structs are read during the call only)
+    if (!a.DZ || !a.OBS || !a.G) { g_err = w_ + "DZ, OBS and G must not be NULL"; return DOJO_ERR_INVALID; }
+    if (!a.DU) { g_err = w_ + "gU, gW, gbias and gz need DU"; return DOJO_ERR_INVALID; }
+    if (a.cot_space != 0 && a.cot_space != 1) { g_err = w_ + "cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
+    if (a.cot_space == 1 && !a.Z) { g_err = w_ + "cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
+    if (!a.M && (!a.z0 || !a.Z)) { g_err = w_ + "M = NULL needs z0 and Z (the observation Jacobians are computed from them)"; return DOJO_ERR_INVALID; }
+    if ((((uintptr_t)a.DZ) | (uintptr_t)a.DU) & 15) { g_err = w_ + "DZ and DU must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the record)
+    if (!a.gW && !a.gbias && !a.gU && !a.gz) return DOJO_OK;
+    const size_t B = s->B, nobs = 2 * s->M.nu;
+    const double* M = a.M;
+    if (!M) {
+        const long long n = (long long)H + (a.G_obs ? 1 : 0);
+        TRY(ensure_at_least(s, &s->d_pM, &s->pM_bytes, ((size_t)H + 1) * B * nobs * 24 * sizeof(double)));
+        TRY(launch_observation_jacobian(s, a.z0, a.Z, n, (double*)s->d_pM, st));
+        M = (const double*)s->d_pM;
+    }
+    double* acc = nullptr;
+    if (!p.per_env) { TRY(ensure_at_least(s, (void**)&s->d_pacc, &s->pacc_bytes, B * (size_t)p.na * (nobs + 1) * sizeof(double))); acc = s->d_pacc; }
+    return s->dtype == DOJO_DTYPE_F32 ? launch_policy_adjoint<float>(s, p, H, a, M, acc, st) : launch_policy_adjoint<double>(s, p, H, a, M, acc, st);
+}
+
+// host pointers (the members of *policy too): upload, record on the device, sweep, download -- neither the Jacobians nor M cross PCIe
+int dojo_rollout_policy_gradients(DojoHandle s, const void* z0, const DojoPolicy* policy, int32_t H, const void* G, int32_t cot_space, const void* G_u, const void* G_obs,
+                                  void* Z, void* OBS, void* U_out, int32_t* status, void* gW, void* gbias, void* gU, void* gz) {
+    Enter enter_(s);
+    const char* who = "dojo_rollout_policy_gradients";
+    const std::string w_ = std::string(who) + ": ";
+    TRY(refuse_policy(s, z0, policy, H, who));
+    TRY(refuse_policy_adjoint(s, policy, H, who));
+    if (!G || (cot_space != 0 && cot_space != 1)) { g_err = w_ + "G is required and cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_record(s, who));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
+    const size_t na = (size_t)policy->na, Bw = policy->per_env ? B : 1, nobs = 2 * nu;
+    const size_t record = HB * nx * (nx + nu) * w, mbytes = (HB + B) * nobs * 24 * sizeof(double);
+    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
+    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + 3 * up(HB * nu * w) + up(B * nx * w)
+                  + 2 * up((HB + B) * nobs * w) + 2 * up(Bw * na * (nobs + 1) * w) + 2 * up(nobs * w) + (policy->U_ff ? up(HB * nu * w) : 0)
+                  + ((s->d_pM && s->pM_bytes >= mbytes) ? 0 : up(mbytes)) + (policy->per_env ? 0 : up(B * na * (nobs + 1) * sizeof(double)));
+    need += record_workspaces(s);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b) {
+        g_err = w_ + "the record of " + std::to_string(record) + " bytes and the observation Jacobians of " + std::to_string(mbytes) + " bytes (" + std::to_string(need)
+                + " bytes with the other buffers of the call) do not fit into the " + std::to_string(free_b) + " bytes of free device memory";
+        return DOJO_ERR_INVALID;
+    }
+    DojoPolicy p = *policy;
+    DevBuf dz0, dW, db, dm, dsc, dUff, dG, dGu, dGo, dZ, dO, dU, dS, dDZ, dDU, dgW, dgb, dgU, dgz;
+    auto upl = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
+        *dst = nullptr;
+        if (!src) return DOJO_OK;
+        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        *dst = d.p;
+        return DOJO_OK;
+    };
+    DojoPolicyAdjoint a{};
+    const void* z0d = nullptr;
+    TRY(upl(dz0, z0, B * nz * w, &z0d)); TRY(upl(dW, policy->W, Bw * na * nobs * w, &p.W)); TRY(upl(db, policy->bias, Bw * na * w, &p.bias));
+    TRY(upl(dm, policy->mean, nobs * w, &p.mean)); TRY(upl(dsc, policy->scale, nobs * w, &p.scale)); TRY(upl(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
+    TRY(upl(dG, G, HB * ng * w, &a.G)); TRY(upl(dGu, G_u, HB * nu * w, &a.G_u)); TRY(upl(dGo, G_obs, (HB + B) * nobs * w, &a.G_obs));
+    HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dO.alloc((HB + B) * nobs * w)); HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
+    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w));
+    HIPCHK(dgW.alloc(Bw * na * nobs * w)); HIPCHK(dgb.alloc(Bw * na * w)); HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w));
+    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, &p, dO.p, dU.p));
+    a.DZ = dDZ.p; a.DU = dDU.p; a.OBS = dO.p; a.status = (const int32_t*)dS.p; a.z0 = z0d; a.Z = dZ.p; a.M = nullptr; a.cot_space = cot_space;
+    a.gW = dgW.p; a.gbias = dgb.p; a.gU = dgU.p; a.gz = dgz.p;
+    TRY(dojo_rollout_policy_adjoint_dev(s, &p, H, &a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
+    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
+    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
+    if (gW) HIPCHK(hipMemcpy(gW, dgW.p, Bw * na * nobs * w, hipMemcpyDeviceToHost));
+    if (gbias) HIPCHK(hipMemcpy(gbias, dgb.p, Bw * na * w, hipMemcpyDeviceToHost));
+    if (gU) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
     if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
     return DOJO_OK;

@@ -41,7 +41,9 @@ def lib():
                   "dojo_minimal_to_maximal", "dojo_maximal_to_minimal", "dojo_step_minimal",
                   "dojo_minimal_to_maximal_dev", "dojo_maximal_to_minimal_dev", "dojo_step_minimal_dev",
                   "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
-                  "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients", "dojo_rollout_policy_dev", "dojo_rollout_policy"):
+                  "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients", "dojo_rollout_policy_dev", "dojo_rollout_policy",
+                  "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
+                  "dojo_rollout_policy_gradients"):
             getattr(L, f).restype = C.c_int
         L.dojo_destroy.restype = None
         _lib = L
@@ -57,7 +59,9 @@ EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error",
                     "dojo_simulate", "dojo_simulate_dev", "dojo_observe", "dojo_observe_dev",
                     "dojo_set_external_force", "dojo_set_external_force_dev",
                     "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients",
-                    "dojo_rollout_policy_dev", "dojo_rollout_policy"]
+                    "dojo_rollout_policy_dev", "dojo_rollout_policy",
+                    "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
+                    "dojo_rollout_policy_gradients"]
 
 
 class DojoPolicy(C.Structure):
@@ -66,6 +70,13 @@ class DojoPolicy(C.Structure):
     _fields_ = [("W", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p), ("U_ff", C.c_void_p),
                 ("per_env", C.c_int32), ("act_off", C.c_int32), ("na", C.c_int32), ("contact_forces", C.c_int32), ("contact_init", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class DojoPolicyAdjoint(C.Structure):
+    """include/dojo_hip.h `DojoPolicyAdjoint`: the record, the cotangents and the outputs of dojo_rollout_policy_adjoint_dev (device pointers)"""
+    _fields_ = [("DZ", C.c_void_p), ("DU", C.c_void_p), ("OBS", C.c_void_p), ("status", C.c_void_p), ("z0", C.c_void_p), ("Z", C.c_void_p), ("M", C.c_void_p),
+                ("G", C.c_void_p), ("G_u", C.c_void_p), ("G_obs", C.c_void_p), ("gW", C.c_void_p), ("gbias", C.c_void_p), ("gU", C.c_void_p), ("gz", C.c_void_p),
+                ("cot_space", C.c_int32), ("reserved", C.c_int32)]
 
 
 # columns of a Storage row (src/simulation/storage.jl:15-24)
@@ -288,6 +299,56 @@ class BatchedMechanism:
         U = np.empty((max(H, 0), B, s.nu), self.np_dtype); st = np.empty((max(H, 0), B), np.int32)
         _chk(lib().dojo_rollout_policy(self.h, _p(z0), C.byref(pol), H, _p(Z), _p(OBS), _p(U), _p(st)))
         return Z, OBS, U, st
+
+    def observation_jacobian(self, z):
+        """maximal_to_minimal_jacobian (dojo_observation_jacobian) at z [B,13Nb] -> the COMPACT [B, 2nu, 24] fp64: row i is minimal coordinate i, columns
+        0..11 the derivative w.r.t. the tangent coordinates [x; v; phi; omega] of the parent body of the joint that owns the row (0 for a joint on the
+        origin), 12..23 w.r.t. those of its child body.  coords.dense_observation_jacobian scatters it to [B, 2nu, 12Nb]."""
+        B, s = self.batch, self.spec
+        z = self._arr(z, (B, s.nz))
+        M = np.empty((B, 2 * s.nu, 24), np.float64)
+        _chk(lib().dojo_observation_jacobian(self.h, _p(z), _p(M)))
+        return M
+
+    def rollout_policy_gradients(self, z0, W, G, steps=None, bias=None, mean=None, scale=None, U_ff=None, act_off=0, G_u=None, G_obs=None, cot_space="tangent"):
+        """Reverse mode through a closed-loop rollout (dojo_rollout_policy_gradients): the rollout of `rollout_policy` (without contact observations) and
+        the gradient of a trajectory loss w.r.t. the policy, the feed-forward term and the initial state; the recorded Jacobians stay on the device.
+        G [H,B,nx] ("tangent") or [H,B,13Nb] ("state"): cotangent w.r.t. the state after every step; G_u [H,B,nu], G_obs [H+1,B,nobs] (optional):
+        w.r.t. the applied controls and the observations.  Returns (Z, OBS, U, status, gW, gbias, gU [H,B,nu], gz0 [B,nx] tangent); gW, gbias have
+        the shapes of W, bias ([B,na,nobs] / [B,na] for one policy per environment; [na,nobs] / [na], summed over the batch, for a shared one)."""
+        B, s = self.batch, self.spec
+        z0 = self._arr(z0, (B, s.nz))
+        if cot_space not in ("tangent", "state", 0, 1):
+            raise ValueError("cot_space must be 'tangent' or 'state'")
+        cs = 1 if cot_space in ("state", 1) else 0
+        if G is None:
+            raise ValueError("rollout_policy_gradients needs the cotangents G of the loss w.r.t. the state after every step")
+        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
+        if G.shape != (H, B, s.nz if cs else s.nx):
+            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
+        if steps is not None and int(steps) != H:
+            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
+        W = np.ascontiguousarray(W, dtype=self.np_dtype)
+        if W.ndim not in (2, 3):
+            raise ValueError("W must be [na, nobs] or [B, na, nobs]")
+        per_env = W.ndim == 3
+        na, nobs = W.shape[-2], 2 * s.nu
+        W = self._arr(W, (B, na, nobs) if per_env else (na, nobs))
+        bias = None if bias is None else self._arr(bias, (B, na) if per_env else (na,))
+        mean = None if mean is None else self._arr(mean, (nobs,))
+        scale = None if scale is None else self._arr(scale, (nobs,))
+        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
+        G_u = None if G_u is None else self._arr(G_u, (H, B, s.nu))
+        G_obs = None if G_obs is None else self._arr(G_obs, (H + 1, B, nobs))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        pol = DojoPolicy(ptr(W), ptr(bias), ptr(mean), ptr(scale), ptr(U_ff), int(per_env), int(act_off), int(na), 0, 0, 0)
+        Z = np.empty((H, B, s.nz), self.np_dtype); OBS = np.empty((H + 1, B, nobs), self.np_dtype)
+        U = np.empty((H, B, s.nu), self.np_dtype); st = np.empty((H, B), np.int32)
+        gW = np.empty_like(W); gb = np.empty((B, na) if per_env else (na,), self.np_dtype)
+        gU = np.empty((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
+        _chk(lib().dojo_rollout_policy_gradients(self.h, _p(z0), C.byref(pol), H, _p(G), cs, _p(G_u), _p(G_obs), _p(Z), _p(OBS), _p(U), _p(st),
+                                                 _p(gW), _p(gb), _p(gU), _p(gz)))
+        return Z, OBS, U, st, gW, gb, gU, gz
 
     def set_external_force(self, fext):
         """set_external_force!(body; force, torque) for all bodies: fext [B, Nb, 6] = [Fext (world); τext (body frame)],

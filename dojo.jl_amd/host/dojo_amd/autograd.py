@@ -4,6 +4,9 @@ Jacobians and the reverse sweep are the library's kernels, include/dojo_hip.h "R
     Z = differentiable_rollout(mech, z0, U)          # z0 [B,13Nb], U [H,B,nu] device tensors -> Z [H,B,13Nb]
     loss(Z).backward()                               # U.grad [H,B,nu], z0.grad [B,13Nb]
 
+    Z, OBS, U = differentiable_policy_rollout(mech, z0, W, bias=b, U_ff=Uff)     # closed loop: u_k = U_ff[k] + E (b + W ((o_k - mean) .* scale))
+    loss(Z, OBS, U).backward()                       # W.grad, b.grad, Uff.grad, z0.grad
+
 Everything is enqueued on torch's current stream and nothing synchronizes.  The gradient is the chain of the handle's gradient mode:
 set `mech.set_gradient_mode(api.GRAD_CONSISTENT)` for the derivative of the rollout.
 """
@@ -82,3 +85,79 @@ def differentiable_rollout(mech, z0, U=None, steps=None):
     Z, status = _Rollout.apply(mech, z0, U, steps)
     Z.status = status
     return Z
+
+
+class _PolicyRollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mech, z0, W, bias, U_ff, steps, mean, scale, act_off):
+        s, B = mech.spec, mech.batch
+        dt = torch.float32 if mech.dtype_code == 1 else torch.float64
+        nobs = 2 * s.nu
+
+        def want(t, what, shapes):
+            if t is None:
+                return None
+            if not t.is_cuda or t.dtype != dt or tuple(t.shape) not in shapes:
+                raise ValueError("%s must be a %s device tensor of shape %s" % (what, dt, " or ".join(str(x) for x in shapes)))
+            return t.contiguous()
+        z0c = want(z0, "z0", [(B, s.nz)])
+        if W is None or W.dim() not in (2, 3):
+            raise ValueError("W must be [na, nobs] or [B, na, nobs]")
+        per_env = W.dim() == 3
+        na = int(W.shape[-2])
+        Wc = want(W, "W", [(B, na, nobs) if per_env else (na, nobs)])
+        bc = want(bias, "bias", [(B, na) if per_env else (na,)])
+        mc, sc = want(mean, "mean", [(nobs,)]), want(scale, "scale", [(nobs,)])
+        if U_ff is not None:
+            H = int(U_ff.shape[0]); Uc = want(U_ff, "U_ff", [(H, B, s.nu)])
+        else:
+            H = int(steps); Uc = None
+        dev = z0.device
+        Z = torch.empty((H, B, s.nz), dtype=dt, device=dev); OBS = torch.empty((H + 1, B, nobs), dtype=dt, device=dev)
+        U = torch.empty((H, B, s.nu), dtype=dt, device=dev); status = torch.empty((H, B), dtype=torch.int32, device=dev)
+        DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)          # the record: freed with the graph
+        DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()
+        pol = api.DojoPolicy(p(Wc), p(bc), p(mc), p(sc), p(Uc), int(per_env), int(act_off), na, 0, 0, 0)
+        api._chk(api.lib().dojo_rollout_policy_record_dev(mech.h, _ptr(z0c), C.byref(pol), H, _ptr(Z), _ptr(OBS), _ptr(U), _ptr(status), _ptr(DZ), _ptr(DU),
+                                                          _stream(dev)))
+        ctx.mech, ctx.H, ctx.per_env, ctx.na, ctx.act_off = mech, H, per_env, na, int(act_off)
+        ctx.has = (bias is not None, U_ff is not None, mean is not None, scale is not None)
+        ctx.save_for_backward(z0c, Wc, Z, OBS, status, DZ, DU, *[t for t in (mc, sc) if t is not None])
+        ctx.mark_non_differentiable(status)
+        return Z, OBS, U, status
+
+    @staticmethod
+    def backward(ctx, gZ, gOBS, gU_out, _gstatus):
+        mech, H = ctx.mech, ctx.H
+        s, B = mech.spec, mech.batch
+        z0, W, Z, OBS, status, DZ, DU = ctx.saved_tensors[:7]
+        rest = list(ctx.saved_tensors[7:])
+        mean = rest.pop(0) if ctx.has[2] else None
+        scale = rest.pop(0) if ctx.has[3] else None
+        dt, dev, nobs = Z.dtype, Z.device, 2 * s.nu
+        # (a cotangent torch leaves out is a zero: the state's is required by the ABI, the other two are optional)
+        gZ = torch.zeros_like(Z) if gZ is None else gZ.contiguous()
+        gOBS = None if gOBS is None else gOBS.contiguous()
+        gU_out = None if gU_out is None else gU_out.contiguous()
+        need = ctx.needs_input_grad                    # (mech, z0, W, bias, U_ff, steps, mean, scale, act_off)
+        gW = torch.empty_like(W) if need[2] else None
+        gb = torch.empty((B, ctx.na) if ctx.per_env else (ctx.na,), dtype=dt, device=dev) if (ctx.has[0] and need[3]) else None
+        gU = torch.empty((H, B, s.nu), dtype=dt, device=dev) if (ctx.has[1] and need[4]) else None
+        gz = torch.empty((B, s.nx), dtype=dt, device=dev) if need[1] else None
+        p = lambda t: None if t is None else t.data_ptr()
+        pol = api.DojoPolicy(p(W), None, p(mean), p(scale), None, int(ctx.per_env), ctx.act_off, ctx.na, 0, 0, 0)
+        a = api.DojoPolicyAdjoint(p(DZ), p(DU), p(OBS), p(status), p(z0), p(Z), None, p(gZ), p(gU_out), p(gOBS), p(gW), p(gb), p(gU), p(gz), 1, 0)
+        api._chk(api.lib().dojo_rollout_policy_adjoint_dev(mech.h, C.byref(pol), H, C.byref(a), _stream(dev)))
+        return None, (lift_tangent(gz, z0) if gz is not None else None), gW, gb, gU, None, None, None, None
+
+
+def differentiable_policy_rollout(mech, z0, W, bias=None, U_ff=None, steps=None, mean=None, scale=None, act_off=0):
+    """-> (Z [H,B,13Nb], OBS [H+1,B,2nu], U [H,B,nu]): the closed-loop rollout from z0 under u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale)) as a node of
+    torch's graph (W [na,nobs] shared or [B,na,nobs] per environment; H from U_ff, else `steps`).  Forward: dojo_rollout_policy_record_dev into
+    torch-owned tensors; backward: ONE dojo_rollout_policy_adjoint_dev call with the cotangents of all three outputs.  Gradients flow to z0 (lifted
+    to state shape as in differentiable_rollout), W, bias and U_ff; mean and scale are frozen.  A shared W receives the sum over the batch.
+    Z.status [H,B] (int32, non-differentiable) is the solver status of every step; nothing flows through a failed step's Jacobians."""
+    Z, OBS, U, status = _PolicyRollout.apply(mech, z0, W, bias, U_ff, steps, mean, scale, act_off)
+    Z.status = status
+    return Z, OBS, U

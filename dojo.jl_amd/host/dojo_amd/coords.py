@@ -90,6 +90,22 @@ def maximal_to_minimal(spec, z):
     return np.concatenate(out) if out else np.zeros(0)
 
 
+def dense_observation_jacobian(spec, Mc):
+    """compact maximal_to_minimal Jacobian [B, 2nu, 24] (BatchedMechanism.observation_jacobian, dojo_observation_jacobian_dev: per row the derivative
+    w.r.t. the tangent coordinates of the owning joint's parent body, then of its child body) -> dense [B, 2nu, 12Nb]"""
+    Mc = np.asarray(Mc)
+    B = Mc.shape[0]
+    J = np.zeros((B, 2 * spec.nu, 12 * spec.Nb), Mc.dtype)
+    r = 0
+    for j in spec.joints:
+        n = 2 * j.nu
+        if j.parent >= 0:
+            J[:, r:r + n, 12 * j.parent:12 * j.parent + 12] = Mc[:, r:r + n, 0:12]
+        J[:, r:r + n, 12 * j.child:12 * j.child + 12] = Mc[:, r:r + n, 12:24]
+        r += n
+    return J
+
+
 def minimal_state_dict(spec, coords=None, vels=None):
     """Build a minimal state vector from {joint_name: coordinates} / {joint_name: velocities}."""
     x = np.zeros(2 * spec.nu)

@@ -212,6 +212,35 @@ function rollout_policy(bm::BatchedMechanism{T}, z0::Matrix{T}, W::Array{T}, H::
     return Z, OBS, U, status
 end
 
+"""
+reverse mode through a closed-loop rollout (no counterpart in Dojo.jl): the rollout of `rollout_policy` (without contact observations) and the
+gradient of a trajectory loss w.r.t. the policy, the feed-forward term and the initial state; the recorded Jacobians stay on the device.
+G[nx | nz, B, H] is the cotangent w.r.t. the state after every step (`cot_space = :tangent | :state`), G_u[nu, B, H] and G_obs[nobs, B, H + 1]
+(optional) those w.r.t. the applied controls and the observations.  Array conventions as in `rollout_policy`.
+-> Z, OBS, U, status, gW (the shape of W), gbias ([na] / [na, B]), gU[nu, B, H], gz0[nx, B] (tangent coordinates).
+"""
+function rollout_policy_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, W::Array{T}, G::Array{T,3}; bias::Union{Nothing,Array{T}}=nothing,
+                                  mean::Union{Nothing,Vector{T}}=nothing, scale::Union{Nothing,Vector{T}}=nothing, U_ff::Union{Nothing,Array{T,3}}=nothing,
+                                  act_off::Integer=0, G_u::Union{Nothing,Array{T,3}}=nothing, G_obs::Union{Nothing,Array{T,3}}=nothing,
+                                  cot_space::Symbol=:tangent, opts=Dojo.SolverOptions{Float64}()) where T
+    set_options!(bm, opts)
+    H = size(G, 3); nobs = 2 * bm.nu
+    size(W, 1) == nobs || error("W must have nobs = $nobs rows")
+    na = size(W, 2); per_env = ndims(W) == 3
+    Z = Array{T}(undef, bm.nz, bm.batch, H); OBS = Array{T}(undef, nobs, bm.batch, H + 1)
+    U = Array{T}(undef, bm.nu, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    gW = similar(W); gbias = per_env ? Matrix{T}(undef, na, bm.batch) : Vector{T}(undef, na)
+    gU = Array{T}(undef, bm.nu, bm.batch, H); gz = Matrix{T}(undef, bm.nx, bm.batch)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve W bias mean scale U_ff G_u G_obs begin
+        pol = Ref(DojoPolicy(p(W), p(bias), p(mean), p(scale), p(U_ff), Int32(per_env), Int32(act_off), Int32(na), Int32(0), Int32(0), Int32(0)))
+        check(@ccall $(fn(:dojo_rollout_policy_gradients))(bm.handle::Ptr{Cvoid}, z0::Ptr{T}, pol::Ptr{DojoPolicy}, Int32(H)::Int32, G::Ptr{T},
+                                                           Int32(cot_space === :state ? 1 : 0)::Int32, p(G_u)::Ptr{Cvoid}, p(G_obs)::Ptr{Cvoid}, Z::Ptr{T}, OBS::Ptr{T},
+                                                           U::Ptr{T}, status::Ptr{Int32}, gW::Ptr{T}, gbias::Ptr{T}, gU::Ptr{T}, gz::Ptr{T})::Cint)
+    end
+    return Z, OBS, U, status, gW, gbias, gU, gz
+end
+
 "which states the IFT data blocks are evaluated at: 0 = as the reference does after step! (post-update_state!), 1 = at the solved step (consistent)"
 set_gradient_mode!(bm::BatchedMechanism, mode::Integer) = check(@ccall $(fn(:dojo_set_gradient_mode))(bm.handle::Ptr{Cvoid}, Int32(mode)::Int32)::Cint)
 

@@ -400,7 +400,7 @@ int  dojo_rollout_gradients(DojoHandle h, const void* z0, const void* U, int32_t
  * Refused before anything is launched, text on the handle -- DOJO_ERR_INVALID: NULL handle, z0, policy or W; H < 1; nu = 0; na < 1, act_off < 0 or
  * act_off + na > nu; contact_init = 1 on a handle without a solution.  DOJO_ERR_UNSUPPORTED: a mechanism with a kinematic loop, contact_forces with
  * LinearContact (both as dojo_observe_dev); more than 2048 observations.
- * Not part of it: reverse mode through the policy (OBS and U_out are what such a sweep needs), non-affine policies, rewards / termination, running
+ * Not part of it: contact observations in reverse mode (below), non-affine policies, rewards / termination, running
  * normaliser statistics, control clamping, re-projection to minimal coordinates between the steps (DojoEnvironments' step! does that; simulate! does not). */
 typedef struct DojoPolicy {
     const void* W;        /* [Bw][na][nobs] row-major, handle dtype, device memory; required            */
@@ -419,6 +419,78 @@ int  dojo_rollout_policy_dev(DojoHandle h, const void* z0, const DojoPolicy* pol
                              void* Z, void* OBS, void* U_out, int32_t* status, void* stream);
 int  dojo_rollout_policy(DojoHandle h, const void* z0, const DojoPolicy* policy, int32_t H,
                          void* Z, void* OBS, void* U_out, int32_t* status);
+
+/* Reverse mode through closed-loop rollouts: the gradient of a trajectory loss w.r.t. the POLICY (W, bias), the feed-forward term and the initial
+ * state -- what replaces the random search of examples/learning/ant_ars.jl with first-order optimisation.  No counterpart in the reference, which
+ * differentiates one step at a time (src/gradients/state.jl:69-126).  csrc/dojo_policy_adjoint.hpp has the kernels.
+ *
+ * Per environment: z_0 = z0, z_k = Z[k-1]; o_k = the minimal-coordinate observation of z_k; ohat_k = (o_k - mean) .* scale, formed in fp64 from the
+ * RECORDED, rounded OBS[k] exactly as the forward kernel forms it; u_k = U_ff[k] + E (bias + W ohat_k); M_k = d o_k / d z_k [2nu x nx] in the tangent
+ * coordinates [x; v; phi; omega] per body (dq = q (x) (0, phi): the convention of dz and of cot_space = 1), evaluated at z_k itself.  With the
+ * cotangents g_k (w.r.t. the state after step k), GU_k (w.r.t. U_out[k]) and GO_k (w.r.t. OBS[k], k = 0 .. H):
+ *     lambda <- g_{H-1} + M_H^T GO_H;   gW <- 0;   gbias <- 0
+ *     for k = H-1 .. 0:   if status && status[k][b] != 0:  lambda <- 0          (by select: DZ_k, DU_k need not be finite and are not read)
+ *                         gu     = DU_k^T lambda + GU_k                          -> gU[k]   (gradient w.r.t. U_ff[k]; all nu entries)
+ *                         a      = gu[act_off .. act_off + na - 1]
+ *                         gbias += a;   gW += a ohat_k^T
+ *                         go     = scale .* (W^T a) + GO_k
+ *                         lambda = DZ_k^T lambda + M_k^T go   (+ g_{k-1} if k > 0)
+ *     gz <- lambda
+ * A failed step is a step whose DZ_k, DU_k are zero; everything else proceeds (with G_u = G_obs = NULL: gU[k] = 0 and nothing is added to gW, the
+ * rule of dojo_rollout_adjoint_dev; with W = 0 the recursion for gU and gz IS that entry's).  mean and scale are frozen: no gradient is produced
+ * for them, and the rounding of o_k is not differentiated.
+ *
+ * dojo_observation_jacobian_dev: maximal_to_minimal_jacobian (src/gradients/state.jl:9-56) of n * B states z [n][B][13Nb] (handle dtype) in one
+ * launch over all (state, environment, joint) triples.  M is double [n][B][2nu][24], COMPACT and always fp64 (as dojo_get_mu is): row i is minimal
+ * coordinate i in the order of dojo_maximal_to_minimal; columns 0..11 are the derivative w.r.t. the tangent coordinates of the PARENT body of the
+ * joint that owns the row, columns 12..23 w.r.t. those of its CHILD body.  A joint on the origin has no parent columns: they are written as 0 and no
+ * consumer reads them.  dojo_observation_jacobian: host pointers, z [B][13Nb] (n = 1).  Mechanisms with a kinematic loop: DOJO_ERR_UNSUPPORTED.
+ *
+ * dojo_rollout_policy_record_dev = dojo_rollout_policy_dev plus the record of dojo_rollout_record_dev (DZ [H][B][nx][nx], DU [H][B][nu][nx], device
+ * layout).  Z, OBS, U_out, DZ, DU are required, status may be NULL.  It refuses what dojo_rollout_policy_dev and dojo_rollout_record_dev refuse.
+ *
+ * dojo_rollout_policy_adjoint_dev: the sweep above.  `policy` as for the forward call (bias and U_ff are not read); *a is host memory read during
+ * the call, its members are device pointers in the handle dtype.  M = NULL: the library computes it from (z0, Z) into a workspace of the handle with
+ * the kernel of dojo_observation_jacobian_dev (M[H] is computed and read only when G_obs is given).  per_env = 1: gW [B][na][nobs], gbias [B][na];
+ * per_env = 0: gW [na][nobs], gbias [na], the sums over the batch (a second small kernel, summation order fixed by B alone).  Launches go on `stream`
+ * only and nothing synchronizes (a workspace that has to GROW is replaced, which waits for the device once).  All arithmetic is fp64, outputs are
+ * rounded once, no atomics: results are bit-identical from run to run and independent of the batch size and of an environment's place in the batch.
+ * Refused before anything is launched, text on the handle -- DOJO_ERR_INVALID: what dojo_rollout_policy_dev refuses; NULL a, DZ, DU, OBS or G;
+ * cot_space not 0 / 1; cot_space = 1 without Z; M = NULL without z0 and Z; DZ or DU not 16-byte aligned.  DOJO_ERR_UNSUPPORTED:
+ * policy->contact_forces = 1 (the derivative of the previous step's impulses w.r.t. the state is not part of the record, and treating them as
+ * constants would silently return something that is not the derivative); a sweep whose LDS need (4 nx + nu + 2 nobs + na (nobs + 1) doubles:
+ * Ant 7 KB, Atlas 30 KB) exceeds 64 KB.
+ *
+ * dojo_rollout_policy_gradients (host pointers, the members of *policy included): uploads, records, sweeps, downloads Z [H][B][13Nb],
+ * OBS [H+1][B][nobs], U_out [H][B][nu], status [H][B], gW, gbias, gU [H][B][nu], gz [B][nx] (each may be NULL).  G [H][B][nx | 13Nb] is required,
+ * G_u [H][B][nu] and G_obs [H+1][B][nobs] may be NULL.  The record and M never cross PCIe; a record (plus M) that does not fit into the free device
+ * memory: DOJO_ERR_INVALID with the byte count in the text, before any launch. */
+typedef struct DojoPolicyAdjoint {
+    const void* DZ;         /* [H][B][nx][nx] as recorded; required, 16-byte aligned                       */
+    const void* DU;         /* [H][B][nu][nx] as recorded; required, 16-byte aligned                       */
+    const void* OBS;        /* [H+1][B][nobs] as recorded; required                                        */
+    const int32_t* status;  /* [H][B] or NULL (every step solved)                                          */
+    const void* z0;         /* [B][13Nb]; needed when M is NULL                                            */
+    const void* Z;          /* [H][B][13Nb]; needed when M is NULL, or cot_space = 1                       */
+    const double* M;        /* [H+1][B][2nu][24] compact observation Jacobians, or NULL (computed)         */
+    const void* G;          /* [H][B][nx] (cot_space 0) or [H][B][13Nb] (cot_space 1); required            */
+    const void* G_u;        /* [H][B][nu] cotangent of U_out, or NULL                                      */
+    const void* G_obs;      /* [H+1][B][nobs] cotangent of OBS, or NULL                                    */
+    void* gW;               /* out: [Bw][na][nobs], or NULL                                                */
+    void* gbias;            /* out: [Bw][na], or NULL                                                      */
+    void* gU;               /* out: [H][B][nu] gradient w.r.t. U_ff, or NULL                               */
+    void* gz;               /* out: [B][nx] gradient w.r.t. z0 in tangent coordinates, or NULL             */
+    int32_t cot_space;      /* 0: G in tangent coordinates; 1: in state coordinates (as dojo_rollout_adjoint_dev) */
+    int32_t reserved;
+} DojoPolicyAdjoint;
+int  dojo_observation_jacobian_dev(DojoHandle h, const void* z, int32_t n, double* M, void* stream);
+int  dojo_observation_jacobian(DojoHandle h, const void* z, double* M);
+int  dojo_rollout_policy_record_dev(DojoHandle h, const void* z0, const DojoPolicy* policy, int32_t H,
+                                    void* Z, void* OBS, void* U_out, int32_t* status, void* DZ, void* DU, void* stream);
+int  dojo_rollout_policy_adjoint_dev(DojoHandle h, const DojoPolicy* policy, int32_t H, const DojoPolicyAdjoint* a, void* stream);
+int  dojo_rollout_policy_gradients(DojoHandle h, const void* z0, const DojoPolicy* policy, int32_t H, const void* G, int32_t cot_space,
+                                   const void* G_u, const void* G_obs, void* Z, void* OBS, void* U_out, int32_t* status,
+                                   void* gW, void* gbias, void* gU, void* gz);
 
 /* get_state(environment) of DojoEnvironments (environments.jl:100-102; quadruped_sampling.jl:67-72): the minimal state
  * of the mechanism, and with contact_forces != 0 the normal impulse of every contact of the last step clamped to
