@@ -12,6 +12,7 @@
 #include "dojo_adjoint.hpp"
 #include "dojo_policy.hpp"
 #include "dojo_policy_adjoint.hpp"
+#include "dojo_mlp.hpp"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -139,6 +140,7 @@ struct DojoSim {
     void* d_pM = nullptr; size_t pM_bytes = 0;             // [H+1][B][2nu][24] fp64: the observation Jacobians of a closed-loop sweep whose caller passes none (grown on demand)
     double* d_pacc = nullptr;                              // [B][na (nobs + 1)] fp64: per-environment gW / gbias of a shared policy, in front of the reduction
     size_t pacc_bytes = 0;
+    double* d_macc = nullptr; size_t macc_bytes = 0;       // [B][P] fp64: the accumulators of the MLP sweep between its steps, and in front of the reduction (dojo_mlp.hpp)
     // iteration cap + continuation kernel (dojo_set_iteration_cap; dojo_device.hpp Globals::iter_cap)
     int iter_cap = -1;                  // < 0: automatic (DOJO_DEFAULT_ITERATION_CAP where the continuation kernel exists), 0: off, > 0: as given
     void* d_resume = nullptr;           // [B][CARRY_PER_ENV] loop scalars of the solves the step kernel left unfinished
@@ -1006,6 +1008,57 @@ int launch_policy_any(const DojoSim* s, const DojoPolicy& p, const void* z, cons
     return s->dtype == DOJO_DTYPE_F32 ? launch_policy<float>(s, p, z, csg, uff, obs, u, sp) : launch_policy<double>(s, p, z, csg, uff, obs, u, sp);
 }
 
+// dojo_rollout_mlp_dev: the same controller with a tanh network in place of the mat-vec (dojo_mlp.hpp); act: [B][nh] of this step or null
+template <class TIO>
+int launch_mlp(const DojoSim* s, const DojoMlpPolicy& p, const dj::mlp::Shape& sh, const void* z, const void* csg, const void* uff, void* obs, void* u, double* act, const Span& sp) {
+    const int Nc = p.contact_forces ? s->M.Nc : 0, nobs = 2 * s->M.nu + Nc;
+    const dj::mlp::Args<TIO> A{(const dj::NodeP<double>*)s->d_nodes, (const TIO*)z, (const TIO*)csg, (const TIO*)p.theta, (const TIO*)p.mean, (const TIO*)p.scale,
+                               (const TIO*)uff, (TIO*)obs, (TIO*)u, act, (int)sp.env0, sp.nenv, s->M.Nb, s->M.nu, Nc, nobs, p.act_off, p.per_env ? 1 : 0, (int)sh.P, s->M.dt, sh};
+    hipLaunchKernelGGL((dj::mlp::rollout_mlp_kernel<TIO>), dim3((unsigned)((sp.nenv + dj::policy::ENVS - 1) / dj::policy::ENVS)), dim3(dj::policy::THREADS),
+                       dj::mlp::lds_bytes(nobs, sh.nh), sp.stream, A);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
+
+// The controller of a closed-loop rollout, as rollout_core sees it: the affine policy or the network (exactly one is set), and what the network records
+struct Controller {
+    const DojoPolicy* affine = nullptr;
+    const DojoMlpPolicy* mlp = nullptr;
+    dj::mlp::Shape shape{};
+    double* ACT = nullptr;              // [H][B][nh] or null
+    bool contact_forces() const { return affine ? affine->contact_forces != 0 : mlp->contact_forces != 0; }
+    bool contact_init() const { return affine ? affine->contact_init != 0 : mlp->contact_init != 0; }
+};
+// the controls of step k (u != null) or the observation of the final state (u = null, k = H)
+int launch_controller(const DojoSim* s, const Controller& c, int k, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
+    if (c.affine) return launch_policy_any(s, *c.affine, z, csg, uff, obs, u, sp);
+    double* const act = (c.ACT && u) ? c.ACT + (size_t)k * s->B * c.shape.nh : nullptr;
+    return s->dtype == DOJO_DTYPE_F32 ? launch_mlp<float>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp) : launch_mlp<double>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp);
+}
+
+// dojo_rollout_mlp_adjoint_dev: the sweep (one workgroup per environment, one launch) and, for a shared policy, the reduction over the batch
+template <class TIO>
+int launch_mlp_adjoint(const DojoSim* s, const DojoMlpPolicy& p, const dj::mlp::Shape& sh, int H, const DojoMlpAdjoint& a, const double* M, double* ws, hipStream_t st) {
+    const int nx = 12 * s->M.Nb, nu = (int)s->M.nu, nobs = 2 * nu;
+    dj::mlp::AdjointArgs<TIO> A{};
+    A.DZ = (const TIO*)a.DZ; A.DU = (const TIO*)a.DU; A.OBS = (const TIO*)a.OBS; A.ACT = a.ACT; A.M = M; A.G = (const TIO*)a.G; A.Z = (const TIO*)a.Z;
+    A.G_u = (const TIO*)a.G_u; A.G_obs = (const TIO*)a.G_obs; A.status = a.status; A.theta = (const TIO*)p.theta; A.mean = (const TIO*)p.mean; A.scale = (const TIO*)p.scale;
+    A.touch = dj::padjoint::Touch{s->d_touch_ptr, s->d_touch_ent};
+    A.ws = ws; A.gtheta = (TIO*)a.gtheta; A.gU = (TIO*)a.gU; A.gz = (TIO*)a.gz;
+    A.H = H; A.B = s->B; A.nx = nx; A.nu = nu; A.nobs = nobs; A.act_off = p.act_off; A.per_env = p.per_env ? 1 : 0; A.shared = p.per_env ? 0 : 1; A.cot_space = a.cot_space;
+    A.P = (int)sh.P; A.s = sh;
+    hipLaunchKernelGGL((dj::mlp::rollout_mlp_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::padjoint::THREADS), dj::mlp::adjoint_lds_bytes(nx, nu, nobs, sh.wmax, sh.nh), st, A);
+    HIPCHK(hipGetLastError());
+    if (!p.per_env && a.gtheta) {
+        const int nacc = (int)sh.P, per = dj::padjoint::THREADS / dj::adjoint::ROW;
+        // at n_layers = 1 theta is [W | bias], the order of the affine sweep's accumulators: every entry goes to the one output
+        hipLaunchKernelGGL((dj::padjoint::policy_reduce_kernel<TIO>), dim3((unsigned)((nacc + per - 1) / per)), dim3(dj::padjoint::THREADS), 0, st, (const double*)ws, s->B, nacc, nacc,
+                           (TIO*)a.gtheta, (TIO*)nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    return DOJO_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1357,10 +1410,10 @@ int dojo_gradients(DojoHandle s, void* dz, void* du) {
 // simulate! with pre-sampled controls (src/simulation/simulate.jl:16-37): H steps, each fed with the previous step's
 // internal next state; storage != null records save_to_storage! rows [H][B][Nb][25] of every solved step
 // DZ / DU != null: the IFT Jacobians of every step as well, [H][B][nx][nx] / [H][B][nu][nx] in the device layout of dojo_step_dev (dojo_rollout_record_dev)
-// pol != null (dojo_rollout_policy_dev; checked by the caller): U is the feed-forward term and the controls of step k are made on the group's stream, directly in front of
+// pol != null (dojo_rollout_policy_dev, dojo_rollout_mlp_dev; checked by the caller; a Controller of either kind): U is the feed-forward term and the controls of step k are made on the group's stream, directly in front of
 // the step, by the policy kernel -- into U_out[k] (null: one [B][nu] buffer of the handle, a group's launches being serial); OBS [H+1][B][nobs] or null records what it saw
 static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* storage, void* stream, void* DZ = nullptr, void* DU = nullptr,
-                        const DojoPolicy* pol = nullptr, void* OBS = nullptr, void* U_out = nullptr) {
+                        const Controller* pol = nullptr, void* OBS = nullptr, void* U_out = nullptr) {
     if (!s || !z0 || H < 1) { g_err = "dojo_rollout_dev: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, nx = 12 * s->M.Nb;
@@ -1369,7 +1422,7 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
     ENSURE(s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w);
     if (storage) ENSURE(s->d_res, B * 6 * s->M.Nb * w);
     if (pol && !U_out) ENSURE(s->d_pu, B * nu * w);
-    const size_t nobs = pol ? 2 * nu + (pol->contact_forces ? (size_t)s->M.Nc : 0) : 0;
+    const size_t nobs = pol ? 2 * nu + (pol->contact_forces() ? (size_t)s->M.Nc : 0) : 0;
     hipStream_t st = (hipStream_t)stream;
     const char* cur = (const char*)z0;      // the state a group's next step starts from; behind the loops: the last state (the same buffer for every group)
     int slot = -1; TRY(begin_timing(s, &slot, st));
@@ -1391,7 +1444,7 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
             const char* uk = (U && nu) ? (const char*)U + (size_t)k * B * nu * w : nullptr;
             if (pol) {
                 char* upol = U_out ? (char*)U_out + (size_t)k * B * nu * w : (char*)s->d_pu;
-                TRY(launch_policy_any(s, *pol, cur, (k > 0 || pol->contact_init) ? s->d_csg : nullptr, uk, OBS ? (char*)OBS + (size_t)k * B * nobs * w : nullptr, upol, sp));
+                TRY(launch_controller(s, *pol, k, cur, (k > 0 || pol->contact_init()) ? s->d_csg : nullptr, uk, OBS ? (char*)OBS + (size_t)k * B * nobs * w : nullptr, upol, sp));
                 uk = upol;
             }
             void* sk = storage ? (char*)storage + (size_t)k * B * 25 * s->M.Nb * w : nullptr;
@@ -1400,7 +1453,7 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
             TRY(launch_any(s, StepIO{cur, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, dzk, duk, nullptr, sk}, sp, m));
             cur = nxt;
         }
-        if (pol && OBS) TRY(launch_policy_any(s, *pol, cur, s->d_csg, nullptr, (char*)OBS + (size_t)H * B * nobs * w, nullptr, sp));      // the observation of the final state
+        if (pol && OBS) TRY(launch_controller(s, *pol, H, cur, s->d_csg, nullptr, (char*)OBS + (size_t)H * B * nobs * w, nullptr, sp));      // the observation of the final state
         if (NG > 1) { HIPCHK(hipEventRecord(s->gevents[gi], sp.stream)); HIPCHK(hipStreamWaitEvent(st, s->gevents[gi], 0)); }
     }
     TRY(end_timing(s, slot, false, H, st));
@@ -1446,7 +1499,8 @@ int dojo_rollout_policy_dev(DojoHandle s, const void* z0, const DojoPolicy* poli
     Enter enter_(s);
     TRY(refuse_policy(s, z0, policy, H, "dojo_rollout_policy_dev"));
     const DojoPolicy p = *policy;      // (the caller's struct is read during the call only)
-    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, nullptr, nullptr, &p, OBS, U_out);
+    Controller c; c.affine = &p;
+    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, nullptr, nullptr, &c, OBS, U_out);
 }
 
 // host pointers (the members of *policy too): upload, roll out on the device, download
@@ -1472,7 +1526,8 @@ int dojo_rollout_policy(DojoHandle s, const void* z0, const DojoPolicy* policy, 
     if (OBS) HIPCHK(dO.alloc((HB + B) * nobs * w));
     if (U_out) HIPCHK(dU.alloc(HB * nu * w));
     if (status) HIPCHK(dS.alloc(HB * sizeof(int)));
-    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, nullptr, nullptr, &p, dO.p, dU.p));
+    Controller c; c.affine = &p;
+    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, nullptr, nullptr, &c, dO.p, dU.p));
     HIPCHK(hipDeviceSynchronize());
     if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
     if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
@@ -1605,7 +1660,8 @@ int dojo_rollout_policy_record_dev(DojoHandle s, const void* z0, const DojoPolic
     if (!Z || !OBS || !U_out || !DZ || !DU) { g_err = "dojo_rollout_policy_record_dev: Z, OBS, U_out, DZ and DU are required"; return DOJO_ERR_INVALID; }
     TRY(refuse_record(s, "dojo_rollout_policy_record_dev"));
     const DojoPolicy p = *policy;
-    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, DZ, DU, &p, OBS, U_out);
+    Controller c; c.affine = &p;
+    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, DZ, DU, &c, OBS, U_out);
 }
 
 // everything the closed-loop sweep refuses, before anything is launched or allocated (z0 of refuse_policy: not this entry's -- the policy stands in)
@@ -1696,7 +1752,8 @@ int dojo_rollout_policy_gradients(DojoHandle s, const void* z0, const DojoPolicy
     HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dO.alloc((HB + B) * nobs * w)); HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
     HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w));
     HIPCHK(dgW.alloc(Bw * na * nobs * w)); HIPCHK(dgb.alloc(Bw * na * w)); HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w));
-    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, &p, dO.p, dU.p));
+    Controller c; c.affine = &p;
+    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, &c, dO.p, dU.p));
     a.DZ = dDZ.p; a.DU = dDU.p; a.OBS = dO.p; a.status = (const int32_t*)dS.p; a.z0 = z0d; a.Z = dZ.p; a.M = nullptr; a.cot_space = cot_space;
     a.gW = dgW.p; a.gbias = dgb.p; a.gU = dgU.p; a.gz = dgz.p;
     TRY(dojo_rollout_policy_adjoint_dev(s, &p, H, &a, nullptr));
@@ -1707,6 +1764,195 @@ int dojo_rollout_policy_gradients(DojoHandle s, const void* z0, const DojoPolicy
     if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
     if (gW) HIPCHK(hipMemcpy(gW, dgW.p, Bw * na * nobs * w, hipMemcpyDeviceToHost));
     if (gbias) HIPCHK(hipMemcpy(gbias, dgb.p, Bw * na * w, hipMemcpyDeviceToHost));
+    if (gU) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
+    return DOJO_OK;
+}
+
+// ---- closed-loop rollouts with a network policy, forward and reverse mode (dojo_mlp.hpp) ----
+// Everything the forward entries refuse, before anything is launched or allocated; *sh: what the widths determine
+static int refuse_mlp(DojoHandle s, const void* z0, const DojoMlpPolicy* p, int32_t H, const char* who, dj::mlp::Shape* sh) {
+    const std::string w_ = std::string(who) + ": ";
+    if (!s || !z0 || !p || !p->theta) { g_err = w_ + "bad argument (handle, z0, policy and policy->theta are required)"; return DOJO_ERR_INVALID; }
+    const int L = p->n_layers;
+    if (L < 1 || L > DOJO_MLP_MAX_LAYERS) { g_err = w_ + "n_layers must be 1 .. " + std::to_string(DOJO_MLP_MAX_LAYERS); return DOJO_ERR_INVALID; }
+    for (int l = 0; l <= L; ++l)
+        if (p->width[l] < 1) { g_err = w_ + "width[" + std::to_string(l) + "] must be >= 1"; return DOJO_ERR_INVALID; }
+    // the affine policy with the same observation and the same driven inputs: what dojo_rollout_policy_dev refuses
+    const DojoPolicy q{p->theta, nullptr, p->mean, p->scale, p->U_ff, p->per_env, p->act_off, p->width[L], p->contact_forces, p->contact_init, 0};
+    TRY(refuse_policy(s, z0, &q, H, who));
+    const long long nobs = 2 * (long long)s->M.nu + (p->contact_forces ? (long long)s->M.Nc : 0);
+    if (p->width[0] != nobs) { g_err = w_ + "width[0] must be the number of observations, " + std::to_string(nobs); return DOJO_ERR_INVALID; }
+    *sh = dj::mlp::shape(L, p->width);
+    if (sh->P > 0x7fffffffLL) { g_err = w_ + "supports fewer than 2^31 parameters per policy"; return DOJO_ERR_UNSUPPORTED; }
+    if (dj::mlp::lds_bytes((int)nobs, sh->nh) > 65536) {
+        g_err = w_ + "the controller keeps 4 (nobs + nh) doubles in LDS (nh: the hidden units), which exceeds 64 KB for this policy"; return DOJO_ERR_UNSUPPORTED;
+    }
+    return DOJO_OK;
+}
+
+int dojo_rollout_mlp_dev(DojoHandle s, const void* z0, const DojoMlpPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, double* ACT, int32_t* status, void* stream) {
+    Enter enter_(s);
+    Controller c;
+    TRY(refuse_mlp(s, z0, policy, H, "dojo_rollout_mlp_dev", &c.shape));
+    const DojoMlpPolicy p = *policy;      // (the caller's struct is read during the call only)
+    c.mlp = &p; c.ACT = c.shape.nh ? ACT : nullptr;
+    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, nullptr, nullptr, &c, OBS, U_out);
+}
+
+// host pointers (the members of *policy too): upload, roll out on the device, download
+int dojo_rollout_mlp(DojoHandle s, const void* z0, const DojoMlpPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, int32_t* status) {
+    Enter enter_(s);
+    Controller c;
+    TRY(refuse_mlp(s, z0, policy, H, "dojo_rollout_mlp", &c.shape));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, Bw = policy->per_env ? B : 1, P = (size_t)c.shape.P;
+    const size_t nobs = 2 * nu + (policy->contact_forces ? (size_t)s->M.Nc : 0);
+    DojoMlpPolicy p = *policy;
+    DevBuf dz0, dth, dm, dsc, dUff, dZ, dO, dU, dS;
+    auto up = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
+        *dst = nullptr;
+        if (!src) return DOJO_OK;
+        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        *dst = d.p;
+        return DOJO_OK;
+    };
+    const void* z0d = nullptr;
+    TRY(up(dz0, z0, B * nz * w, &z0d)); TRY(up(dth, policy->theta, Bw * P * w, &p.theta));
+    TRY(up(dm, policy->mean, nobs * w, &p.mean)); TRY(up(dsc, policy->scale, nobs * w, &p.scale)); TRY(up(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
+    if (Z) HIPCHK(dZ.alloc(HB * nz * w));
+    if (OBS) HIPCHK(dO.alloc((HB + B) * nobs * w));
+    if (U_out) HIPCHK(dU.alloc(HB * nu * w));
+    if (status) HIPCHK(dS.alloc(HB * sizeof(int)));
+    c.mlp = &p;
+    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, nullptr, nullptr, &c, dO.p, dU.p));
+    HIPCHK(hipDeviceSynchronize());
+    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
+    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
+    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
+    if (Z) HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
+    return DOJO_OK;
+}
+
+int dojo_rollout_mlp_record_dev(DojoHandle s, const void* z0, const DojoMlpPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, double* ACT, int32_t* status,
+                                void* DZ, void* DU, void* stream) {
+    Enter enter_(s);
+    const char* who = "dojo_rollout_mlp_record_dev";
+    Controller c;
+    TRY(refuse_mlp(s, z0, policy, H, who, &c.shape));
+    if (!Z || !OBS || !U_out || !DZ || !DU) { g_err = std::string(who) + ": Z, OBS, U_out, DZ and DU are required"; return DOJO_ERR_INVALID; }
+    if (policy->n_layers > 1 && !ACT) { g_err = std::string(who) + ": ACT is required with n_layers > 1 (the sweep reads the activations from it)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_record(s, who));
+    const DojoMlpPolicy p = *policy;
+    c.mlp = &p; c.ACT = c.shape.nh ? ACT : nullptr;
+    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, DZ, DU, &c, OBS, U_out);
+}
+
+// everything the network sweep refuses, before anything is launched or allocated (z0 of refuse_mlp: not this entry's -- the policy stands in)
+static int refuse_mlp_adjoint(DojoHandle s, const DojoMlpPolicy* p, int32_t H, const char* who, dj::mlp::Shape* sh) {
+    const std::string w_ = std::string(who) + ": ";
+    TRY(refuse_mlp(s, p, p, H, who, sh));
+    if (p->contact_forces) {
+        g_err = w_ + "contact_forces = 1 is not supported in reverse mode (the derivative of the previous step's impulses w.r.t. the state is not part of the record)";
+        return DOJO_ERR_UNSUPPORTED;
+    }
+    if (dj::mlp::adjoint_lds_bytes(12 * s->M.Nb, (int)s->M.nu, 2 * (int)s->M.nu, sh->wmax, sh->nh) > 65536) {
+        g_err = w_ + "the sweep keeps 4 nx + nu + 2 nobs + 2 wmax + nh doubles in LDS, which exceeds 64 KB for this mechanism and policy"; return DOJO_ERR_UNSUPPORTED;
+    }
+    return DOJO_OK;
+}
+
+int dojo_rollout_mlp_adjoint_dev(DojoHandle s, const DojoMlpPolicy* policy, int32_t H, const DojoMlpAdjoint* a_, void* stream) {
+    Enter enter_(s);
+    const char* who = "dojo_rollout_mlp_adjoint_dev";
+    const std::string w_ = std::string(who) + ": ";
+    dj::mlp::Shape sh{};
+    TRY(refuse_mlp_adjoint(s, policy, H, who, &sh));
+    if (!a_) { g_err = w_ + "the argument record must not be NULL"; return DOJO_ERR_INVALID; }
+    const DojoMlpPolicy p = *policy; const DojoMlpAdjoint a = *a_;      // (the caller's structs are read during the call only)
+    if (!a.DZ || !a.OBS || !a.G) { g_err = w_ + "DZ, OBS and G must not be NULL"; return DOJO_ERR_INVALID; }
+    if (!a.DU) { g_err = w_ + "gU, gtheta and gz need DU"; return DOJO_ERR_INVALID; }
+    if (p.n_layers > 1 && !a.ACT) { g_err = w_ + "ACT is required with n_layers > 1 (the recorded activations)"; return DOJO_ERR_INVALID; }
+    if (a.cot_space != 0 && a.cot_space != 1) { g_err = w_ + "cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
+    if (a.cot_space == 1 && !a.Z) { g_err = w_ + "cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
+    if (!a.M && (!a.z0 || !a.Z)) { g_err = w_ + "M = NULL needs z0 and Z (the observation Jacobians are computed from them)"; return DOJO_ERR_INVALID; }
+    if ((((uintptr_t)a.DZ) | (uintptr_t)a.DU) & 15) { g_err = w_ + "DZ and DU must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the record)
+    if (!a.gtheta && !a.gU && !a.gz) return DOJO_OK;
+    const size_t B = s->B, nobs = 2 * s->M.nu;
+    const double* M = a.M;
+    if (!M) {
+        const long long n = (long long)H + (a.G_obs ? 1 : 0);
+        TRY(ensure_at_least(s, &s->d_pM, &s->pM_bytes, ((size_t)H + 1) * B * nobs * 24 * sizeof(double)));
+        TRY(launch_observation_jacobian(s, a.z0, a.Z, n, (double*)s->d_pM, st));
+        M = (const double*)s->d_pM;
+    }
+    TRY(ensure_at_least(s, (void**)&s->d_macc, &s->macc_bytes, B * (size_t)sh.P * sizeof(double)));
+    return s->dtype == DOJO_DTYPE_F32 ? launch_mlp_adjoint<float>(s, p, sh, H, a, M, s->d_macc, st) : launch_mlp_adjoint<double>(s, p, sh, H, a, M, s->d_macc, st);
+}
+
+// host pointers (the members of *policy too): upload, record on the device, sweep, download -- the Jacobians, M and ACT do not cross PCIe
+int dojo_rollout_mlp_gradients(DojoHandle s, const void* z0, const DojoMlpPolicy* policy, int32_t H, const void* G, int32_t cot_space, const void* G_u, const void* G_obs,
+                               void* Z, void* OBS, void* U_out, int32_t* status, void* gtheta, void* gU, void* gz) {
+    Enter enter_(s);
+    const char* who = "dojo_rollout_mlp_gradients";
+    const std::string w_ = std::string(who) + ": ";
+    Controller c;
+    if (!z0) { g_err = w_ + "bad argument (handle, z0, policy and policy->theta are required)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_mlp_adjoint(s, policy, H, who, &c.shape));
+    if (!G || (cot_space != 0 && cot_space != 1)) { g_err = w_ + "G is required and cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_record(s, who));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
+    const size_t Bw = policy->per_env ? B : 1, nobs = 2 * nu, P = (size_t)c.shape.P, nh = (size_t)c.shape.nh;
+    const size_t record = HB * nx * (nx + nu) * w, mbytes = (HB + B) * nobs * 24 * sizeof(double), abytes = HB * nh * sizeof(double), wsbytes = B * P * sizeof(double);
+    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
+    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + 3 * up(HB * nu * w) + up(B * nx * w)
+                  + 2 * up((HB + B) * nobs * w) + 2 * up(Bw * P * w) + 2 * up(nobs * w) + (policy->U_ff ? up(HB * nu * w) : 0)
+                  + ((s->d_pM && s->pM_bytes >= mbytes) ? 0 : up(mbytes)) + (nh ? up(abytes) : 0) + ((s->d_macc && s->macc_bytes >= wsbytes) ? 0 : up(wsbytes));
+    need += record_workspaces(s);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b) {
+        g_err = w_ + "the record of " + std::to_string(record) + " bytes, the observation Jacobians of " + std::to_string(mbytes) + " bytes, the activations of " + std::to_string(abytes)
+                + " bytes and the accumulators of " + std::to_string(wsbytes) + " bytes (" + std::to_string(need) + " bytes with the other buffers of the call) do not fit into the "
+                + std::to_string(free_b) + " bytes of free device memory";
+        return DOJO_ERR_INVALID;
+    }
+    DojoMlpPolicy p = *policy;
+    DevBuf dz0, dth, dm, dsc, dUff, dG, dGu, dGo, dZ, dO, dU, dS, dA, dDZ, dDU, dgth, dgU, dgz;
+    auto upl = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
+        *dst = nullptr;
+        if (!src) return DOJO_OK;
+        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        *dst = d.p;
+        return DOJO_OK;
+    };
+    DojoMlpAdjoint a{};
+    const void* z0d = nullptr;
+    TRY(upl(dz0, z0, B * nz * w, &z0d)); TRY(upl(dth, policy->theta, Bw * P * w, &p.theta));
+    TRY(upl(dm, policy->mean, nobs * w, &p.mean)); TRY(upl(dsc, policy->scale, nobs * w, &p.scale)); TRY(upl(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
+    TRY(upl(dG, G, HB * ng * w, &a.G)); TRY(upl(dGu, G_u, HB * nu * w, &a.G_u)); TRY(upl(dGo, G_obs, (HB + B) * nobs * w, &a.G_obs));
+    HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dO.alloc((HB + B) * nobs * w)); HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
+    if (nh) HIPCHK(dA.alloc(abytes));
+    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w));
+    HIPCHK(dgth.alloc(Bw * P * w)); HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w));
+    c.mlp = &p; c.ACT = nh ? (double*)dA.p : nullptr;
+    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, &c, dO.p, dU.p));
+    a.DZ = dDZ.p; a.DU = dDU.p; a.OBS = dO.p; a.ACT = c.ACT; a.status = (const int32_t*)dS.p; a.z0 = z0d; a.Z = dZ.p; a.M = nullptr; a.cot_space = cot_space;
+    a.gtheta = dgth.p; a.gU = dgU.p; a.gz = dgz.p;
+    TRY(dojo_rollout_mlp_adjoint_dev(s, &p, H, &a, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
+    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
+    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
+    if (gtheta) HIPCHK(hipMemcpy(gtheta, dgth.p, Bw * P * w, hipMemcpyDeviceToHost));
     if (gU) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
     if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));

@@ -43,7 +43,8 @@ def lib():
                   "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
                   "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients", "dojo_rollout_policy_dev", "dojo_rollout_policy",
                   "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
-                  "dojo_rollout_policy_gradients"):
+                  "dojo_rollout_policy_gradients",
+                  "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients"):
             getattr(L, f).restype = C.c_int
         L.dojo_destroy.restype = None
         _lib = L
@@ -61,7 +62,8 @@ EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error",
                     "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients",
                     "dojo_rollout_policy_dev", "dojo_rollout_policy",
                     "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
-                    "dojo_rollout_policy_gradients"]
+                    "dojo_rollout_policy_gradients",
+                    "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients"]
 
 
 class DojoPolicy(C.Structure):
@@ -77,6 +79,71 @@ class DojoPolicyAdjoint(C.Structure):
     _fields_ = [("DZ", C.c_void_p), ("DU", C.c_void_p), ("OBS", C.c_void_p), ("status", C.c_void_p), ("z0", C.c_void_p), ("Z", C.c_void_p), ("M", C.c_void_p),
                 ("G", C.c_void_p), ("G_u", C.c_void_p), ("G_obs", C.c_void_p), ("gW", C.c_void_p), ("gbias", C.c_void_p), ("gU", C.c_void_p), ("gz", C.c_void_p),
                 ("cot_space", C.c_int32), ("reserved", C.c_int32)]
+
+
+MLP_MAX_LAYERS = 4      # DOJO_MLP_MAX_LAYERS
+
+
+class DojoMlpPolicy(C.Structure):
+    """include/dojo_hip.h `DojoMlpPolicy`: the tanh network policy h_l = tanh(b_l + W_l h_{l-1}), u = U_ff + E (b_L + W_L h_{L-1}); theta is the flat
+    parameter vector of `pack_mlp`; device pointers for dojo_rollout_mlp_dev, host pointers for dojo_rollout_mlp"""
+    _fields_ = [("theta", C.c_void_p), ("mean", C.c_void_p), ("scale", C.c_void_p), ("U_ff", C.c_void_p),
+                ("per_env", C.c_int32), ("act_off", C.c_int32), ("n_layers", C.c_int32), ("width", C.c_int32 * (MLP_MAX_LAYERS + 1)),
+                ("contact_forces", C.c_int32), ("contact_init", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DojoMlpAdjoint(C.Structure):
+    """include/dojo_hip.h `DojoMlpAdjoint`: the record (with the activations ACT), the cotangents and the outputs of dojo_rollout_mlp_adjoint_dev"""
+    _fields_ = [("DZ", C.c_void_p), ("DU", C.c_void_p), ("OBS", C.c_void_p), ("ACT", C.c_void_p), ("status", C.c_void_p), ("z0", C.c_void_p), ("Z", C.c_void_p),
+                ("M", C.c_void_p), ("G", C.c_void_p), ("G_u", C.c_void_p), ("G_obs", C.c_void_p), ("gtheta", C.c_void_p), ("gU", C.c_void_p), ("gz", C.c_void_p),
+                ("cot_space", C.c_int32), ("reserved", C.c_int32)]
+
+
+def mlp_sizes(widths):
+    """-> (P, nh): the entries of theta, P = sum_l n_l (n_{l-1} + 1), and the hidden units n_1 + .. + n_{L-1} of the widths [n_0, .., n_L]"""
+    w = [int(n) for n in widths]
+    if not 2 <= len(w) <= MLP_MAX_LAYERS + 1 or min(w) < 1:
+        raise ValueError("widths must be [n_0, .., n_L] with 1 <= L <= %d and every width >= 1" % MLP_MAX_LAYERS)
+    return sum(w[l] * (w[l - 1] + 1) for l in range(1, len(w))), sum(w[1:-1])
+
+
+def mlp_policy_struct(theta, mean, scale, U_ff, per_env, act_off, widths, contact_forces=0, contact_init=0):
+    """a DojoMlpPolicy from addresses (int or None) and the widths"""
+    w = [int(n) for n in widths]
+    arr = (C.c_int32 * (MLP_MAX_LAYERS + 1))(*(w + [0] * (MLP_MAX_LAYERS + 1 - len(w)))[:MLP_MAX_LAYERS + 1])
+    return DojoMlpPolicy(theta, mean, scale, U_ff, int(per_env), int(act_off), len(w) - 1, arr, int(contact_forces), int(contact_init), 0)
+
+
+def pack_mlp(weights, biases):
+    """weights [W_1 .. W_L], W_l [n_l, n_{l-1}] (or [B, n_l, n_{l-1}]: one policy per environment), biases [b_1 .. b_L], b_l [n_l] (or [B, n_l])
+    -> (theta, widths): theta [P] (or [B, P]) in the layout of the ABI -- layer after layer W_l row-major, then b_l -- and widths [n_0, .., n_L]"""
+    Ws = [np.asarray(W) for W in weights]; bs = [np.asarray(b) for b in biases]
+    if not Ws or len(Ws) != len(bs):
+        raise ValueError("pack_mlp needs one bias per weight matrix")
+    lead = Ws[0].shape[:-2]
+    widths = [int(Ws[0].shape[-1])]
+    parts = []
+    for W, b in zip(Ws, bs):
+        if W.ndim != len(lead) + 2 or W.shape[:-2] != lead or W.shape[-1] != widths[-1] or b.shape != lead + (W.shape[-2],):
+            raise ValueError("pack_mlp: W_l must be [.., n_l, n_{l-1}] and b_l [.., n_l] with matching widths")
+        widths.append(int(W.shape[-2]))
+        parts += [W.reshape(lead + (-1,)), b]
+    return np.ascontiguousarray(np.concatenate(parts, axis=-1)), widths
+
+
+def unpack_mlp(theta, widths):
+    """the inverse of pack_mlp: theta [P] or [B, P] -> (weights, biases), views into theta"""
+    theta = np.asarray(theta); w = [int(n) for n in widths]
+    P, _ = mlp_sizes(w)
+    if theta.shape[-1] != P:
+        raise ValueError("theta has %d entries, the widths %s need %d" % (theta.shape[-1], w, P))
+    lead, o = theta.shape[:-1], 0
+    Ws, bs = [], []
+    for l in range(1, len(w)):
+        n = w[l] * w[l - 1]
+        Ws.append(theta[..., o:o + n].reshape(lead + (w[l], w[l - 1]))); o += n
+        bs.append(theta[..., o:o + w[l]]); o += w[l]
+    return Ws, bs
 
 
 # columns of a Storage row (src/simulation/storage.jl:15-24)
@@ -349,6 +416,69 @@ class BatchedMechanism:
         _chk(lib().dojo_rollout_policy_gradients(self.h, _p(z0), C.byref(pol), H, _p(G), cs, _p(G_u), _p(G_obs), _p(Z), _p(OBS), _p(U), _p(st),
                                                  _p(gW), _p(gb), _p(gU), _p(gz)))
         return Z, OBS, U, st, gW, gb, gU, gz
+
+    def _mlp_args(self, theta, widths):
+        """theta [P] or [B, P] in the handle dtype, the widths as ints, whether there is one policy per environment"""
+        w = [int(n) for n in widths]
+        P, _ = mlp_sizes(w)
+        theta = np.ascontiguousarray(theta, dtype=self.np_dtype)
+        if theta.ndim not in (1, 2):
+            raise ValueError("theta must be [P] or [B, P]")
+        per_env = theta.ndim == 2
+        theta = self._arr(theta, (self.batch, P) if per_env else (P,))
+        return theta, w, per_env
+
+    def rollout_mlp(self, z0, theta, widths, steps, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):
+        """Closed-loop rollout with a tanh network policy (dojo_rollout_mlp): `rollout_policy` with h_l = tanh(b_l + W_l h_{l-1}), h_0 = (o_k - mean) .* scale,
+        u_k = U_ff[k] + E (b_L + W_L h_{L-1}) evaluated on the device between the steps.  theta [P] (shared) or [B, P] (one policy per environment) and
+        widths [n_0 = nobs, .., n_L = na] as `pack_mlp` returns them.  Returns (Z [H,B,13Nb], OBS [H+1,B,nobs], U [H,B,nu], status [H,B])."""
+        B, s = self.batch, self.spec
+        H = int(steps)
+        z0 = self._arr(z0, (B, s.nz))
+        nobs = 2 * s.nu + (len(s.contacts) if contact_forces else 0)
+        theta, w, per_env = self._mlp_args(theta, widths)
+        mean = None if mean is None else self._arr(mean, (nobs,))
+        scale = None if scale is None else self._arr(scale, (nobs,))
+        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        pol = mlp_policy_struct(ptr(theta), ptr(mean), ptr(scale), ptr(U_ff), per_env, act_off, w, bool(contact_forces), contact_init)
+        Z = np.empty((max(H, 0), B, s.nz), self.np_dtype); OBS = np.empty((max(H, 0) + 1, B, nobs), self.np_dtype)
+        U = np.empty((max(H, 0), B, s.nu), self.np_dtype); st = np.empty((max(H, 0), B), np.int32)
+        _chk(lib().dojo_rollout_mlp(self.h, _p(z0), C.byref(pol), H, _p(Z), _p(OBS), _p(U), _p(st)))
+        return Z, OBS, U, st
+
+    def rollout_mlp_gradients(self, z0, theta, widths, G, steps=None, mean=None, scale=None, U_ff=None, act_off=0, G_u=None, G_obs=None, cot_space="tangent"):
+        """Reverse mode through `rollout_mlp` (dojo_rollout_mlp_gradients; without contact observations): the rollout and the gradient of a trajectory
+        loss w.r.t. the network's parameters, the feed-forward term and the initial state; the record, the observation Jacobians and the activations
+        stay on the device.  Cotangents as in `rollout_policy_gradients`.  Returns (Z, OBS, U, status, gtheta, gU [H,B,nu], gz0 [B,nx] tangent); gtheta
+        has the shape of theta ([B, P]; or [P], summed over the batch, for a shared policy)."""
+        B, s = self.batch, self.spec
+        z0 = self._arr(z0, (B, s.nz))
+        if cot_space not in ("tangent", "state", 0, 1):
+            raise ValueError("cot_space must be 'tangent' or 'state'")
+        cs = 1 if cot_space in ("state", 1) else 0
+        if G is None:
+            raise ValueError("rollout_mlp_gradients needs the cotangents G of the loss w.r.t. the state after every step")
+        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
+        if G.shape != (H, B, s.nz if cs else s.nx):
+            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
+        if steps is not None and int(steps) != H:
+            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
+        nobs = 2 * s.nu
+        theta, w, per_env = self._mlp_args(theta, widths)
+        mean = None if mean is None else self._arr(mean, (nobs,))
+        scale = None if scale is None else self._arr(scale, (nobs,))
+        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
+        G_u = None if G_u is None else self._arr(G_u, (H, B, s.nu))
+        G_obs = None if G_obs is None else self._arr(G_obs, (H + 1, B, nobs))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        pol = mlp_policy_struct(ptr(theta), ptr(mean), ptr(scale), ptr(U_ff), per_env, act_off, w)
+        Z = np.empty((H, B, s.nz), self.np_dtype); OBS = np.empty((H + 1, B, nobs), self.np_dtype)
+        U = np.empty((H, B, s.nu), self.np_dtype); st = np.empty((H, B), np.int32)
+        gth = np.empty_like(theta); gU = np.empty((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
+        _chk(lib().dojo_rollout_mlp_gradients(self.h, _p(z0), C.byref(pol), H, _p(G), cs, _p(G_u), _p(G_obs), _p(Z), _p(OBS), _p(U), _p(st),
+                                              _p(gth), _p(gU), _p(gz)))
+        return Z, OBS, U, st, gth, gU, gz
 
     def set_external_force(self, fext):
         """set_external_force!(body; force, torque) for all bodies: fext [B, Nb, 6] = [Fext (world); τext (body frame)],

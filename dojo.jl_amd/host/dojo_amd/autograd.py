@@ -7,6 +7,10 @@ Jacobians and the reverse sweep are the library's kernels, include/dojo_hip.h "R
     Z, OBS, U = differentiable_policy_rollout(mech, z0, W, bias=b, U_ff=Uff)     # closed loop: u_k = U_ff[k] + E (b + W ((o_k - mean) .* scale))
     loss(Z, OBS, U).backward()                       # W.grad, b.grad, Uff.grad, z0.grad
 
+    theta = torch.cat([t.reshape(-1) for layer in net for t in (layer.weight, layer.bias)])      # a torch.nn tanh MLP in the layout of api.pack_mlp
+    Z, OBS, U = differentiable_mlp_rollout(mech, z0, theta, widths, U_ff=Uff)      # closed loop through the network
+    loss(Z, OBS, U).backward()                       # reaches the modules' parameters through the cat
+
 Everything is enqueued on torch's current stream and nothing synchronizes.  The gradient is the chain of the handle's gradient mode:
 set `mech.set_gradient_mode(api.GRAD_CONSISTENT)` for the derivative of the rollout.
 """
@@ -159,5 +163,82 @@ def differentiable_policy_rollout(mech, z0, W, bias=None, U_ff=None, steps=None,
     to state shape as in differentiable_rollout), W, bias and U_ff; mean and scale are frozen.  A shared W receives the sum over the batch.
     Z.status [H,B] (int32, non-differentiable) is the solver status of every step; nothing flows through a failed step's Jacobians."""
     Z, OBS, U, status = _PolicyRollout.apply(mech, z0, W, bias, U_ff, steps, mean, scale, act_off)
+    Z.status = status
+    return Z, OBS, U
+
+
+class _MlpRollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mech, z0, theta, widths, U_ff, steps, mean, scale, act_off):
+        s, B = mech.spec, mech.batch
+        dt = torch.float32 if mech.dtype_code == 1 else torch.float64
+        nobs = 2 * s.nu
+        w = [int(n) for n in widths]
+        P, nh = api.mlp_sizes(w)
+
+        def want(t, what, shapes):
+            if t is None:
+                return None
+            if not t.is_cuda or t.dtype != dt or tuple(t.shape) not in shapes:
+                raise ValueError("%s must be a %s device tensor of shape %s" % (what, dt, " or ".join(str(x) for x in shapes)))
+            return t.contiguous()
+        z0c = want(z0, "z0", [(B, s.nz)])
+        if theta is None or theta.dim() not in (1, 2):
+            raise ValueError("theta must be [P] or [B, P]")
+        per_env = theta.dim() == 2
+        thc = want(theta, "theta", [(B, P) if per_env else (P,)])
+        mc, sc = want(mean, "mean", [(nobs,)]), want(scale, "scale", [(nobs,)])
+        if U_ff is not None:
+            H = int(U_ff.shape[0]); Uc = want(U_ff, "U_ff", [(H, B, s.nu)])
+        else:
+            H = int(steps); Uc = None
+        dev = z0.device
+        Z = torch.empty((H, B, s.nz), dtype=dt, device=dev); OBS = torch.empty((H + 1, B, nobs), dtype=dt, device=dev)
+        U = torch.empty((H, B, s.nu), dtype=dt, device=dev); status = torch.empty((H, B), dtype=torch.int32, device=dev)
+        ACT = torch.empty((H, B, nh), dtype=torch.float64, device=dev)      # the record: freed with the graph
+        DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)
+        DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev)
+        p = lambda t: None if t is None else t.data_ptr()
+        pol = api.mlp_policy_struct(p(thc), p(mc), p(sc), p(Uc), per_env, act_off, w)
+        api._chk(api.lib().dojo_rollout_mlp_record_dev(mech.h, _ptr(z0c), C.byref(pol), H, _ptr(Z), _ptr(OBS), _ptr(U), _ptr(ACT), _ptr(status), _ptr(DZ), _ptr(DU),
+                                                       _stream(dev)))
+        ctx.mech, ctx.H, ctx.per_env, ctx.widths, ctx.act_off = mech, H, per_env, w, int(act_off)
+        ctx.has = (U_ff is not None, mean is not None, scale is not None)
+        ctx.save_for_backward(z0c, thc, Z, OBS, status, DZ, DU, ACT, *[t for t in (mc, sc) if t is not None])
+        ctx.mark_non_differentiable(status)
+        return Z, OBS, U, status
+
+    @staticmethod
+    def backward(ctx, gZ, gOBS, gU_out, _gstatus):
+        mech, H = ctx.mech, ctx.H
+        s, B = mech.spec, mech.batch
+        z0, theta, Z, OBS, status, DZ, DU, ACT = ctx.saved_tensors[:8]
+        rest = list(ctx.saved_tensors[8:])
+        mean = rest.pop(0) if ctx.has[1] else None
+        scale = rest.pop(0) if ctx.has[2] else None
+        dt, dev = Z.dtype, Z.device
+        gZ = torch.zeros_like(Z) if gZ is None else gZ.contiguous()
+        gOBS = None if gOBS is None else gOBS.contiguous()
+        gU_out = None if gU_out is None else gU_out.contiguous()
+        need = ctx.needs_input_grad                    # (mech, z0, theta, widths, U_ff, steps, mean, scale, act_off)
+        gth = torch.empty_like(theta) if need[2] else None
+        gU = torch.empty((H, B, s.nu), dtype=dt, device=dev) if (ctx.has[0] and need[4]) else None
+        gz = torch.empty((B, s.nx), dtype=dt, device=dev) if need[1] else None
+        p = lambda t: None if t is None else t.data_ptr()
+        pol = api.mlp_policy_struct(p(theta), p(mean), p(scale), None, ctx.per_env, ctx.act_off, ctx.widths)
+        a = api.DojoMlpAdjoint(p(DZ), p(DU), p(OBS), p(ACT) if ACT.numel() else None, p(status), p(z0), p(Z), None, p(gZ), p(gU_out), p(gOBS), p(gth), p(gU), p(gz), 1, 0)
+        api._chk(api.lib().dojo_rollout_mlp_adjoint_dev(mech.h, C.byref(pol), H, C.byref(a), _stream(dev)))
+        return None, (lift_tangent(gz, z0) if gz is not None else None), gth, None, gU, None, None, None, None
+
+
+def differentiable_mlp_rollout(mech, z0, theta, widths, U_ff=None, steps=None, mean=None, scale=None, act_off=0):
+    """-> (Z [H,B,13Nb], OBS [H+1,B,2nu], U [H,B,nu]): the closed-loop rollout from z0 under the tanh network of include/dojo_hip.h `DojoMlpPolicy` as a node of
+    torch's graph.  theta is ONE flat tensor, [P] (shared) or [B, P] (one policy per environment), in the layout of api.pack_mlp -- layer after layer the
+    row-major weight, then the bias -- so that the parameters of a torch.nn module reach it through torch.cat; widths = [n_0 = 2 nu, .., n_L = na].
+    Forward: dojo_rollout_mlp_record_dev into torch-owned tensors (the activations ACT are saved for backward beside DZ and DU); backward: ONE
+    dojo_rollout_mlp_adjoint_dev call with the cotangents of all three outputs.  Gradients flow to z0 (lifted to state shape as in
+    differentiable_rollout), theta and U_ff; mean and scale are frozen.  A shared theta receives the sum over the batch.  Z.status [H,B] (int32,
+    non-differentiable) is the solver status of every step; nothing flows through a failed step's Jacobians."""
+    Z, OBS, U, status = _MlpRollout.apply(mech, z0, theta, widths, U_ff, steps, mean, scale, act_off)
     Z.status = status
     return Z, OBS, U

@@ -241,6 +241,66 @@ function rollout_policy_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, W::Arr
     return Z, OBS, U, status, gW, gbias, gU, gz
 end
 
+"mirror of `DojoMlpPolicy` (include/dojo_hip.h): four pointers, three Int32, the five widths, three Int32"
+struct DojoMlpPolicy
+    theta::Ptr{Cvoid}; mean::Ptr{Cvoid}; scale::Ptr{Cvoid}; U_ff::Ptr{Cvoid}
+    per_env::Int32; act_off::Int32; n_layers::Int32; width::NTuple{5,Int32}
+    contact_forces::Int32; contact_init::Int32; reserved::Int32
+end
+mlp_widths(widths) = (1 <= length(widths) - 1 <= 4 || error("widths must be [n_0, .., n_L] with 1 <= L <= 4");
+                      ntuple(i -> Int32(i <= length(widths) ? widths[i] : 0), 5))
+mlp_parameters(widths) = sum(widths[l + 1] * (widths[l] + 1) for l in 1:length(widths) - 1)
+
+"""
+closed-loop rollout with a tanh network policy: `rollout_policy` with h_l = tanh.(b_l + W_l h_{l-1}), h_0 = (o_k - mean) .* scale,
+u_k = U_ff[k] + E (b_L + W_L h_{L-1}) evaluated on the device between the steps.  theta[P] (shared) or theta[P, B] (one policy per environment) is the
+flat parameter vector of the ABI: layer after layer W_l ROW-major [n_l][n_{l-1}] (i.e. `vec(W_l')`), then b_l; widths = [n_0 = nobs, .., n_L = na].
+-> Z[nz, B, H], OBS[nobs, B, H + 1], U[nu, B, H], status[B, H].
+"""
+function rollout_mlp(bm::BatchedMechanism{T}, z0::Matrix{T}, theta::Array{T}, widths::Vector{<:Integer}, H::Integer; mean::Union{Nothing,Vector{T}}=nothing,
+                     scale::Union{Nothing,Vector{T}}=nothing, U_ff::Union{Nothing,Array{T,3}}=nothing, act_off::Integer=0, contact_forces::Bool=false,
+                     contact_init::Integer=0, opts=Dojo.SolverOptions{Float64}()) where T
+    set_options!(bm, opts)
+    nobs = widths[1]
+    size(theta, 1) == mlp_parameters(widths) || error("theta must have $(mlp_parameters(widths)) rows")
+    Z = Array{T}(undef, bm.nz, bm.batch, H); OBS = Array{T}(undef, nobs, bm.batch, H + 1)
+    U = Array{T}(undef, bm.nu, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve theta mean scale U_ff begin
+        pol = Ref(DojoMlpPolicy(p(theta), p(mean), p(scale), p(U_ff), Int32(ndims(theta) == 2), Int32(act_off), Int32(length(widths) - 1), mlp_widths(widths),
+                                Int32(contact_forces), Int32(contact_init), Int32(0)))
+        check(@ccall $(fn(:dojo_rollout_mlp))(bm.handle::Ptr{Cvoid}, z0::Ptr{T}, pol::Ptr{DojoMlpPolicy}, Int32(H)::Int32, Z::Ptr{T}, OBS::Ptr{T}, U::Ptr{T}, status::Ptr{Int32})::Cint)
+    end
+    return Z, OBS, U, status
+end
+
+"""
+reverse mode through `rollout_mlp` (without contact observations): the rollout and the gradient of a trajectory loss w.r.t. the network's parameters,
+the feed-forward term and the initial state; the record, the observation Jacobians and the activations stay on the device.  Cotangents as in
+`rollout_policy_gradients`.  -> Z, OBS, U, status, gtheta (the shape of theta; summed over the batch for a shared policy), gU[nu, B, H], gz0[nx, B].
+"""
+function rollout_mlp_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, theta::Array{T}, widths::Vector{<:Integer}, G::Array{T,3};
+                               mean::Union{Nothing,Vector{T}}=nothing, scale::Union{Nothing,Vector{T}}=nothing, U_ff::Union{Nothing,Array{T,3}}=nothing,
+                               act_off::Integer=0, G_u::Union{Nothing,Array{T,3}}=nothing, G_obs::Union{Nothing,Array{T,3}}=nothing,
+                               cot_space::Symbol=:tangent, opts=Dojo.SolverOptions{Float64}()) where T
+    set_options!(bm, opts)
+    H = size(G, 3); nobs = 2 * bm.nu
+    widths[1] == nobs || error("widths[1] must be nobs = $nobs")
+    size(theta, 1) == mlp_parameters(widths) || error("theta must have $(mlp_parameters(widths)) rows")
+    Z = Array{T}(undef, bm.nz, bm.batch, H); OBS = Array{T}(undef, nobs, bm.batch, H + 1)
+    U = Array{T}(undef, bm.nu, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    gtheta = similar(theta); gU = Array{T}(undef, bm.nu, bm.batch, H); gz = Matrix{T}(undef, bm.nx, bm.batch)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve theta mean scale U_ff G_u G_obs begin
+        pol = Ref(DojoMlpPolicy(p(theta), p(mean), p(scale), p(U_ff), Int32(ndims(theta) == 2), Int32(act_off), Int32(length(widths) - 1), mlp_widths(widths),
+                                Int32(0), Int32(0), Int32(0)))
+        check(@ccall $(fn(:dojo_rollout_mlp_gradients))(bm.handle::Ptr{Cvoid}, z0::Ptr{T}, pol::Ptr{DojoMlpPolicy}, Int32(H)::Int32, G::Ptr{T},
+                                                        Int32(cot_space === :state ? 1 : 0)::Int32, p(G_u)::Ptr{Cvoid}, p(G_obs)::Ptr{Cvoid}, Z::Ptr{T}, OBS::Ptr{T},
+                                                        U::Ptr{T}, status::Ptr{Int32}, gtheta::Ptr{T}, gU::Ptr{T}, gz::Ptr{T})::Cint)
+    end
+    return Z, OBS, U, status, gtheta, gU, gz
+end
+
 "which states the IFT data blocks are evaluated at: 0 = as the reference does after step! (post-update_state!), 1 = at the solved step (consistent)"
 set_gradient_mode!(bm::BatchedMechanism, mode::Integer) = check(@ccall $(fn(:dojo_set_gradient_mode))(bm.handle::Ptr{Cvoid}, Int32(mode)::Int32)::Cint)
 

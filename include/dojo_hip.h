@@ -400,8 +400,8 @@ int  dojo_rollout_gradients(DojoHandle h, const void* z0, const void* U, int32_t
  * Refused before anything is launched, text on the handle -- DOJO_ERR_INVALID: NULL handle, z0, policy or W; H < 1; nu = 0; na < 1, act_off < 0 or
  * act_off + na > nu; contact_init = 1 on a handle without a solution.  DOJO_ERR_UNSUPPORTED: a mechanism with a kinematic loop, contact_forces with
  * LinearContact (both as dojo_observe_dev); more than 2048 observations.
- * Not part of it: contact observations in reverse mode (below), non-affine policies, rewards / termination, running
- * normaliser statistics, control clamping, re-projection to minimal coordinates between the steps (DojoEnvironments' step! does that; simulate! does not). */
+ * Not part of it: contact observations in reverse mode (below), activations other than the tanh of the network policy (DojoMlpPolicy below), output
+ * squashing, rewards / termination, running normaliser statistics, control clamping, re-projection to minimal coordinates between the steps (DojoEnvironments' step! does that; simulate! does not). */
 typedef struct DojoPolicy {
     const void* W;        /* [Bw][na][nobs] row-major, handle dtype, device memory; required            */
     const void* bias;     /* [Bw][na] or NULL (zeros)                                                   */
@@ -491,6 +491,89 @@ int  dojo_rollout_policy_adjoint_dev(DojoHandle h, const DojoPolicy* policy, int
 int  dojo_rollout_policy_gradients(DojoHandle h, const void* z0, const DojoPolicy* policy, int32_t H, const void* G, int32_t cot_space,
                                    const void* G_u, const void* G_obs, void* Z, void* OBS, void* U_out, int32_t* status,
                                    void* gW, void* gbias, void* gU, void* gz);
+
+/* Closed-loop rollouts with a network policy, forward and reverse mode: dojo_rollout_policy_dev and dojo_rollout_policy_adjoint_dev with a small tanh
+ * MLP in place of the affine map -- first-order optimisation of a neural controller through the simulator in one call per direction.
+ * csrc/dojo_mlp.hpp has the kernels.  Per environment b and step k, L = n_layers (1 .. DOJO_MLP_MAX_LAYERS), widths n_0 = nobs, hidden
+ * n_1 .. n_{L-1}, n_L = na (the driven inputs: act_off .. act_off + na - 1), each >= 1:
+ *
+ *     o_k  = the observation of dojo_rollout_policy_dev (rounded once to the handle dtype -> OBS[k]; the policy consumes the ROUNDED value)
+ *     h_0  = (o_k - mean) .* scale                                    fp64
+ *     p_l  = b_l + W_l h_{l-1},   h_l = tanh(p_l)   l = 1 .. L-1      fp64;  h_1 .. h_{L-1} -> ACT[k][b]
+ *     a    = b_L + W_L h_{L-1}                                        (no activation on the output layer)
+ *     u    = U_ff[k][b];  u[act_off + i] += a_i                       rounded once -> U_out[k][b], read by step k
+ *
+ * theta: one flat vector of P = sum_l n_l (n_{l-1} + 1) entries in the handle dtype, layer after layer: W_l row-major [n_l][n_{l-1}], then b_l [n_l].
+ * per_env = 1: theta [B][P]; per_env = 0: theta [P], shared.  ACT is double [H][B][nh], nh = n_1 + .. + n_{L-1}: fp64 whatever the handle dtype (as M
+ * is); it is what the sweep reads, which therefore evaluates no tanh and repeats no forward pass.  With n_layers = 1, theta = [W | bias] and every
+ * output of every entry below is bit-identical to the affine entry fed (W, bias).  tanh is the device library's fp64 tanh.  Every dot product is
+ * summed in an order fixed by the widths alone; no atomics; results do not depend on the batch, the groups or per_env = 0 against theta given B times.
+ *
+ * dojo_rollout_mlp_dev (device pointers, the members of *policy included) mirrors dojo_rollout_policy_dev argument for argument, plus ACT; Z, OBS,
+ * U_out, ACT, status may each be NULL.  dojo_rollout_mlp: host pointers.  dojo_rollout_mlp_record_dev = dojo_rollout_mlp_dev plus the record of
+ * dojo_rollout_record_dev; Z, OBS, U_out, DZ, DU are required, and ACT with n_layers > 1.
+ *
+ * dojo_rollout_mlp_adjoint_dev: with the notation of dojo_rollout_policy_adjoint_dev (lambda, g_k, GU_k, GO_k, M_k, failed steps by select),
+ *     gu = DU_k^T lambda + GU_k -> gU[k];   delta_L = gu[act_off .. act_off + na - 1]
+ *     for l = L .. 1:   g b_l += delta_l;   g W_l += delta_l h_{l-1}^T;   delta_{l-1} = (W_l^T delta_l) .* (1 - h_{l-1}^2)   (no factor for l = 1)
+ *     go = scale .* delta_0 + GO_k;   lambda = DZ_k^T lambda + M_k^T go (+ g_{k-1} if k > 0)
+ * with h_0 formed from the recorded OBS[k] and h_l from the recorded ACT[k].  gtheta has the layout of theta: [B][P] (per_env = 1) or [P], the sum
+ * over the batch (per_env = 0; a second small kernel, order fixed by B alone).  The P accumulators of an environment live in an fp64 workspace of
+ * the handle ([B][P], grown on demand), each owned by one lane for the whole launch; fp64 throughout, outputs rounded once.  That workspace (like M's
+ * and the affine sweep's) is ONE PER HANDLE and is read and written at every step of the sweep: sweeps on one handle must be ordered -- enqueue them on
+ * one stream, or make the later one wait for the earlier; concurrent sweeps need a handle each.  mean and scale are
+ * frozen; U_ff is not read.  dojo_rollout_mlp_gradients (host pointers): upload, record, sweep, download; the record, M and ACT
+ * never cross PCIe, and the free-memory check of dojo_rollout_policy_gradients covers ACT and the workspace as well.
+ *
+ * Refused before anything is launched, text on the handle that names the entry point -- DOJO_ERR_INVALID: what the affine counterpart refuses (theta
+ * in the place of W); n_layers outside 1 .. DOJO_MLP_MAX_LAYERS; a width < 1; width[0] != nobs; act_off + width[n_layers] > nu (na IS
+ * width[n_layers]); n_layers > 1 with ACT = NULL in the record and adjoint entries.  DOJO_ERR_UNSUPPORTED: contact_forces = 1 in the adjoint and
+ * gradients entries (the reason given above); a policy of 2^31 parameters or more; a policy whose LDS need exceeds 64 KB in either kernel --
+ *     forward:  4 (nobs + nh) doubles                              (four environments per workgroup: h_0 and the activations)
+ *     sweep:    4 nx + nu + 2 nobs + 2 wmax + nh doubles,  wmax = the largest width     (Ant, [28, 64, 64, 8]: 5 KB and 7.4 KB)
+ * Not part of it: other activations, output squashing or clamping, gradients w.r.t. mean and scale, contact observations in reverse mode. */
+#define DOJO_MLP_MAX_LAYERS 4
+typedef struct DojoMlpPolicy {
+    const void* theta;    /* [Bw][P], handle dtype; required                                            */
+    const void* mean;     /* [nobs] or NULL (zeros): shared by all environments                         */
+    const void* scale;    /* [nobs] or NULL (ones)                                                      */
+    const void* U_ff;     /* [H][B][nu] or NULL (zeros)                                                 */
+    int32_t per_env;      /* 1: Bw = B (one policy per environment); 0: Bw = 1 (shared)                 */
+    int32_t act_off;      /* the policy drives inputs act_off .. act_off + width[n_layers] - 1          */
+    int32_t n_layers;     /* L: 1 .. DOJO_MLP_MAX_LAYERS (1: the affine policy)                         */
+    int32_t width[DOJO_MLP_MAX_LAYERS + 1];   /* n_0 = nobs, n_1 .. n_{L-1}, n_L = na; entries past L are not read */
+    int32_t contact_forces;/* nobs = 2 nu + (contact_forces ? Nc : 0), as dojo_observe_dev              */
+    int32_t contact_init; /* as DojoPolicy                                                              */
+    int32_t reserved;
+} DojoMlpPolicy;
+typedef struct DojoMlpAdjoint {
+    const void* DZ;         /* [H][B][nx][nx] as recorded; required, 16-byte aligned                       */
+    const void* DU;         /* [H][B][nu][nx] as recorded; required, 16-byte aligned                       */
+    const void* OBS;        /* [H+1][B][nobs] as recorded; required                                        */
+    const double* ACT;      /* [H][B][nh] as recorded; required with n_layers > 1                          */
+    const int32_t* status;  /* [H][B] or NULL (every step solved)                                          */
+    const void* z0;         /* [B][13Nb]; needed when M is NULL                                            */
+    const void* Z;          /* [H][B][13Nb]; needed when M is NULL, or cot_space = 1                       */
+    const double* M;        /* [H+1][B][2nu][24] compact observation Jacobians, or NULL (computed)         */
+    const void* G;          /* [H][B][nx] (cot_space 0) or [H][B][13Nb] (cot_space 1); required            */
+    const void* G_u;        /* [H][B][nu] cotangent of U_out, or NULL                                      */
+    const void* G_obs;      /* [H+1][B][nobs] cotangent of OBS, or NULL                                    */
+    void* gtheta;           /* out: [Bw][P], or NULL                                                       */
+    void* gU;               /* out: [H][B][nu] gradient w.r.t. U_ff, or NULL                               */
+    void* gz;               /* out: [B][nx] gradient w.r.t. z0 in tangent coordinates, or NULL             */
+    int32_t cot_space;      /* 0: G in tangent coordinates; 1: in state coordinates                        */
+    int32_t reserved;
+} DojoMlpAdjoint;
+int  dojo_rollout_mlp_dev(DojoHandle h, const void* z0, const DojoMlpPolicy* policy, int32_t H,
+                          void* Z, void* OBS, void* U_out, double* ACT, int32_t* status, void* stream);
+int  dojo_rollout_mlp(DojoHandle h, const void* z0, const DojoMlpPolicy* policy, int32_t H,
+                      void* Z, void* OBS, void* U_out, int32_t* status);
+int  dojo_rollout_mlp_record_dev(DojoHandle h, const void* z0, const DojoMlpPolicy* policy, int32_t H,
+                                 void* Z, void* OBS, void* U_out, double* ACT, int32_t* status, void* DZ, void* DU, void* stream);
+int  dojo_rollout_mlp_adjoint_dev(DojoHandle h, const DojoMlpPolicy* policy, int32_t H, const DojoMlpAdjoint* a, void* stream);
+int  dojo_rollout_mlp_gradients(DojoHandle h, const void* z0, const DojoMlpPolicy* policy, int32_t H, const void* G, int32_t cot_space,
+                                const void* G_u, const void* G_obs, void* Z, void* OBS, void* U_out, int32_t* status,
+                                void* gtheta, void* gU, void* gz);
 
 /* get_state(environment) of DojoEnvironments (environments.jl:100-102; quadruped_sampling.jl:67-72): the minimal state
  * of the mechanism, and with contact_forces != 0 the normal impulse of every contact of the last step clamped to
