@@ -13,6 +13,7 @@
 #include "dojo_policy.hpp"
 #include "dojo_policy_adjoint.hpp"
 #include "dojo_mlp.hpp"
+#include "dojo_data_adjoint.hpp"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -140,6 +141,7 @@ struct DojoSim {
     void* d_pM = nullptr; size_t pM_bytes = 0;             // [H+1][B][2nu][24] fp64: the observation Jacobians of a closed-loop sweep whose caller passes none (grown on demand)
     double* d_pacc = nullptr;                              // [B][na (nobs + 1)] fp64: per-environment gW / gbias of a shared policy, in front of the reduction
     size_t pacc_bytes = 0;
+    double* d_dacc = nullptr; size_t dacc_bytes = 0;       // [B][5Nc] fp64: per-environment contact-data gradients in front of the reduction (dojo_data_adjoint.hpp)
     double* d_macc = nullptr; size_t macc_bytes = 0;       // [B][P] fp64: the accumulators of the MLP sweep between its steps, and in front of the reduction (dojo_mlp.hpp)
     // iteration cap + continuation kernel (dojo_set_iteration_cap; dojo_device.hpp Globals::iter_cap)
     int iter_cap = -1;                  // < 0: automatic (DOJO_DEFAULT_ITERATION_CAP where the continuation kernel exists), 0: off, > 0: as given
@@ -1004,6 +1006,22 @@ int ensure_at_least(DojoSim* s, void** p, size_t* have, size_t bytes) {
     return DOJO_OK;
 }
 
+// dojo_rollout_data_adjoint_dev: the contact-data sweep (dojo_data_adjoint.hpp; one workgroup per environment, one launch) and, for the gradient shared by the
+// batch, the reduction over the environments (one workgroup per entry)
+template <class TIO>
+int launch_data_adjoint(const DojoSim* s, int H, const void* DZ, const void* DC, const void* G, int cot_space, const void* Z, const int* status, void* gtheta_env, double* acc,
+                        void* gtheta, void* gz, hipStream_t st) {
+    const int nx = 12 * s->M.Nb, nth = 5 * s->M.Nc;
+    const dj::dadjoint::Args<TIO> A{(const TIO*)DZ, (const TIO*)DC, (const TIO*)G, (const TIO*)Z, status, (TIO*)gtheta_env, acc, (TIO*)gz, H, s->B, nx, nth, cot_space};
+    hipLaunchKernelGGL((dj::dadjoint::rollout_data_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::dadjoint::THREADS), dj::dadjoint::lds_bytes(nx, nth), st, A);
+    HIPCHK(hipGetLastError());
+    if (acc) {
+        hipLaunchKernelGGL((dj::dadjoint::data_reduce_kernel<TIO>), dim3((unsigned)nth), dim3(dj::dadjoint::THREADS), 0, st, (const double*)acc, s->B, nth, (TIO*)gtheta);
+        HIPCHK(hipGetLastError());
+    }
+    return DOJO_OK;
+}
+
 int launch_policy_any(const DojoSim* s, const DojoPolicy& p, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
     return s->dtype == DOJO_DTYPE_F32 ? launch_policy<float>(s, p, z, csg, uff, obs, u, sp) : launch_policy<double>(s, p, z, csg, uff, obs, u, sp);
 }
@@ -1410,10 +1428,12 @@ int dojo_gradients(DojoHandle s, void* dz, void* du) {
 // simulate! with pre-sampled controls (src/simulation/simulate.jl:16-37): H steps, each fed with the previous step's
 // internal next state; storage != null records save_to_storage! rows [H][B][Nb][25] of every solved step
 // DZ / DU != null: the IFT Jacobians of every step as well, [H][B][nx][nx] / [H][B][nu][nx] in the device layout of dojo_step_dev (dojo_rollout_record_dev)
+// DC != null (dojo_rollout_data_record_dev; with DZ): the contact-data columns of every step as well, [H][B][5Nc][nx] -- the step launch of a group is followed directly, on the same
+// span and stream, by the contact-data IFT kernel of dojo_contact_gradients_dev, which reads the hand-off record that step just left for exactly those environments
 // pol != null (dojo_rollout_policy_dev, dojo_rollout_mlp_dev; checked by the caller; a Controller of either kind): U is the feed-forward term and the controls of step k are made on the group's stream, directly in front of
 // the step, by the policy kernel -- into U_out[k] (null: one [B][nu] buffer of the handle, a group's launches being serial); OBS [H+1][B][nobs] or null records what it saw
 static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* storage, void* stream, void* DZ = nullptr, void* DU = nullptr,
-                        const Controller* pol = nullptr, void* OBS = nullptr, void* U_out = nullptr) {
+                        const Controller* pol = nullptr, void* OBS = nullptr, void* U_out = nullptr, void* DC = nullptr) {
     if (!s || !z0 || H < 1) { g_err = "dojo_rollout_dev: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, nx = 12 * s->M.Nb;
@@ -1451,6 +1471,8 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
             void* dzk = DZ ? (char*)DZ + (size_t)k * B * nx * nx * w : nullptr;
             void* duk = (DU && nu) ? (char*)DU + (size_t)k * B * nx * nu * w : nullptr;
             TRY(launch_any(s, StepIO{cur, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, dzk, duk, nullptr, sk}, sp, m));
+            // (the same Mode: the same hand-off record, no timing slot -- m.slot is null --, and a launch with io.dc never reorders the dispatch)
+            if (DC && s->M.Nc > 0) TRY(launch_any(s, StepIO{cur, uk, nxt, nullptr, nullptr, nullptr, nullptr, (char*)DC + (size_t)k * B * nx * 5 * s->M.Nc * w, nullptr}, sp, m));
             cur = nxt;
         }
         if (pol && OBS) TRY(launch_controller(s, *pol, H, cur, s->d_csg, nullptr, (char*)OBS + (size_t)H * B * nobs * w, nullptr, sp));      // the observation of the final state
@@ -1614,6 +1636,93 @@ int dojo_rollout_gradients(DojoHandle s, const void* z0, const void* U, int32_t 
     HIPCHK(hipDeviceSynchronize());
     if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
     if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
+    if (gU && nu) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
+    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
+    return DOJO_OK;
+}
+
+// ---- contact-data gradients through rollouts (dojo_data_adjoint.hpp): get_contact_gradients (src/gradients/contact.jl:1-55) per step, chained as in
+// examples/system_identification/utilities.jl:42-90, in reverse mode on the device ----
+// dojo_rollout_record_dev plus the contact-data columns of every step, DC [H][B][5Nc][nx] in the layout of dojo_contact_gradients_dev
+int dojo_rollout_data_record_dev(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* DZ, void* DU, void* DC, void* stream) {
+    if (!DC) return dojo_rollout_record_dev(s, z0, U, H, Z, status, DZ, DU, stream);
+    Enter enter_(s);
+    const char* who = "dojo_rollout_data_record_dev";
+    if (!s || !z0 || H < 1 || !Z || !DZ || (!DU && s->M.nu > 0)) { g_err = std::string(who) + ": bad argument (z0, Z, DZ and -- with nu > 0 -- DU are required, H >= 1)"; return DOJO_ERR_INVALID; }
+    {   // body-body contacts, Impact / Linear contacts, more than 64 contacts, the lane mapping: refused before anything is allocated or launched
+        const int rc = refuse_unsupported(s, true, s->M.Nc > 0);
+        if (rc != DOJO_OK) { g_err = std::string(who) + ": " + g_err.c_str(); return rc; }
+    }
+    return rollout_core(s, z0, U, H, Z, status, nullptr, stream, DZ, DU, nullptr, nullptr, nullptr, DC);
+}
+
+int dojo_rollout_data_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void* DC, const void* G, int32_t cot_space, const void* Z, const int32_t* status,
+                                  void* gtheta_env, void* gtheta, void* gz, void* stream) {
+    Enter enter_(s);
+    const std::string who = "dojo_rollout_data_adjoint_dev";
+    if (!s) { g_err = who + ": bad argument"; return DOJO_ERR_INVALID; }
+    const int Nc = s->M.Nc;
+    if (H < 1) { g_err = who + ": H must be >= 1"; return DOJO_ERR_INVALID; }
+    if (!DZ || !G) { g_err = who + ": DZ and G must not be NULL"; return DOJO_ERR_INVALID; }
+    if (!DC && Nc > 0) { g_err = who + ": DC must not be NULL (a mechanism without contacts has none)"; return DOJO_ERR_INVALID; }
+    if (cot_space != 0 && cot_space != 1) { g_err = who + ": cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
+    if (cot_space == 1 && !Z) { g_err = who + ": cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
+    if (!gtheta_env && !gtheta && !gz) { g_err = who + ": gtheta_env, gtheta and gz are all NULL"; return DOJO_ERR_INVALID; }
+    if ((((uintptr_t)DZ) | (Nc > 0 ? (uintptr_t)DC : (uintptr_t)0)) & 15) { g_err = who + ": DZ and DC must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
+    if (dj::dadjoint::lds_bytes(12 * s->M.Nb, 5 * Nc) > 65536) { g_err = who + ": lambda, g and the 5 Nc accumulators (4 nx + 5 Nc doubles) do not fit into 64 KB of LDS"; return DOJO_ERR_UNSUPPORTED; }
+    if (Nc == 0) { gtheta_env = nullptr; gtheta = nullptr; }      // no contact data: gz alone, the gtheta outputs are not touched
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the Jacobians)
+    if (!gtheta_env && !gtheta && !gz) return DOJO_OK;
+    if (gtheta) TRY(ensure_at_least(s, (void**)&s->d_dacc, &s->dacc_bytes, (size_t)s->B * 5 * Nc * sizeof(double)));
+    double* acc = gtheta ? s->d_dacc : nullptr;
+    return s->dtype == DOJO_DTYPE_F32 ? launch_data_adjoint<float>(s, H, DZ, DC, G, cot_space, Z, status, gtheta_env, acc, gtheta, gz, st)
+                                      : launch_data_adjoint<double>(s, H, DZ, DC, G, cot_space, Z, status, gtheta_env, acc, gtheta, gz, st);
+}
+
+// host pointers: upload, record on the device (with the contact-data columns), the contact-data sweep -- and the open-loop sweep over the same record when gU is
+// wanted --, download.  The Jacobians never cross PCIe.
+int dojo_rollout_data_gradients(DojoHandle s, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space, void* Z, int32_t* status,
+                                void* gtheta, void* gtheta_env, void* gU, void* gz) {
+    Enter enter_(s);
+    const std::string who = "dojo_rollout_data_gradients";
+    if (!s || !z0 || !G || H < 1 || (cot_space != 0 && cot_space != 1)) { g_err = who + ": bad argument"; return DOJO_ERR_INVALID; }
+    {
+        const int rc = refuse_unsupported(s, true, s->M.Nc > 0);
+        if (rc != DOJO_OK) { g_err = who + ": " + g_err.c_str(); return rc; }
+    }
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, nth = 5 * (size_t)s->M.Nc, HB = (size_t)H * B, ng = cot_space ? nz : nx;
+    const size_t record = HB * nx * (nx + nu + nth) * w;
+    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
+    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + up(HB * nx * nth * w) + up(HB * nu * w)
+                  + up(B * nx * w) + up(B * nth * w) + up(nth * w) + up(B * nth * sizeof(double)) + ((U && nu) ? up(HB * nu * w) : 0);
+    need += record_workspaces(s);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b) {
+        g_err = who + ": the record of " + std::to_string(record) + " bytes (H B nx (nx + nu + 5 Nc) scalars; " + std::to_string(need) + " bytes with the other buffers of the call) does not fit into the "
+                + std::to_string(free_b) + " bytes of free device memory";
+        return DOJO_ERR_INVALID;
+    }
+    DevBuf dz0, dU, dG, dZ, dS, dDZ, dDU, dDC, dgU, dgz, dgt, dgte;
+    HIPCHK(dz0.alloc(B * nz * w)); HIPCHK(dG.alloc(HB * ng * w)); HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
+    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w)); HIPCHK(dDC.alloc(HB * nx * nth * w));
+    HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w)); HIPCHK(dgt.alloc(nth * w)); HIPCHK(dgte.alloc(B * nth * w));
+    HIPCHK(hipMemcpy(dz0.p, z0, B * nz * w, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dG.p, G, HB * ng * w, hipMemcpyHostToDevice));
+    if (U && nu) { HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(hipMemcpy(dU.p, U, HB * nu * w, hipMemcpyHostToDevice)); }
+    TRY(rollout_core(s, dz0.p, dU.p, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, nullptr, nullptr, nullptr, dDC.p));
+    TRY(dojo_rollout_data_adjoint_dev(s, H, dDZ.p, dDC.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, (gtheta_env && nth) ? dgte.p : nullptr, (gtheta && nth) ? dgt.p : nullptr, dgz.p, nullptr));
+    if (gU && nu) TRY(dojo_rollout_adjoint_dev(s, H, dDZ.p, dDU.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, dgU.p, nullptr, nullptr));
+    HIPCHK(hipDeviceSynchronize());
+    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
+    if (gtheta && nth) HIPCHK(hipMemcpy(gtheta, dgt.p, nth * w, hipMemcpyDeviceToHost));
+    if (gtheta_env && nth) HIPCHK(hipMemcpy(gtheta_env, dgte.p, B * nth * w, hipMemcpyDeviceToHost));
     if (gU && nu) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
     if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
@@ -2033,6 +2142,47 @@ int dojo_contact_gradients(DojoHandle s, void* dc) {
     HIPCHK(hipMemcpy(tmp.data(), d_dc.p, tmp.size(), hipMemcpyDeviceToHost));
     for (size_t b = 0; b < B; ++b) for (size_t c = 0; c < ncc; ++c) for (size_t r = 0; r < nx; ++r)
         std::memcpy((char*)dc + ((b * nx + r) * ncc + c) * w, tmp.data() + ((b * ncc + c) * nx + r) * w, w);
+    return DOJO_OK;
+}
+
+// set_data!(mechanism.contacts, theta) (examples/system_identification/utilities.jl:52) on a live handle: theta [Nc][5] =
+// [friction_coefficient, contact_radius, contact_origin(3)] per contact.  The contact table is the only place these values live (the cut element of a
+// body-body contact holds the contact's index, make_globals reads none of them), so the handle then steps as one created with theta.
+int dojo_set_contact_data(DojoHandle s, const double* theta) {
+    Enter enter_(s);
+    if (!s) { g_err = "dojo_set_contact_data: bad argument"; return DOJO_ERR_INVALID; }
+    const int Nc = s->M.Nc;
+    if (Nc == 0) return DOJO_OK;
+    if (!theta) { g_err = "dojo_set_contact_data: theta must not be NULL"; return DOJO_ERR_INVALID; }
+    for (int c = 0; c < Nc; ++c) {
+        const double* t = theta + 5 * (size_t)c;
+        for (int i = 0; i < 5; ++i) if (!std::isfinite(t[i])) { g_err = "dojo_set_contact_data: contact " + std::to_string(c) + " has a non-finite value"; return DOJO_ERR_INVALID; }
+        if (t[0] < 0.0 || t[1] < 0.0) { g_err = "dojo_set_contact_data: contact " + std::to_string(c) + " has a negative friction coefficient or radius"; return DOJO_ERR_INVALID; }
+        if (s->M.contact_model == 1 && t[0] != 0.0) {
+            g_err = "dojo_set_contact_data: an ImpactContact has no friction coefficient (contact " + std::to_string(c) + ": pass 0)"; return DOJO_ERR_UNSUPPORTED;
+        }
+    }
+    HIPCHK(hipSetDevice(s->device));
+    TRY(join_groups(s, nullptr));
+    HIPCHK(hipDeviceSynchronize());                          // steps still in flight read the previous table
+    for (int c = 0; c < Nc; ++c) {
+        dj::ContactP<double>& Q = s->M.contacts[c]; const double* t = theta + 5 * (size_t)c;
+        Q.mu = t[0]; Q.r = t[1]; for (int i = 0; i < 3; ++i) Q.o[i] = t[2 + i];
+    }
+    std::vector<dj::ContactP<double>> contacts; for (auto& c : s->M.contacts) contacts.push_back(dj::cast_contact<double>(c));     // the contacts part of upload_tables
+    HIPCHK(hipMemcpy(s->d_contacts, contacts.data(), contacts.size() * sizeof(dj::ContactP<double>), hipMemcpyHostToDevice));
+    s->have_grad = false;                                    // the hand-off record holds a solution obtained with the old theta
+    return DOJO_OK;
+}
+int dojo_get_contact_data(DojoHandle s, double* theta) {
+    Enter enter_(s);
+    if (!s) { g_err = "dojo_get_contact_data: bad argument"; return DOJO_ERR_INVALID; }
+    if (s->M.Nc == 0) return DOJO_OK;
+    if (!theta) { g_err = "dojo_get_contact_data: theta must not be NULL"; return DOJO_ERR_INVALID; }
+    for (int c = 0; c < s->M.Nc; ++c) {
+        const dj::ContactP<double>& Q = s->M.contacts[c]; double* t = theta + 5 * (size_t)c;
+        t[0] = Q.mu; t[1] = Q.r; for (int i = 0; i < 3; ++i) t[2 + i] = Q.o[i];
+    }
     return DOJO_OK;
 }
 

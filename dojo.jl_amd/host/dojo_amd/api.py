@@ -44,7 +44,8 @@ def lib():
                   "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients", "dojo_rollout_policy_dev", "dojo_rollout_policy",
                   "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
                   "dojo_rollout_policy_gradients",
-                  "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients"):
+                  "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
+                  "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients"):
             getattr(L, f).restype = C.c_int
         L.dojo_destroy.restype = None
         _lib = L
@@ -63,7 +64,8 @@ EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error",
                     "dojo_rollout_policy_dev", "dojo_rollout_policy",
                     "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
                     "dojo_rollout_policy_gradients",
-                    "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients"]
+                    "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
+                    "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients"]
 
 
 class DojoPolicy(C.Structure):
@@ -339,6 +341,46 @@ class BatchedMechanism:
         gU = np.zeros((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
         _chk(lib().dojo_rollout_gradients(self.h, _p(z0), _p(U), H, _p(G), cs, _p(Z), _p(st), _p(gU) if s.nu else None, _p(gz)))
         return Z, st, gU, gz
+
+    def set_contact_data(self, theta):
+        """set_data!(mechanism.contacts, theta) on the live handle (dojo_set_contact_data): theta [Nc, 5] = [friction_coefficient, contact_radius,
+        contact_origin(3)] per contact, shared by all environments.  The handle then steps as one created with theta; `contact_gradients` needs a new
+        differentiable step first."""
+        Nc = len(self.spec.contacts)
+        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(Nc, 5))
+        _chk(lib().dojo_set_contact_data(self.h, _p(th) if Nc else None))
+
+    def contact_data(self):
+        """the handle's contact data [Nc, 5] (dojo_get_contact_data)"""
+        th = np.zeros((len(self.spec.contacts), 5), np.float64)
+        _chk(lib().dojo_get_contact_data(self.h, _p(th) if len(th) else None))
+        return th
+
+    def rollout_data_gradients(self, z0, U=None, G=None, steps=None, cot_space="tangent", per_env=False):
+        """Reverse-mode rollout w.r.t. the contact data (dojo_rollout_data_gradients): the rollout of `rollout`, and the gradient of a trajectory loss
+        w.r.t. theta = `contact_data()`, the controls and the initial state, from the recorded IFT Jacobians of every step (state, control and
+        contact-data columns), which stay on the device.  G and cot_space as in `rollout_gradients`.  Returns (Z [H,B,13Nb], status [H,B],
+        gtheta [Nc,5] summed over the batch, gtheta_env [B,Nc,5] (per_env=True, else None), gU [H,B,nu], gz0 [B,nx] tangent)."""
+        B, s = self.batch, self.spec
+        Nc = len(s.contacts)
+        z0 = self._arr(z0, (B, s.nz))
+        if cot_space not in ("tangent", "state", 0, 1):
+            raise ValueError("cot_space must be 'tangent' or 'state'")
+        cs = 1 if cot_space in ("state", 1) else 0
+        if G is None:
+            raise ValueError("rollout_data_gradients needs the cotangents G of the loss w.r.t. the state after every step")
+        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
+        if G.shape != (H, B, s.nz if cs else s.nx):
+            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
+        if steps is not None and int(steps) != H:
+            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
+        U = self._arr(U, (H, B, s.nu)) if (U is not None and s.nu) else None
+        Z = np.empty((H, B, s.nz), self.np_dtype); st = np.empty((H, B), np.int32)
+        gth = np.zeros((Nc, 5), self.np_dtype); gte = np.zeros((B, Nc, 5), self.np_dtype) if per_env else None
+        gU = np.zeros((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
+        _chk(lib().dojo_rollout_data_gradients(self.h, _p(z0), _p(U), H, _p(G), cs, _p(Z), _p(st), _p(gth) if Nc else None,
+                                               _p(gte) if (per_env and Nc) else None, _p(gU) if s.nu else None, _p(gz)))
+        return Z, st, gth, gte, gU, gz
 
     def rollout_policy(self, z0, W, steps, bias=None, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):
         """Closed-loop rollout (dojo_rollout_policy): simulate! with the affine feedback policy u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale))

@@ -11,6 +11,9 @@ Jacobians and the reverse sweep are the library's kernels, include/dojo_hip.h "R
     Z, OBS, U = differentiable_mlp_rollout(mech, z0, theta, widths, U_ff=Uff)      # closed loop through the network
     loss(Z, OBS, U).backward()                       # reaches the modules' parameters through the cat
 
+    Z = differentiable_data_rollout(mech, z0, U, theta)      # theta [Nc,5] fp64: the contact data (system identification)
+    loss(Z).backward()                               # theta.grad [Nc,5], U.grad, z0.grad
+
 Everything is enqueued on torch's current stream and nothing synchronizes.  The gradient is the chain of the handle's gradient mode:
 set `mech.set_gradient_mode(api.GRAD_CONSISTENT)` for the derivative of the rollout.
 """
@@ -87,6 +90,71 @@ def differentiable_rollout(mech, z0, U=None, steps=None):
     the unit sphere of quaternions (its component along q0, which no rollout can see, is zero); x, v, omega are plain.  Nothing flows through a
     failed step.  Z.status [H,B] (int32, non-differentiable) is the solver status of every step."""
     Z, status = _Rollout.apply(mech, z0, U, steps)
+    Z.status = status
+    return Z
+
+
+class _DataRollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mech, z0, U, theta, steps):
+        s, B = mech.spec, mech.batch
+        Nc = len(s.contacts)
+        dt = torch.float32 if mech.dtype_code == 1 else torch.float64
+        if not z0.is_cuda or z0.dtype != dt or tuple(z0.shape) != (B, s.nz):
+            raise ValueError("z0 must be a %s device tensor of shape %s" % (dt, (B, s.nz)))
+        if theta is None or theta.dtype != torch.float64 or tuple(theta.shape) != (Nc, 5):
+            raise ValueError("theta must be a float64 tensor of shape %s" % ((Nc, 5),))
+        if U is not None and s.nu:
+            if not U.is_cuda or U.dtype != dt or U.dim() != 3 or tuple(U.shape[1:]) != (B, s.nu):
+                raise ValueError("U must be a %s device tensor of shape (H, %d, %d)" % (dt, B, s.nu))
+            H = int(U.shape[0]); Uc = U.contiguous()
+        else:
+            H = int(steps); Uc = None
+        mech.set_contact_data(theta.detach().cpu().numpy())      # (waits for the handle's work in flight: the table is mechanism data)
+        dev = z0.device; z0c = z0.contiguous()
+        Z = torch.empty((H, B, s.nz), dtype=dt, device=dev)
+        status = torch.empty((H, B), dtype=torch.int32, device=dev)
+        DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)          # the record: freed with the graph
+        DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev) if s.nu else None
+        DC = torch.empty((H, B, 5 * Nc, s.nx), dtype=dt, device=dev) if Nc else None
+        api._chk(api.lib().dojo_rollout_data_record_dev(mech.h, _ptr(z0c), _ptr(Uc), H, _ptr(Z), _ptr(status), _ptr(DZ), _ptr(DU), _ptr(DC), _stream(dev)))
+        ctx.mech, ctx.H, ctx.has_u, ctx.theta_device, ctx.layout = mech, H, U is not None, theta.device, (DU is not None, DC is not None)
+        ctx.save_for_backward(z0c, Z, status, DZ, *[t for t in (DU, DC) if t is not None])
+        ctx.mark_non_differentiable(status)
+        return Z, status
+
+    @staticmethod
+    def backward(ctx, gZ, _gstatus):
+        mech, H = ctx.mech, ctx.H
+        s, B = mech.spec, mech.batch
+        Nc = len(s.contacts)
+        z0, Z, status, DZ = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        DU = rest.pop(0) if ctx.layout[0] else None
+        DC = rest.pop(0) if ctx.layout[1] else None
+        gZ = gZ.contiguous()
+        need = ctx.needs_input_grad                    # (mech, z0, U, theta, steps)
+        want_u = ctx.has_u and s.nu > 0 and need[2]
+        gU = torch.empty((H, B, s.nu), dtype=Z.dtype, device=Z.device) if want_u else None
+        gz = torch.empty((B, s.nx), dtype=Z.dtype, device=Z.device) if need[1] else None
+        gth = torch.empty((Nc, 5), dtype=Z.dtype, device=Z.device) if (need[3] and Nc) else None
+        if gth is not None or gz is not None:
+            api._chk(api.lib().dojo_rollout_data_adjoint_dev(mech.h, H, _ptr(DZ), _ptr(DC), _ptr(gZ), 1, _ptr(Z), _ptr(status), None, _ptr(gth), _ptr(gz), _stream(Z.device)))
+        if gU is not None:
+            api._chk(api.lib().dojo_rollout_adjoint_dev(mech.h, H, _ptr(DZ), _ptr(DU), _ptr(gZ), 1, _ptr(Z), _ptr(status), _ptr(gU), None, _stream(Z.device)))
+        if need[3] and gth is None:
+            gth = torch.zeros((0, 5), dtype=Z.dtype, device=Z.device)
+        return None, (lift_tangent(gz, z0) if gz is not None else None), gU, (gth.double().to(ctx.theta_device) if need[3] else None), None
+
+
+def differentiable_data_rollout(mech, z0, U, theta, steps=None):
+    """-> Z [H,B,13Nb], the states after every step of the rollout from z0 under the controls U [H,B,nu] (None with `steps`) with the contact data
+    theta [Nc,5] = [friction_coefficient, contact_radius, contact_origin(3)] per contact (fp64, CPU or device; shared by the batch), as a node of
+    torch's graph.  Forward: `mech.set_contact_data(theta)`, then dojo_rollout_data_record_dev into torch-owned tensors (the Jacobians of every step,
+    H B nx (nx + nu + 5 Nc) scalars, live as long as the graph).  Backward: dojo_rollout_data_adjoint_dev for theta (summed over the batch) and z0,
+    dojo_rollout_adjoint_dev over the same record for U.  z0's gradient is lifted to state shape as in differentiable_rollout; nothing flows
+    through a failed step.  Z.status [H,B] (int32, non-differentiable) is the solver status of every step."""
+    Z, status = _DataRollout.apply(mech, z0, U, theta, steps)
     Z.status = status
     return Z
 

@@ -182,6 +182,32 @@ function rollout_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, U::Array{T,3}
     return Z, status, gU, gz
 end
 
+"""
+set_data!(mechanism.contacts, θ) on the live handle (examples/system_identification/utilities.jl:52): θ[5, Nc] =
+[friction_coefficient; contact_radius; contact_origin(3)] per contact, shared by all environments.  The handle then steps as one created with θ.
+"""
+function set_contact_data!(bm::BatchedMechanism, θ::Matrix{Float64})
+    check(@ccall $(fn(:dojo_set_contact_data))(bm.handle::Ptr{Cvoid}, θ::Ptr{Float64})::Cint)
+    return bm
+end
+
+"""
+reverse-mode rollout w.r.t. the contact data: get_contact_gradients (src/gradients/contact.jl:1-55) of every step chained as in
+examples/system_identification/utilities.jl:42-90, transposed, on the device.  G as in `rollout_gradients`.
+-> Z[nz, B, H], status[B, H], gθ[5, Nc] (summed over the batch), gθ_env[5, Nc, B], gU[nu, B, H], gz0[nx, B] (tangent coordinates).
+"""
+function rollout_data_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, U::Array{T,3}, G::Array{T,3}; cot_space::Symbol=:tangent, opts=Dojo.SolverOptions{Float64}()) where T
+    set_options!(bm, opts)
+    H = size(G, 3); Nc = length(bm.mechanism.contacts)
+    Z = Array{T}(undef, bm.nz, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    gθ = zeros(T, 5, Nc); gθ_env = zeros(T, 5, Nc, bm.batch)
+    gU = zeros(T, bm.nu, bm.batch, H); gz = Matrix{T}(undef, bm.nx, bm.batch)
+    check(@ccall $(fn(:dojo_rollout_data_gradients))(bm.handle::Ptr{Cvoid}, z0::Ptr{T}, (bm.nu > 0 ? pointer(U) : C_NULL)::Ptr{T}, H::Int32, G::Ptr{T},
+                                                     Int32(cot_space === :state ? 1 : 0)::Int32, Z::Ptr{T}, status::Ptr{Int32},
+                                                     (Nc > 0 ? pointer(gθ) : C_NULL)::Ptr{T}, (Nc > 0 ? pointer(gθ_env) : C_NULL)::Ptr{T}, gU::Ptr{T}, gz::Ptr{T})::Cint)
+    return Z, status, gθ, gθ_env, gU, gz
+end
+
 "mirror of `DojoPolicy` (include/dojo_hip.h): five pointers, six Int32"
 struct DojoPolicy
     W::Ptr{Cvoid}; bias::Ptr{Cvoid}; mean::Ptr{Cvoid}; scale::Ptr{Cvoid}; U_ff::Ptr{Cvoid}

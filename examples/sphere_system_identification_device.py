@@ -15,6 +15,14 @@ Here: the ten trajectories are ONE batch (B = 10); `dojo_step_dev` + `dojo_gradi
 cost evaluation builds a handle for its θ (set_data!(mechanism.contacts, θ), utilities.jl:52).  The data were generated with θ* = [0.2, 0.5].
 
     python examples/sphere_system_identification_device.py          # needs a GPU: libdojo_hip has no CPU fallback
+
+`--rollout`: the same dataset and cost in reverse mode on ONE handle.  A cost evaluation is one three-step rollout of the batch that records the
+Jacobians of every step on the device (∂z'/∂z, ∂z'/∂θ), its gradient one sweep over them (`dojo_amd.autograd.differentiable_data_rollout`:
+dojo_rollout_data_record_dev + dojo_rollout_data_adjoint_dev); θ changes between evaluations through `set_contact_data`, no handle is rebuilt and
+no Jacobian is downloaded.  The optimiser is torch.optim.LBFGS.  (The reference's Gauss-Newton Hessian JᵀQJ needs the forward-mode sensitivities
+∂z/∂θ themselves, which a reverse sweep does not produce: that path stays the default one above.)
+
+    python examples/sphere_system_identification_device.py --rollout
 """
 import os
 import sys
@@ -104,8 +112,56 @@ def quasi_newton_solve(f, fgH, x0, iters=20, gtol=1e-8, ftol=1e-6, lower=(0.0, 0
     return x
 
 
+def rollout_solve(Z, guess=(0.0, 1.0), lower=(0.0, 0.05), upper=(0.8, 1.0), grad_mode=0, opts=None, verbose=True):
+    """the cost of `loss` through differentiable_data_rollout on one handle, minimised over θ[:2] by torch.optim.LBFGS inside the example's box (the
+    box enters as a clamp plus a quadratic penalty on what the clamp cut off, so that an iterate outside is pushed back) -> (θ[:2], cost)"""
+    import torch
+    from dojo_amd.autograd import differentiable_data_rollout
+    B, H = len(Z), len(TIMESTEPS)
+    gm = api.BatchedMechanism(sphere(np.array([0.2, 0.5])), B, dtype="f64", opts=opts)
+    gm.set_gradient_mode(grad_mode)
+    z0 = torch.from_numpy(Z[:, TIMESTEPS[0] - 1].copy()).cuda()
+    Zt = torch.from_numpy(np.ascontiguousarray(Z[:, list(TIMESTEPS)].transpose(1, 0, 2))).cuda()       # [H, B, 13]
+    Qd = torch.from_numpy(np.diag(Q).copy()).cuda()
+    lo, hi = torch.tensor(lower, dtype=torch.float64), torch.tensor(upper, dtype=torch.float64)
+    p = torch.tensor(guess, dtype=torch.float64, requires_grad=True)
+    evals = [0]
+
+    def cost(p):
+        pc = torch.minimum(torch.maximum(p, lo), hi)
+        theta = torch.cat([pc, torch.zeros(3, dtype=torch.float64)]).reshape(1, 5)
+        Zp = differentiable_data_rollout(gm, z0, None, theta, steps=H)
+        assert (Zp.status == 0).all()
+        e = Zp - Zt
+        evals[0] += 1
+        return 0.5 * (e * e * Qd).sum().cpu() + 1e3 * ((p - pc) ** 2).sum()
+
+    # (lr = 0.05: the first trial step of a line search.  At the guess the gradient w.r.t. the radius is ~1e3, and a unit step lands beyond the minimum where
+    #  the sphere no longer touches the floor and the cost is flat in θ)
+    opt = torch.optim.LBFGS([p], lr=0.05, max_iter=300, history_size=10, tolerance_grad=1e-12, tolerance_change=1e-16, line_search_fn="strong_wolfe")
+
+    def closure():
+        opt.zero_grad()
+        f = cost(p)
+        f.backward()
+        if verbose:
+            print("eval %3d   f: %.6e   theta = [%.6f, %.6f]   |g| = %.2e" % (evals[0], f.item(), p[0].item(), p[1].item(), p.grad.abs().max().item()))
+        return f
+
+    opt.step(closure)
+    with torch.no_grad():
+        sol = torch.minimum(torch.maximum(p, lo), hi)
+        f = cost(sol).item()
+    gm.close()
+    return sol.numpy(), f
+
+
 def main():
     Z = dataset()
+    if "--rollout" in sys.argv[1:]:
+        sol, f = rollout_solve(Z)
+        print("solution (reverse mode, one handle): friction_coefficient %.6f (0.2), contact_radius %.6f (0.5), cost %.3e" % (sol[0], sol[1], f))
+        return
     f0 = lambda th: loss(np.concatenate([th, np.zeros(3)]), Z)
     fgH0 = lambda th: loss(np.concatenate([th, np.zeros(3)]), Z, derivatives=True)
     print("cost at the parameters the data were generated with, f([0.2, 0.5]) = %.3e" % f0(np.array([0.2, 0.5])))

@@ -25,6 +25,8 @@
  *   dojo_observe       <- get_state(environment)  DojoEnvironments/src/environments.jl:100-102,
  *                         environments/ant_ars.jl:72-80, environments/quadruped_sampling.jl:67-72
  *   dojo_contact_gradients <- get_contact_gradients(mechanism) src/gradients/contact.jl:1-55
+ *   dojo_rollout_data_gradients / dojo_set_contact_data <- get_contact_gradients src/gradients/contact.jl:1-55, chained as in
+ *                         examples/system_identification/utilities.jl:42-90 (set_data!(mechanism.contacts, theta), utilities.jl:52)
  *   dojo_minimal_to_maximal / dojo_maximal_to_minimal / dojo_step_minimal / dojo_minimal_gradients
  *                      <- minimal_to_maximal, maximal_to_minimal  src/mechanism/state.jl:9-66,
  *                         step_minimal_coordinates!               src/simulation/step.jl:42-60,
@@ -375,6 +377,57 @@ int  dojo_rollout_adjoint_dev(DojoHandle h, int32_t H, const void* DZ, const voi
                               const void* Z, const int32_t* status, void* gU, void* gz, void* stream);
 int  dojo_rollout_gradients(DojoHandle h, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space,
                             void* Z, int32_t* status, void* gU, void* gz);
+
+/* Contact-parameter gradients through rollouts (system identification): get_contact_gradients, src/gradients/contact.jl:1-55, chained as in
+ * examples/system_identification/utilities.jl:42-90 -- here in reverse mode, on the device (csrc/dojo_data_adjoint.hpp).
+ *
+ * theta is the contact data of get_contact_gradients: 5 values per contact, [friction_coefficient, contact_radius, contact_origin(3)], in
+ * mechanism.contacts order -- [Nc][5], n_theta = 5 Nc.  It is mechanism data, SHARED by all environments of a handle.  (One theta per
+ * environment would put the contact table on the batch axis of the step kernel: not supported.)
+ *
+ * dojo_set_contact_data: set_data!(mechanism.contacts, theta) on a live handle.  Joins the handle's environment groups, waits for the work
+ * in flight, replaces friction coefficient, radius and origin of every contact and uploads the contact table again; the handle then steps
+ * bit-identically to one created with theta.  The solution of an earlier differentiable step no longer belongs to the handle's data:
+ * dojo_contact_gradients fails until the next dojo_step(..., with_gradient = 1).  theta is a HOST pointer (fp64, whatever the handle's
+ * dtype).  DOJO_ERR_INVALID: a negative or non-finite friction coefficient or radius, a non-finite origin.  DOJO_ERR_UNSUPPORTED: a
+ * non-zero friction coefficient on an ImpactContact (it has none: pass 0).  Nothing is changed when a value is refused.
+ * dojo_get_contact_data: the handle's current theta.  With Nc = 0 both return DOJO_OK and touch nothing.
+ *
+ * dojo_rollout_data_record_dev = dojo_rollout_record_dev plus DC [H][B][5Nc][nx]: for every step the contact-data columns in the layout
+ * dojo_contact_gradients_dev writes (column-major per environment, DC[k][b][c][r] = d x_{k+1}[r] / d theta[c]: a column holds nx
+ * contiguous rows).  On a failed step DC[k][b], like DZ[k][b], holds nothing of use.  Refused like dojo_contact_gradients_dev, before
+ * anything is allocated or launched: body-body contacts, ImpactContact / LinearContact, more than 64 contacts, mechanisms outside the
+ * quad mapping (> 32 bodies).  DC == NULL: the call IS dojo_rollout_record_dev.
+ * Memory of the record: H * B * nx * (nx + nu + 5 Nc) * w bytes -- Ant (nx 156, nu 14, Nc 4), fp32, B = 4096, H = 20: 9.7 GB.
+ *
+ * dojo_rollout_data_adjoint_dev: ONE sweep launch on `stream` (plus a small reduction when gtheta is wanted), no synchronization.  With
+ * g_k as in dojo_rollout_adjoint_dev (G, cot_space, Z, status have the same meaning), per environment b:
+ *     lambda <- g_{H-1};  a <- 0
+ *     for k = H-1 .. 0:   if status && status[k][b] != 0:  lambda <- 0                           (DZ_k, DC_k are not read)
+ *                         else:                            a <- a + DC_k[b]^T lambda;   lambda <- DZ_k[b]^T lambda
+ *                         if k > 0: lambda <- lambda + g_{k-1}
+ *     gtheta_env[b] <- a   [B][5Nc];    gz[b] <- lambda   [B][nx], tangent coordinates;    gtheta <- sum_b a_b   [5Nc]
+ * Each output may be NULL, not all three.  Every product and sum is fp64, lambda and a stay fp64 between the steps, outputs are rounded
+ * once (gtheta after the sum over the batch).  No atomics, fixed summation orders: all outputs are bit-identical from run to run;
+ * gtheta_env and gz do not depend on the batch size or on an environment's position in the batch (the sum gtheta does: its order is
+ * fixed by B).  The gradient w.r.t. the controls is dojo_rollout_adjoint_dev's, over the same record.
+ * DOJO_ERR_INVALID (text on the handle, nothing launched): H < 1; NULL DZ or G; NULL DC with Nc > 0; all three outputs NULL;
+ * cot_space = 1 without Z; DZ or DC not 16-byte aligned.  Nc = 0: gz is computed, gtheta_env and gtheta are not touched.
+ *
+ * dojo_rollout_data_gradients (host pointers): uploads z0, U (NULL = zeros), G; allocates the record on the device, records, runs the
+ * sweep above -- and dojo_rollout_adjoint_dev over the same record when gU is not NULL --, downloads Z, status, gtheta [5Nc],
+ * gtheta_env [B][5Nc], gU [H][B][nu], gz [B][nx] (each may be NULL).  A record that does not fit into the free device memory:
+ * DOJO_ERR_INVALID with the byte count in the text, before any launch. */
+int  dojo_set_contact_data(DojoHandle h, const double* theta /* [Nc][5] */);
+int  dojo_get_contact_data(DojoHandle h, double* theta /* [Nc][5] */);
+int  dojo_rollout_data_record_dev(DojoHandle h, const void* z0, const void* U, int32_t H, void* Z, int32_t* status,
+                                  void* DZ, void* DU, void* DC /* [H][B][5Nc][nx] */, void* stream);
+int  dojo_rollout_data_adjoint_dev(DojoHandle h, int32_t H, const void* DZ, const void* DC, const void* G, int32_t cot_space,
+                                   const void* Z, const int32_t* status,
+                                   void* gtheta_env /* [B][5Nc] or NULL */, void* gtheta /* [5Nc], summed over the batch, or NULL */,
+                                   void* gz /* [B][nx] or NULL */, void* stream);
+int  dojo_rollout_data_gradients(DojoHandle h, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space,
+                                 void* Z, int32_t* status, void* gtheta, void* gtheta_env, void* gU, void* gz);
 
 /* Closed-loop rollouts: simulate!(mechanism, steps, storage, control!) (src/simulation/simulate.jl:16-37) with a controller that looks at the
  * state -- an affine feedback policy per environment, evaluated ON THE DEVICE between the steps (csrc/dojo_policy.hpp: observation, normalisation,
