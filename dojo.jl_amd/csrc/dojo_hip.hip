@@ -22,6 +22,7 @@
 #include <string>
 #include <map>
 #include <vector>
+#include <deque>
 #include <algorithm>
 #include <mutex>
 #include <dlfcn.h>
@@ -83,6 +84,21 @@ enum { PH_ALL = 0, PH_MAIN = 1, PH_GRAD = 2, PH_CONT = 3 };
 // the environments [env0, env0 + nenv) and their stream (env0: a multiple of the environments per wavefront), and how the kernels are run
 struct StepIO { const void *z, *u; void* z_next; int *status, *iters; void *dz, *du, *dc, *storage; };
 struct Span { size_t env0; int nenv; hipStream_t stream; };
+// What a rollout (rollout_core) is told: device arrays over the H steps, null = not given / not wanted
+struct Controller;
+struct RolloutIO {
+    const void* z0 = nullptr;               // [B][nz] the initial state (required)
+    const void* U = nullptr;                // [H][B][nu] pre-sampled controls; with a controller: its feed-forward term
+    void* Z = nullptr;                      // [H][B][nz] the state behind every step (null: the last one alone, in the handle's d_zn)
+    int32_t* status = nullptr;              // [H][B]
+    void* storage = nullptr;                // [H][B][Nb][25] save_to_storage! rows of every solved step
+    void *DZ = nullptr, *DU = nullptr;      // [H][B][nx][nx] / [H][B][nu][nx] the IFT Jacobians of every step, in the device layout of dojo_step_dev (dojo_rollout_record_dev)
+    void* DC = nullptr;                     // [H][B][5Nc][nx] (with DZ) the contact-data columns of every step: the step launch of a group is followed directly, on the same span and stream,
+                                            // by the contact-data IFT kernel of dojo_contact_gradients_dev, which reads the hand-off record that step just left for exactly those environments
+    const Controller* controller = nullptr; // closed loop (checked by the caller): the controls of step k are made on the group's stream, directly in front of the step, by the policy kernel ...
+    void* OBS = nullptr;                    // ... [H+1][B][nobs] what it saw
+    void* U_out = nullptr;                  // ... [H][B][nu] what it made (null: one [B][nu] buffer of the handle, a group's launches being serial)
+};
 struct Mode {
     int phase;
     int* slot;                         // timed launches: where a PH_ALL / PH_MAIN launch puts the timing slot it took, and the PH_GRAD launch of the same group finds it; null = not timed
@@ -156,6 +172,7 @@ struct DojoSim {
     std::map<size_t, int> dispatch_have;                   // first workgroup of a segment -> environments of the launch whose permutation it holds
     std::vector<int> group_slot;        // timing slot of the phased launches of an environment group (PH_MAIN -> PH_GRAD)
     std::vector<void*> owned;           // device memory of this handle (ensure), freed by dojo_destroy
+    size_t* measure = nullptr;          // not null: ensure / ensure_at_least add what they would allocate to it, and allocate nothing (Measuring)
     bool have_grad = false, have_solution = false, have_u = false;
     std::string err; std::mutex err_m;  // text of the last failure of a call on this handle (dojo_handle_error)
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;   // RCCL communicator of this handle's process group (dojo_comm_init)
@@ -396,9 +413,20 @@ __global__ void __launch_bounds__(1024) dispatch_order_kernel(const int* iters, 
 }
 } // namespace ckern
 
+// what an allocation takes from the device: whole 4096-byte granules, at least 8 bytes
+size_t granules(size_t bytes) { return (std::max<size_t>(bytes, 8) + 4095) / 4096 * 4096; }
+// While one lives, the handle measures: the code that allocates its workspaces runs as usual, and every buffer it would have to allocate adds its size to
+// `bytes` instead -- what a call is going to take is totalled by the lines that take it
+struct Measuring {
+    DojoSim* s; size_t bytes = 0;
+    explicit Measuring(DojoSim* s_) : s(s_) { s->measure = &bytes; }
+    ~Measuring() { s->measure = nullptr; }
+    Measuring(const Measuring&) = delete; Measuring& operator=(const Measuring&) = delete;
+};
 // device memory of the handle, allocated on first use and freed with the handle
 int ensure(DojoSim* s, void** p, size_t bytes) {
     if (*p) return DOJO_OK;
+    if (s->measure) { *s->measure += granules(bytes); return DOJO_OK; }
     HIPCHK(hipMalloc(p, bytes ? bytes : 8));
     s->owned.push_back(*p);
     return DOJO_OK;
@@ -1000,11 +1028,54 @@ int launch_policy_adjoint(const DojoSim* s, const DojoPolicy& p, int H, const Do
 // a workspace of the handle whose size depends on the call: kept while it is large enough, replaced (hipFree waits for the device) when it is not
 int ensure_at_least(DojoSim* s, void** p, size_t* have, size_t bytes) {
     if (*p && *have >= bytes) return DOJO_OK;
+    if (s->measure) { *s->measure += granules(bytes); return DOJO_OK; }
     if (*p) { s->owned.erase(std::remove(s->owned.begin(), s->owned.end(), *p), s->owned.end()); HIPCHK(hipFree(*p)); *p = nullptr; *have = 0; }
     HIPCHK(hipMalloc(p, bytes ? bytes : 8));
     s->owned.push_back(*p); *have = bytes;
     return DOJO_OK;
 }
+// ... those of the sweeps: the observation Jacobians of a closed-loop sweep whose caller passes none, and the per-environment accumulators in front of a reduction over the batch
+size_t pM_size(const DojoSim* s, size_t H) { return (H + 1) * s->B * 2 * s->M.nu * 24 * sizeof(double); }
+size_t macc_size(const DojoSim* s, size_t P) { return (size_t)s->B * P * sizeof(double); }
+int ensure_pM(DojoSim* s, size_t H) { return ensure_at_least(s, &s->d_pM, &s->pM_bytes, pM_size(s, H)); }
+int ensure_pacc(DojoSim* s, size_t na) { return ensure_at_least(s, (void**)&s->d_pacc, &s->pacc_bytes, (size_t)s->B * na * (2 * s->M.nu + 1) * sizeof(double)); }
+int ensure_macc(DojoSim* s, size_t P) { return ensure_at_least(s, (void**)&s->d_macc, &s->macc_bytes, macc_size(s, P)); }
+int ensure_dacc(DojoSim* s) { return ensure_at_least(s, (void**)&s->d_dacc, &s->dacc_bytes, (size_t)s->B * 5 * s->M.Nc * sizeof(double)); }
+
+// The temporary device buffers of a host-pointer rollout entry.  Each is declared once -- its size, the host array uploaded into it, the host array it is downloaded
+// into (either may be none) -- before anything is allocated, so that bytes() is the total of exactly what allocate() takes; all are freed on every return path.
+struct Staging {
+    struct Buf { size_t bytes; const void* src; void* dst; void* p; };
+    std::deque<Buf> bufs;               // (a deque: the references handed out stay valid)
+    Staging() = default; Staging(const Staging&) = delete; Staging& operator=(const Staging&) = delete;
+    ~Staging() { for (Buf& b : bufs) if (b.p) (void)hipFree(b.p); }
+    const Buf& input(size_t bytes, const void* src) { return add(bytes, src, nullptr, src != nullptr); }      // uploaded; a NULL array: no buffer
+    const Buf& output(size_t bytes, void* dst) { return add(bytes, nullptr, dst, dst != nullptr); }           // downloaded; a NULL array: no buffer
+    const Buf& kept(size_t bytes, void* dst = nullptr, bool wanted = true) { return add(bytes, nullptr, dst, wanted); }      // the device side needs it either way; downloaded into a non-NULL array
+    size_t bytes() const { size_t n = 0; for (const Buf& b : bufs) n += granules(b.bytes); return n; }
+    int allocate() {
+        for (Buf& b : bufs) {
+            HIPCHK(hipMalloc(&b.p, b.bytes ? b.bytes : 8));
+            if (b.src) HIPCHK(hipMemcpy(b.p, b.src, b.bytes, hipMemcpyHostToDevice));
+        }
+        return DOJO_OK;
+    }
+    // behind the device work of the call: the downloads, and the last state Z[H-1] into the handle's d_zn (dojo_get_state) as a rollout without Z leaves it there
+    int finish(DojoSim* s, const Buf& Z, int H) {
+        HIPCHK(hipDeviceSynchronize());
+        for (const Buf& b : bufs) if (b.dst) HIPCHK(hipMemcpy(b.dst, b.p, b.bytes, hipMemcpyDeviceToHost));
+        const size_t zb = (size_t)s->B * 13 * s->M.Nb * s->w;
+        if (Z.p) HIPCHK(hipMemcpy(s->d_zn, (char*)Z.p + (size_t)(H - 1) * zb, zb, hipMemcpyDeviceToDevice));
+        return DOJO_OK;
+    }
+private:
+    const Buf& add(size_t bytes, const void* src, void* dst, bool wanted) {
+        static const Buf none{0, nullptr, nullptr, nullptr};
+        if (!wanted) return none;
+        bufs.push_back(Buf{bytes, src, dst, nullptr});
+        return bufs.back();
+    }
+};
 
 // dojo_rollout_data_adjoint_dev: the contact-data sweep (dojo_data_adjoint.hpp; one workgroup per environment, one launch) and, for the gradient shared by the
 // batch, the reduction over the environments (one workgroup per entry)
@@ -1425,26 +1496,29 @@ int dojo_gradients(DojoHandle s, void* dz, void* du) {
     return DOJO_OK;
 }
 
-// simulate! with pre-sampled controls (src/simulation/simulate.jl:16-37): H steps, each fed with the previous step's
-// internal next state; storage != null records save_to_storage! rows [H][B][Nb][25] of every solved step
-// DZ / DU != null: the IFT Jacobians of every step as well, [H][B][nx][nx] / [H][B][nu][nx] in the device layout of dojo_step_dev (dojo_rollout_record_dev)
-// DC != null (dojo_rollout_data_record_dev; with DZ): the contact-data columns of every step as well, [H][B][5Nc][nx] -- the step launch of a group is followed directly, on the same
-// span and stream, by the contact-data IFT kernel of dojo_contact_gradients_dev, which reads the hand-off record that step just left for exactly those environments
-// pol != null (dojo_rollout_policy_dev, dojo_rollout_mlp_dev; checked by the caller; a Controller of either kind): U is the feed-forward term and the controls of step k are made on the group's stream, directly in front of
-// the step, by the policy kernel -- into U_out[k] (null: one [B][nu] buffer of the handle, a group's launches being serial); OBS [H+1][B][nobs] or null records what it saw
-static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* storage, void* stream, void* DZ = nullptr, void* DU = nullptr,
-                        const Controller* pol = nullptr, void* OBS = nullptr, void* U_out = nullptr, void* DC = nullptr) {
-    if (!s || !z0 || H < 1) { g_err = "dojo_rollout_dev: bad argument"; return DOJO_ERR_INVALID; }
-    HIPCHK(hipSetDevice(s->device));
-    size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, nx = 12 * s->M.Nb;
+// the handle's buffers a rollout uses, allocated on first use
+static int ensure_rollout(DojoHandle s, const RolloutIO& io) {
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb;
     ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
     ENSURE(s->d_vel, B * 6 * s->M.Nb * w); ENSURE(s->d_jimp, B * (s->M.n_joint_imp + 1) * w);
     ENSURE(s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w);
-    if (storage) ENSURE(s->d_res, B * 6 * s->M.Nb * w);
-    if (pol && !U_out) ENSURE(s->d_pu, B * nu * w);
+    if (io.storage) ENSURE(s->d_res, B * 6 * s->M.Nb * w);
+    if (io.controller && !io.U_out) ENSURE(s->d_pu, B * s->M.nu * w);
+    return DOJO_OK;
+}
+
+// simulate! with pre-sampled controls (src/simulation/simulate.jl:16-37): H steps, each fed with the previous step's
+// internal next state, and whatever of RolloutIO is asked for recorded along the way
+static int rollout_core(DojoHandle s, int32_t H, const RolloutIO& io, void* stream) {
+    if (!s || !io.z0 || H < 1) { g_err = "dojo_rollout_dev: bad argument"; return DOJO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, nx = 12 * s->M.Nb;
+    TRY(ensure_rollout(s, io));
+    const Controller* pol = io.controller;
     const size_t nobs = pol ? 2 * nu + (pol->contact_forces() ? (size_t)s->M.Nc : 0) : 0;
+    auto at = [](void* p, size_t offset) -> char* { return p ? (char*)p + offset : nullptr; };      // step k of an array that is recorded
     hipStream_t st = (hipStream_t)stream;
-    const char* cur = (const char*)z0;      // the state a group's next step starts from; behind the loops: the last state (the same buffer for every group)
+    const char* cur = (const char*)io.z0;   // the state a group's next step starts from; behind the loops: the last state (the same buffer for every group)
     int slot = -1; TRY(begin_timing(s, &slot, st));
     // Environments are independent, so the batch is rolled out as NG groups on internal streams: a group whose step
     // contains an environment that runs into max_iter (one wavefront, ~5x the mean step time) delays only itself while
@@ -1458,41 +1532,82 @@ static int rollout_core(DojoHandle s, const void* z0, const void* U, int32_t H, 
     for (size_t gi = 0; gi < P.groups(); ++gi) {
         const Span sp = P.span(gi, NG > 1 ? s->gstreams[gi] : st);
         if (NG > 1) HIPCHK(hipStreamWaitEvent(sp.stream, s->fork_event, 0));
-        cur = (const char*)z0;
+        cur = (const char*)io.z0;
         for (int k = 0; k < H; ++k) {
-            char* nxt = Z ? (char*)Z + (size_t)k * B * nz * w : (char*)((k & 1) ? s->d_z : s->d_zn);
-            const char* uk = (U && nu) ? (const char*)U + (size_t)k * B * nu * w : nullptr;
+            const size_t kB = (size_t)k * B;
+            char* nxt = io.Z ? at(io.Z, kB * nz * w) : (char*)((k & 1) ? s->d_z : s->d_zn);
+            const char* uk = nu ? at((void*)io.U, kB * nu * w) : nullptr;
             if (pol) {
-                char* upol = U_out ? (char*)U_out + (size_t)k * B * nu * w : (char*)s->d_pu;
-                TRY(launch_controller(s, *pol, k, cur, (k > 0 || pol->contact_init()) ? s->d_csg : nullptr, uk, OBS ? (char*)OBS + (size_t)k * B * nobs * w : nullptr, upol, sp));
+                char* upol = io.U_out ? at(io.U_out, kB * nu * w) : (char*)s->d_pu;
+                TRY(launch_controller(s, *pol, k, cur, (k > 0 || pol->contact_init()) ? s->d_csg : nullptr, uk, at(io.OBS, kB * nobs * w), upol, sp));
                 uk = upol;
             }
-            void* sk = storage ? (char*)storage + (size_t)k * B * 25 * s->M.Nb * w : nullptr;
-            void* dzk = DZ ? (char*)DZ + (size_t)k * B * nx * nx * w : nullptr;
-            void* duk = (DU && nu) ? (char*)DU + (size_t)k * B * nx * nu * w : nullptr;
-            TRY(launch_any(s, StepIO{cur, uk, nxt, status ? status + (size_t)k * B : nullptr, nullptr, dzk, duk, nullptr, sk}, sp, m));
+            int32_t* stk = io.status ? io.status + kB : nullptr;
+            TRY(launch_any(s, StepIO{cur, uk, nxt, stk, nullptr, at(io.DZ, kB * nx * nx * w), nu ? at(io.DU, kB * nx * nu * w) : nullptr, nullptr, at(io.storage, kB * 25 * s->M.Nb * w)}, sp, m));
             // (the same Mode: the same hand-off record, no timing slot -- m.slot is null --, and a launch with io.dc never reorders the dispatch)
-            if (DC && s->M.Nc > 0) TRY(launch_any(s, StepIO{cur, uk, nxt, nullptr, nullptr, nullptr, nullptr, (char*)DC + (size_t)k * B * nx * 5 * s->M.Nc * w, nullptr}, sp, m));
+            if (io.DC && s->M.Nc > 0) TRY(launch_any(s, StepIO{cur, uk, nxt, nullptr, nullptr, nullptr, nullptr, at(io.DC, kB * nx * 5 * s->M.Nc * w), nullptr}, sp, m));
             cur = nxt;
         }
-        if (pol && OBS) TRY(launch_controller(s, *pol, H, cur, s->d_csg, nullptr, (char*)OBS + (size_t)H * B * nobs * w, nullptr, sp));      // the observation of the final state
+        if (pol && io.OBS) TRY(launch_controller(s, *pol, H, cur, s->d_csg, nullptr, at(io.OBS, (size_t)H * B * nobs * w), nullptr, sp));      // the observation of the final state
         if (NG > 1) { HIPCHK(hipEventRecord(s->gevents[gi], sp.stream)); HIPCHK(hipStreamWaitEvent(st, s->gevents[gi], 0)); }
     }
     TRY(end_timing(s, slot, false, H, st));
-    if (!Z && cur != (const char*)s->d_zn) HIPCHK(hipMemcpyAsync(s->d_zn, cur, B * nz * w, hipMemcpyDeviceToDevice, st));
+    if (!io.Z && cur != (const char*)s->d_zn) HIPCHK(hipMemcpyAsync(s->d_zn, cur, B * nz * w, hipMemcpyDeviceToDevice, st));
     s->have_solution = true; s->have_grad = false;
     return guard.done();
 }
 
+// what a recording entry refuses on top of its own checks: refuse_unsupported's text, with the entry point in front of it
+static int refuse_record(DojoHandle s, const char* who, bool want_dc = false) {
+    const int rc = refuse_unsupported(s, true, want_dc);
+    if (rc != DOJO_OK) g_err = std::string(who) + ": " + g_err.c_str();
+    return rc;
+}
+
+// What the reverse sweeps (*_adjoint_dev) refuse alike, in the order they refuse it: the horizon, the entry's required arrays, the cotangent space, the entry's
+// further conditions, the alignment of the two Jacobian arrays the kernel reads (J1: null when it reads one)
+struct Refusal { bool applies; const char* text; };
+static int refuse_sweep(const char* who, int32_t H, std::initializer_list<Refusal> required, int32_t cot_space, const void* Z, std::initializer_list<Refusal> further,
+                        const void* J0, const void* J1, const char* jacobians) {
+    const std::string w_ = std::string(who) + ": ";
+    if (H < 1) { g_err = w_ + "H must be >= 1"; return DOJO_ERR_INVALID; }
+    for (const Refusal& r : required) if (r.applies) { g_err = w_ + r.text; return DOJO_ERR_INVALID; }
+    if (cot_space != 0 && cot_space != 1) { g_err = w_ + "cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
+    if (cot_space == 1 && !Z) { g_err = w_ + "cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
+    for (const Refusal& r : further) if (r.applies) { g_err = w_ + r.text; return DOJO_ERR_INVALID; }
+    if (((uintptr_t)J0 | (uintptr_t)J1) & 15) { g_err = w_ + jacobians + " must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
+    return DOJO_OK;
+}
+
+// The memory refusal of the *_gradients host entries, before anything is read, allocated or launched: what the call is going to allocate -- its staging buffers and
+// what `handle` measured of the handle's workspaces -- against the free device memory.  `what` opens the text, up to the byte count of the need.
+static int refuse_memory(const std::string& what, const Staging& st, const Measuring& handle, const char* verb) {
+    const size_t need = st.bytes() + handle.bytes;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    if (need <= free_b) return DOJO_OK;
+    g_err = what + std::to_string(need) + " bytes with the other buffers of the call) " + verb + " not fit into the " + std::to_string(free_b) + " bytes of free device memory";
+    return DOJO_ERR_INVALID;
+}
+// the workspaces a recording rollout takes on first use: those of rollout_core (the recording host entries keep no storage and record U_out: the io-dependent buffers of
+// ensure_rollout are not theirs) and of its differentiable step launches (sized for the whole batch, so one group's geometry gives them all)
+static int ensure_record(DojoHandle s) {
+    TRY(ensure_rollout(s, RolloutIO{}));
+    return ensure_workspaces(s, StepIO{}, step_mode(s, 1, false, true), geometry_of(s, whole_batch(s, nullptr), true), true, false);
+}
+
 int dojo_rollout_dev(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status, void* stream) {
     Enter enter_(s);
-    return rollout_core(s, z0, U, H, Z, status, nullptr, stream);
+    RolloutIO io; io.z0 = z0; io.U = U; io.Z = Z; io.status = status;
+    return rollout_core(s, H, io, stream);
 }
 
 int dojo_simulate_dev(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, void* storage, int32_t* status, void* stream) {
     Enter enter_(s);
     if (!storage) { g_err = "dojo_simulate_dev: storage must not be NULL (use dojo_rollout_dev for record = false)"; return DOJO_ERR_INVALID; }
-    return rollout_core(s, z0, U, H, Z, status, storage, stream);
+    RolloutIO io; io.z0 = z0; io.U = U; io.Z = Z; io.status = status; io.storage = storage;
+    return rollout_core(s, H, io, stream);
 }
 
 // dojo_rollout_dev plus the IFT Jacobians of every step, left on the device for dojo_rollout_adjoint_dev
@@ -1500,7 +1615,8 @@ int dojo_rollout_record_dev(DojoHandle s, const void* z0, const void* U, int32_t
     Enter enter_(s);
     if (!s || !z0 || H < 1 || !Z || !DZ || (!DU && s->M.nu > 0)) { g_err = "dojo_rollout_record_dev: bad argument (z0, Z, DZ and -- with nu > 0 -- DU are required, H >= 1)"; return DOJO_ERR_INVALID; }
     TRY(refuse_unsupported(s, true, false));
-    return rollout_core(s, z0, U, H, Z, status, nullptr, stream, DZ, DU);
+    RolloutIO io; io.z0 = z0; io.U = U; io.Z = Z; io.status = status; io.DZ = DZ; io.DU = DU;
+    return rollout_core(s, H, io, stream);
 }
 
 // Closed-loop rollouts: what is refused, before anything is launched or allocated
@@ -1522,7 +1638,8 @@ int dojo_rollout_policy_dev(DojoHandle s, const void* z0, const DojoPolicy* poli
     TRY(refuse_policy(s, z0, policy, H, "dojo_rollout_policy_dev"));
     const DojoPolicy p = *policy;      // (the caller's struct is read during the call only)
     Controller c; c.affine = &p;
-    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, nullptr, nullptr, &c, OBS, U_out);
+    RolloutIO io; io.z0 = z0; io.U = p.U_ff; io.Z = Z; io.status = status; io.controller = &c; io.OBS = OBS; io.U_out = U_out;
+    return rollout_core(s, H, io, stream);
 }
 
 // host pointers (the members of *policy too): upload, roll out on the device, download
@@ -1532,45 +1649,26 @@ int dojo_rollout_policy(DojoHandle s, const void* z0, const DojoPolicy* policy, 
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, na = (size_t)policy->na, Bw = policy->per_env ? B : 1;
     const size_t nobs = 2 * nu + (policy->contact_forces ? (size_t)s->M.Nc : 0);
-    DojoPolicy p = *policy;
-    DevBuf dz0, dW, db, dm, dsc, dUff, dZ, dO, dU, dS;
-    auto up = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
-        *dst = nullptr;
-        if (!src) return DOJO_OK;
-        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-        *dst = d.p;
-        return DOJO_OK;
-    };
-    const void* z0d = nullptr;
-    TRY(up(dz0, z0, B * nz * w, &z0d)); TRY(up(dW, policy->W, Bw * na * nobs * w, &p.W)); TRY(up(db, policy->bias, Bw * na * w, &p.bias));
-    TRY(up(dm, policy->mean, nobs * w, &p.mean)); TRY(up(dsc, policy->scale, nobs * w, &p.scale)); TRY(up(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
-    if (Z) HIPCHK(dZ.alloc(HB * nz * w));
-    if (OBS) HIPCHK(dO.alloc((HB + B) * nobs * w));
-    if (U_out) HIPCHK(dU.alloc(HB * nu * w));
-    if (status) HIPCHK(dS.alloc(HB * sizeof(int)));
+    Staging st;
+    const auto &dz0 = st.input(B * nz * w, z0), &dW = st.input(Bw * na * nobs * w, policy->W), &db = st.input(Bw * na * w, policy->bias);
+    const auto &dm = st.input(nobs * w, policy->mean), &dsc = st.input(nobs * w, policy->scale), &dUff = st.input(HB * nu * w, policy->U_ff);
+    const auto &dZ = st.output(HB * nz * w, Z), &dO = st.output((HB + B) * nobs * w, OBS), &dU = st.output(HB * nu * w, U_out), &dS = st.output(HB * sizeof(int), status);
+    TRY(st.allocate());
+    DojoPolicy p = *policy; p.W = dW.p; p.bias = db.p; p.mean = dm.p; p.scale = dsc.p; p.U_ff = dUff.p;
     Controller c; c.affine = &p;
-    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, nullptr, nullptr, &c, dO.p, dU.p));
-    HIPCHK(hipDeviceSynchronize());
-    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
-    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
-    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
-    if (Z) HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
-    return DOJO_OK;
+    RolloutIO io; io.z0 = dz0.p; io.U = p.U_ff; io.Z = dZ.p; io.status = (int32_t*)dS.p; io.controller = &c; io.OBS = dO.p; io.U_out = dU.p;
+    TRY(rollout_core(s, H, io, nullptr));
+    return st.finish(s, dZ, H);
 }
 
 int dojo_rollout_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void* DU, const void* G, int32_t cot_space, const void* Z, const int32_t* status,
                              void* gU, void* gz, void* stream) {
     Enter enter_(s);
-    if (!s) { g_err = "dojo_rollout_adjoint_dev: bad argument"; return DOJO_ERR_INVALID; }
-    if (H < 1) { g_err = "dojo_rollout_adjoint_dev: H must be >= 1"; return DOJO_ERR_INVALID; }
-    if (!DZ || !G) { g_err = "dojo_rollout_adjoint_dev: DZ and G must not be NULL"; return DOJO_ERR_INVALID; }
-    if (cot_space != 0 && cot_space != 1) { g_err = "dojo_rollout_adjoint_dev: cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
-    if (cot_space == 1 && !Z) { g_err = "dojo_rollout_adjoint_dev: cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
+    const char* who = "dojo_rollout_adjoint_dev";
+    if (!s) { g_err = std::string(who) + ": bad argument"; return DOJO_ERR_INVALID; }
     if (s->M.nu == 0) gU = nullptr;
-    if (gU && !DU) { g_err = "dojo_rollout_adjoint_dev: gU needs DU"; return DOJO_ERR_INVALID; }
-    if ((((uintptr_t)DZ) | (gU ? (uintptr_t)DU : (uintptr_t)0)) & 15) { g_err = "dojo_rollout_adjoint_dev: DZ and DU must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
-    if (dj::adjoint::lds_bytes(12 * s->M.Nb) > 65536) { g_err = "dojo_rollout_adjoint_dev: supports at most 170 bodies (lambda is kept in LDS)"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_sweep(who, H, {{!DZ || !G, "DZ and G must not be NULL"}}, cot_space, Z, {{gU && !DU, "gU needs DU"}}, DZ, gU ? DU : nullptr, "DZ and DU"));
+    if (dj::adjoint::lds_bytes(12 * s->M.Nb) > 65536) { g_err = std::string(who) + ": supports at most 170 bodies (lambda is kept in LDS)"; return DOJO_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the Jacobians)
@@ -1579,67 +1677,28 @@ int dojo_rollout_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void
                                       : launch_adjoint<double>(s, H, DZ, DU, G, cot_space, Z, status, gU, gz, st);
 }
 
-// device memory the workspaces of rollout_core and of the differentiable step launches take on first use (ensure_workspaces: sized for the whole batch,
-// so one group's geometry gives them all), each rounded up as the allocator does: what a recording host entry adds to its own buffers
-static size_t record_workspaces(DojoHandle s) {
-    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
-    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb;
-    size_t need = 0;
-    {
-        const Geometry ge = geometry_of(s, whole_batch(s, nullptr), true);
-        const size_t wT = sizeof(double);
-        if (!s->d_z) need += up(B * nz * w);
-        if (!s->d_zn) need += up(B * nz * w);
-        if (!s->d_vel) need += up(B * 6 * s->M.Nb * w);
-        if (!s->d_jimp) need += up(B * (s->M.n_joint_imp + 1) * w);
-        if (!s->d_csg) need += up(B * (csg_per(s) * s->M.Nc + 1) * w);
-        if (!s->d_sol) need += up(B * s->M.S * dj::sol_record<8, true>() * wT);
-        if (ge.quad && !s->d_fac) need += up(ge.waves_total * dj::FAC_PER_LANE * ge.lanes * wT);
-        if (ge.quad && !s->d_lu) need += up(ge.waves_total * dj::LU_PER_LANE * ge.lanes * wT);
-        if (ge.ypark_stride && !s->d_ypark) need += up(ge.waves_total * (size_t)ge.ypark_stride * wT);
-        if (ge.msg_stride && !s->d_msg) need += up(B * (size_t)ge.msg_stride * wT);
-        if (ge.quad && std::isfinite(refine_threshold(s))) { if (!s->d_blk) need += up(ge.waves_total * 90 * ge.lanes * wT); if (!s->d_flag) need += up(B * sizeof(int)); }
-    }
-    return need;
-}
-
 // host pointers: upload, record on the device, reverse sweep, download -- the Jacobians never cross PCIe
 int dojo_rollout_gradients(DojoHandle s, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space, void* Z, int32_t* status, void* gU, void* gz) {
     Enter enter_(s);
-    if (!s || !z0 || !G || H < 1 || (cot_space != 0 && cot_space != 1)) { g_err = "dojo_rollout_gradients: bad argument"; return DOJO_ERR_INVALID; }
+    const std::string who = "dojo_rollout_gradients";
+    if (!s || !z0 || !G || H < 1 || (cot_space != 0 && cot_space != 1)) { g_err = who + ": bad argument"; return DOJO_ERR_INVALID; }
     TRY(refuse_unsupported(s, true, false));
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
-    const size_t record = HB * nx * (nx + nu) * w;
-    // everything this call allocates: the buffers below (each rounded up as the allocator does) and the workspaces rollout_core and the
-    // differentiable step launches take on first use (ensure_workspaces: sized for the whole batch, so one group's geometry gives them all)
-    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
-    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + up(HB * nu * w) + up(B * nx * w)
-                  + ((U && nu) ? up(HB * nu * w) : 0);
-    need += record_workspaces(s);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b) {
-        g_err = "dojo_rollout_gradients: the record of " + std::to_string(record) + " bytes (H B nx (nx + nu) scalars; " + std::to_string(need) + " bytes with the other buffers of the call) does not fit into the "
-                + std::to_string(free_b) + " bytes of free device memory";
-        return DOJO_ERR_INVALID;
+    Staging st;
+    const auto &dz0 = st.input(B * nz * w, z0), &dG = st.input(HB * ng * w, G), &dU = st.input(HB * nu * w, nu ? U : nullptr);
+    const auto &dZ = st.kept(HB * nz * w, Z), &dS = st.kept(HB * sizeof(int), status), &dDZ = st.kept(HB * nx * nx * w), &dDU = st.kept(HB * nx * nu * w);
+    const auto &dgU = st.kept(HB * nu * w, nu ? gU : nullptr), &dgz = st.kept(B * nx * w, gz);
+    {
+        Measuring handle(s);
+        TRY(ensure_record(s));
+        TRY(refuse_memory(who + ": the record of " + std::to_string(HB * nx * (nx + nu) * w) + " bytes (H B nx (nx + nu) scalars; ", st, handle, "does"));
     }
-    DevBuf dz0, dU, dG, dZ, dS, dDZ, dDU, dgU, dgz;
-    HIPCHK(dz0.alloc(B * nz * w)); HIPCHK(dG.alloc(HB * ng * w)); HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
-    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w)); HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w));
-    HIPCHK(hipMemcpy(dz0.p, z0, B * nz * w, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dG.p, G, HB * ng * w, hipMemcpyHostToDevice));
-    if (U && nu) { HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(hipMemcpy(dU.p, U, HB * nu * w, hipMemcpyHostToDevice)); }
-    TRY(rollout_core(s, dz0.p, dU.p, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p));
+    TRY(st.allocate());
+    RolloutIO io; io.z0 = dz0.p; io.U = dU.p; io.Z = dZ.p; io.status = (int32_t*)dS.p; io.DZ = dDZ.p; io.DU = dDU.p;
+    TRY(rollout_core(s, H, io, nullptr));
     TRY(dojo_rollout_adjoint_dev(s, H, dDZ.p, dDU.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, dgU.p, dgz.p, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
-    if (gU && nu) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
-    return DOJO_OK;
+    return st.finish(s, dZ, H);
 }
 
 // ---- contact-data gradients through rollouts (dojo_data_adjoint.hpp): get_contact_gradients (src/gradients/contact.jl:1-55) per step, chained as in
@@ -1650,33 +1709,27 @@ int dojo_rollout_data_record_dev(DojoHandle s, const void* z0, const void* U, in
     Enter enter_(s);
     const char* who = "dojo_rollout_data_record_dev";
     if (!s || !z0 || H < 1 || !Z || !DZ || (!DU && s->M.nu > 0)) { g_err = std::string(who) + ": bad argument (z0, Z, DZ and -- with nu > 0 -- DU are required, H >= 1)"; return DOJO_ERR_INVALID; }
-    {   // body-body contacts, Impact / Linear contacts, more than 64 contacts, the lane mapping: refused before anything is allocated or launched
-        const int rc = refuse_unsupported(s, true, s->M.Nc > 0);
-        if (rc != DOJO_OK) { g_err = std::string(who) + ": " + g_err.c_str(); return rc; }
-    }
-    return rollout_core(s, z0, U, H, Z, status, nullptr, stream, DZ, DU, nullptr, nullptr, nullptr, DC);
+    // body-body contacts, Impact / Linear contacts, more than 64 contacts, the lane mapping: refused before anything is allocated or launched
+    TRY(refuse_record(s, who, s->M.Nc > 0));
+    RolloutIO io; io.z0 = z0; io.U = U; io.Z = Z; io.status = status; io.DZ = DZ; io.DU = DU; io.DC = DC;
+    return rollout_core(s, H, io, stream);
 }
 
 int dojo_rollout_data_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void* DC, const void* G, int32_t cot_space, const void* Z, const int32_t* status,
                                   void* gtheta_env, void* gtheta, void* gz, void* stream) {
     Enter enter_(s);
-    const std::string who = "dojo_rollout_data_adjoint_dev";
-    if (!s) { g_err = who + ": bad argument"; return DOJO_ERR_INVALID; }
+    const char* who = "dojo_rollout_data_adjoint_dev";
+    if (!s) { g_err = std::string(who) + ": bad argument"; return DOJO_ERR_INVALID; }
     const int Nc = s->M.Nc;
-    if (H < 1) { g_err = who + ": H must be >= 1"; return DOJO_ERR_INVALID; }
-    if (!DZ || !G) { g_err = who + ": DZ and G must not be NULL"; return DOJO_ERR_INVALID; }
-    if (!DC && Nc > 0) { g_err = who + ": DC must not be NULL (a mechanism without contacts has none)"; return DOJO_ERR_INVALID; }
-    if (cot_space != 0 && cot_space != 1) { g_err = who + ": cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
-    if (cot_space == 1 && !Z) { g_err = who + ": cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
-    if (!gtheta_env && !gtheta && !gz) { g_err = who + ": gtheta_env, gtheta and gz are all NULL"; return DOJO_ERR_INVALID; }
-    if ((((uintptr_t)DZ) | (Nc > 0 ? (uintptr_t)DC : (uintptr_t)0)) & 15) { g_err = who + ": DZ and DC must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
-    if (dj::dadjoint::lds_bytes(12 * s->M.Nb, 5 * Nc) > 65536) { g_err = who + ": lambda, g and the 5 Nc accumulators (4 nx + 5 Nc doubles) do not fit into 64 KB of LDS"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_sweep(who, H, {{!DZ || !G, "DZ and G must not be NULL"}, {!DC && Nc > 0, "DC must not be NULL (a mechanism without contacts has none)"}}, cot_space, Z,
+                     {{!gtheta_env && !gtheta && !gz, "gtheta_env, gtheta and gz are all NULL"}}, DZ, Nc > 0 ? DC : nullptr, "DZ and DC"));
+    if (dj::dadjoint::lds_bytes(12 * s->M.Nb, 5 * Nc) > 65536) { g_err = std::string(who) + ": lambda, g and the 5 Nc accumulators (4 nx + 5 Nc doubles) do not fit into 64 KB of LDS"; return DOJO_ERR_UNSUPPORTED; }
     if (Nc == 0) { gtheta_env = nullptr; gtheta = nullptr; }      // no contact data: gz alone, the gtheta outputs are not touched
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the Jacobians)
     if (!gtheta_env && !gtheta && !gz) return DOJO_OK;
-    if (gtheta) TRY(ensure_at_least(s, (void**)&s->d_dacc, &s->dacc_bytes, (size_t)s->B * 5 * Nc * sizeof(double)));
+    if (gtheta) TRY(ensure_dacc(s));
     double* acc = gtheta ? s->d_dacc : nullptr;
     return s->dtype == DOJO_DTYPE_F32 ? launch_data_adjoint<float>(s, H, DZ, DC, G, cot_space, Z, status, gtheta_env, acc, gtheta, gz, st)
                                       : launch_data_adjoint<double>(s, H, DZ, DC, G, cot_space, Z, status, gtheta_env, acc, gtheta, gz, st);
@@ -1689,44 +1742,27 @@ int dojo_rollout_data_gradients(DojoHandle s, const void* z0, const void* U, int
     Enter enter_(s);
     const std::string who = "dojo_rollout_data_gradients";
     if (!s || !z0 || !G || H < 1 || (cot_space != 0 && cot_space != 1)) { g_err = who + ": bad argument"; return DOJO_ERR_INVALID; }
-    {
-        const int rc = refuse_unsupported(s, true, s->M.Nc > 0);
-        if (rc != DOJO_OK) { g_err = who + ": " + g_err.c_str(); return rc; }
-    }
+    TRY(refuse_record(s, who.c_str(), s->M.Nc > 0));
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, nth = 5 * (size_t)s->M.Nc, HB = (size_t)H * B, ng = cot_space ? nz : nx;
-    const size_t record = HB * nx * (nx + nu + nth) * w;
-    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
-    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + up(HB * nx * nth * w) + up(HB * nu * w)
-                  + up(B * nx * w) + up(B * nth * w) + up(nth * w) + up(B * nth * sizeof(double)) + ((U && nu) ? up(HB * nu * w) : 0);
-    need += record_workspaces(s);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b) {
-        g_err = who + ": the record of " + std::to_string(record) + " bytes (H B nx (nx + nu + 5 Nc) scalars; " + std::to_string(need) + " bytes with the other buffers of the call) does not fit into the "
-                + std::to_string(free_b) + " bytes of free device memory";
-        return DOJO_ERR_INVALID;
+    if (!nth) { gtheta = nullptr; gtheta_env = nullptr; }      // no contact data: these outputs are not touched
+    Staging st;
+    const auto &dz0 = st.input(B * nz * w, z0), &dG = st.input(HB * ng * w, G), &dU = st.input(HB * nu * w, nu ? U : nullptr);
+    const auto &dZ = st.kept(HB * nz * w, Z), &dS = st.kept(HB * sizeof(int), status);
+    const auto &dDZ = st.kept(HB * nx * nx * w), &dDU = st.kept(HB * nx * nu * w), &dDC = st.kept(HB * nx * nth * w);
+    const auto &dgt = st.kept(nth * w, gtheta), &dgte = st.kept(B * nth * w, gtheta_env), &dgU = st.kept(HB * nu * w, nu ? gU : nullptr), &dgz = st.kept(B * nx * w, gz);
+    {
+        Measuring handle(s);
+        TRY(ensure_record(s));
+        if (gtheta) TRY(ensure_dacc(s));
+        TRY(refuse_memory(who + ": the record of " + std::to_string(HB * nx * (nx + nu + nth) * w) + " bytes (H B nx (nx + nu + 5 Nc) scalars; ", st, handle, "does"));
     }
-    DevBuf dz0, dU, dG, dZ, dS, dDZ, dDU, dDC, dgU, dgz, dgt, dgte;
-    HIPCHK(dz0.alloc(B * nz * w)); HIPCHK(dG.alloc(HB * ng * w)); HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
-    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w)); HIPCHK(dDC.alloc(HB * nx * nth * w));
-    HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w)); HIPCHK(dgt.alloc(nth * w)); HIPCHK(dgte.alloc(B * nth * w));
-    HIPCHK(hipMemcpy(dz0.p, z0, B * nz * w, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dG.p, G, HB * ng * w, hipMemcpyHostToDevice));
-    if (U && nu) { HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(hipMemcpy(dU.p, U, HB * nu * w, hipMemcpyHostToDevice)); }
-    TRY(rollout_core(s, dz0.p, dU.p, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, nullptr, nullptr, nullptr, dDC.p));
-    TRY(dojo_rollout_data_adjoint_dev(s, H, dDZ.p, dDC.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, (gtheta_env && nth) ? dgte.p : nullptr, (gtheta && nth) ? dgt.p : nullptr, dgz.p, nullptr));
+    TRY(st.allocate());
+    RolloutIO io; io.z0 = dz0.p; io.U = dU.p; io.Z = dZ.p; io.status = (int32_t*)dS.p; io.DZ = dDZ.p; io.DU = dDU.p; io.DC = dDC.p;
+    TRY(rollout_core(s, H, io, nullptr));
+    TRY(dojo_rollout_data_adjoint_dev(s, H, dDZ.p, dDC.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, gtheta_env ? dgte.p : nullptr, gtheta ? dgt.p : nullptr, dgz.p, nullptr));
     if (gU && nu) TRY(dojo_rollout_adjoint_dev(s, H, dDZ.p, dDU.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, dgU.p, nullptr, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
-    if (gtheta && nth) HIPCHK(hipMemcpy(gtheta, dgt.p, nth * w, hipMemcpyDeviceToHost));
-    if (gtheta_env && nth) HIPCHK(hipMemcpy(gtheta_env, dgte.p, B * nth * w, hipMemcpyDeviceToHost));
-    if (gU && nu) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
-    return DOJO_OK;
+    return st.finish(s, dZ, H);
 }
 
 // ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----
@@ -1755,13 +1791,6 @@ int dojo_observation_jacobian(DojoHandle s, const void* z, double* M) {
     return DOJO_OK;
 }
 
-// what a recording entry refuses on top of refuse_policy: refuse_unsupported's text, with the entry point in front of it
-static int refuse_record(DojoHandle s, const char* who) {
-    const int rc = refuse_unsupported(s, true, false);
-    if (rc != DOJO_OK) g_err = std::string(who) + ": " + g_err.c_str();
-    return rc;
-}
-
 int dojo_rollout_policy_record_dev(DojoHandle s, const void* z0, const DojoPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, int32_t* status,
                                    void* DZ, void* DU, void* stream) {
     Enter enter_(s);
@@ -1770,7 +1799,8 @@ int dojo_rollout_policy_record_dev(DojoHandle s, const void* z0, const DojoPolic
     TRY(refuse_record(s, "dojo_rollout_policy_record_dev"));
     const DojoPolicy p = *policy;
     Controller c; c.affine = &p;
-    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, DZ, DU, &c, OBS, U_out);
+    RolloutIO io; io.z0 = z0; io.U = p.U_ff; io.Z = Z; io.status = status; io.DZ = DZ; io.DU = DU; io.controller = &c; io.OBS = OBS; io.U_out = U_out;
+    return rollout_core(s, H, io, stream);
 }
 
 // everything the closed-loop sweep refuses, before anything is launched or allocated (z0 of refuse_policy: not this entry's -- the policy stands in)
@@ -1787,33 +1817,31 @@ static int refuse_policy_adjoint(DojoHandle s, const DojoPolicy* p, int32_t H, c
     return DOJO_OK;
 }
 
+// the observation Jacobians of a closed-loop sweep whose caller passes none (M = NULL): of z0 and the first H - 1 states of Z -- and of the last one where the final
+// observation has a cotangent --, into the handle's buffer
+static int observation_jacobians(DojoHandle s, int32_t H, const void* z0, const void* Z, bool final_state, hipStream_t st, const double** M) {
+    TRY(ensure_pM(s, (size_t)H));
+    TRY(launch_observation_jacobian(s, z0, Z, (long long)H + (final_state ? 1 : 0), (double*)s->d_pM, st));
+    *M = (const double*)s->d_pM;
+    return DOJO_OK;
+}
+
 int dojo_rollout_policy_adjoint_dev(DojoHandle s, const DojoPolicy* policy, int32_t H, const DojoPolicyAdjoint* a_, void* stream) {
     Enter enter_(s);
     const char* who = "dojo_rollout_policy_adjoint_dev";
-    const std::string w_ = std::string(who) + ": ";
     TRY(refuse_policy_adjoint(s, policy, H, who));
-    if (!a_) { g_err = w_ + "the argument record must not be NULL"; return DOJO_ERR_INVALID; }
+    if (!a_) { g_err = std::string(who) + ": the argument record must not be NULL"; return DOJO_ERR_INVALID; }
     const DojoPolicy p = *policy; const DojoPolicyAdjoint a = *a_;      // (the caller's structs are read during the call only)
-    if (!a.DZ || !a.OBS || !a.G) { g_err = w_ + "DZ, OBS and G must not be NULL"; return DOJO_ERR_INVALID; }
-    if (!a.DU) { g_err = w_ + "gU, gW, gbias and gz need DU"; return DOJO_ERR_INVALID; }
-    if (a.cot_space != 0 && a.cot_space != 1) { g_err = w_ + "cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
-    if (a.cot_space == 1 && !a.Z) { g_err = w_ + "cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
-    if (!a.M && (!a.z0 || !a.Z)) { g_err = w_ + "M = NULL needs z0 and Z (the observation Jacobians are computed from them)"; return DOJO_ERR_INVALID; }
-    if ((((uintptr_t)a.DZ) | (uintptr_t)a.DU) & 15) { g_err = w_ + "DZ and DU must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_sweep(who, H, {{!a.DZ || !a.OBS || !a.G, "DZ, OBS and G must not be NULL"}, {!a.DU, "gU, gW, gbias and gz need DU"}}, a.cot_space, a.Z,
+                     {{!a.M && (!a.z0 || !a.Z), "M = NULL needs z0 and Z (the observation Jacobians are computed from them)"}}, a.DZ, a.DU, "DZ and DU"));
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the record)
     if (!a.gW && !a.gbias && !a.gU && !a.gz) return DOJO_OK;
-    const size_t B = s->B, nobs = 2 * s->M.nu;
     const double* M = a.M;
-    if (!M) {
-        const long long n = (long long)H + (a.G_obs ? 1 : 0);
-        TRY(ensure_at_least(s, &s->d_pM, &s->pM_bytes, ((size_t)H + 1) * B * nobs * 24 * sizeof(double)));
-        TRY(launch_observation_jacobian(s, a.z0, a.Z, n, (double*)s->d_pM, st));
-        M = (const double*)s->d_pM;
-    }
+    if (!M) TRY(observation_jacobians(s, H, a.z0, a.Z, a.G_obs != nullptr, st, &M));
     double* acc = nullptr;
-    if (!p.per_env) { TRY(ensure_at_least(s, (void**)&s->d_pacc, &s->pacc_bytes, B * (size_t)p.na * (nobs + 1) * sizeof(double))); acc = s->d_pacc; }
+    if (!p.per_env) { TRY(ensure_pacc(s, (size_t)p.na)); acc = s->d_pacc; }
     return s->dtype == DOJO_DTYPE_F32 ? launch_policy_adjoint<float>(s, p, H, a, M, acc, st) : launch_policy_adjoint<double>(s, p, H, a, M, acc, st);
 }
 
@@ -1830,53 +1858,29 @@ int dojo_rollout_policy_gradients(DojoHandle s, const void* z0, const DojoPolicy
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
     const size_t na = (size_t)policy->na, Bw = policy->per_env ? B : 1, nobs = 2 * nu;
-    const size_t record = HB * nx * (nx + nu) * w, mbytes = (HB + B) * nobs * 24 * sizeof(double);
-    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
-    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + 3 * up(HB * nu * w) + up(B * nx * w)
-                  + 2 * up((HB + B) * nobs * w) + 2 * up(Bw * na * (nobs + 1) * w) + 2 * up(nobs * w) + (policy->U_ff ? up(HB * nu * w) : 0)
-                  + ((s->d_pM && s->pM_bytes >= mbytes) ? 0 : up(mbytes)) + (policy->per_env ? 0 : up(B * na * (nobs + 1) * sizeof(double)));
-    need += record_workspaces(s);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b) {
-        g_err = w_ + "the record of " + std::to_string(record) + " bytes and the observation Jacobians of " + std::to_string(mbytes) + " bytes (" + std::to_string(need)
-                + " bytes with the other buffers of the call) do not fit into the " + std::to_string(free_b) + " bytes of free device memory";
-        return DOJO_ERR_INVALID;
+    Staging st;
+    const auto &dz0 = st.input(B * nz * w, z0), &dW = st.input(Bw * na * nobs * w, policy->W), &db = st.input(Bw * na * w, policy->bias);
+    const auto &dm = st.input(nobs * w, policy->mean), &dsc = st.input(nobs * w, policy->scale), &dUff = st.input(HB * nu * w, policy->U_ff);
+    const auto &dG = st.input(HB * ng * w, G), &dGu = st.input(HB * nu * w, G_u), &dGo = st.input((HB + B) * nobs * w, G_obs);
+    const auto &dZ = st.kept(HB * nz * w, Z), &dO = st.kept((HB + B) * nobs * w, OBS), &dU = st.kept(HB * nu * w, U_out), &dS = st.kept(HB * sizeof(int), status);
+    const auto &dDZ = st.kept(HB * nx * nx * w), &dDU = st.kept(HB * nx * nu * w);
+    const auto &dgW = st.kept(Bw * na * nobs * w, gW), &dgb = st.kept(Bw * na * w, gbias), &dgU = st.kept(HB * nu * w, gU), &dgz = st.kept(B * nx * w, gz);
+    {
+        Measuring handle(s);
+        TRY(ensure_record(s)); TRY(ensure_pM(s, (size_t)H));
+        if (!policy->per_env) TRY(ensure_pacc(s, na));
+        TRY(refuse_memory(w_ + "the record of " + std::to_string(HB * nx * (nx + nu) * w) + " bytes and the observation Jacobians of " + std::to_string(pM_size(s, (size_t)H)) + " bytes (", st, handle, "do"));
     }
-    DojoPolicy p = *policy;
-    DevBuf dz0, dW, db, dm, dsc, dUff, dG, dGu, dGo, dZ, dO, dU, dS, dDZ, dDU, dgW, dgb, dgU, dgz;
-    auto upl = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
-        *dst = nullptr;
-        if (!src) return DOJO_OK;
-        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-        *dst = d.p;
-        return DOJO_OK;
-    };
-    DojoPolicyAdjoint a{};
-    const void* z0d = nullptr;
-    TRY(upl(dz0, z0, B * nz * w, &z0d)); TRY(upl(dW, policy->W, Bw * na * nobs * w, &p.W)); TRY(upl(db, policy->bias, Bw * na * w, &p.bias));
-    TRY(upl(dm, policy->mean, nobs * w, &p.mean)); TRY(upl(dsc, policy->scale, nobs * w, &p.scale)); TRY(upl(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
-    TRY(upl(dG, G, HB * ng * w, &a.G)); TRY(upl(dGu, G_u, HB * nu * w, &a.G_u)); TRY(upl(dGo, G_obs, (HB + B) * nobs * w, &a.G_obs));
-    HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dO.alloc((HB + B) * nobs * w)); HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
-    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w));
-    HIPCHK(dgW.alloc(Bw * na * nobs * w)); HIPCHK(dgb.alloc(Bw * na * w)); HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w));
+    TRY(st.allocate());
+    DojoPolicy p = *policy; p.W = dW.p; p.bias = db.p; p.mean = dm.p; p.scale = dsc.p; p.U_ff = dUff.p;
     Controller c; c.affine = &p;
-    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, &c, dO.p, dU.p));
-    a.DZ = dDZ.p; a.DU = dDU.p; a.OBS = dO.p; a.status = (const int32_t*)dS.p; a.z0 = z0d; a.Z = dZ.p; a.M = nullptr; a.cot_space = cot_space;
+    RolloutIO io; io.z0 = dz0.p; io.U = p.U_ff; io.Z = dZ.p; io.status = (int32_t*)dS.p; io.DZ = dDZ.p; io.DU = dDU.p; io.controller = &c; io.OBS = dO.p; io.U_out = dU.p;
+    TRY(rollout_core(s, H, io, nullptr));
+    DojoPolicyAdjoint a{};
+    a.G = dG.p; a.G_u = dGu.p; a.G_obs = dGo.p; a.DZ = dDZ.p; a.DU = dDU.p; a.OBS = dO.p; a.status = (const int32_t*)dS.p; a.z0 = dz0.p; a.Z = dZ.p; a.M = nullptr; a.cot_space = cot_space;
     a.gW = dgW.p; a.gbias = dgb.p; a.gU = dgU.p; a.gz = dgz.p;
     TRY(dojo_rollout_policy_adjoint_dev(s, &p, H, &a, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
-    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
-    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
-    if (gW) HIPCHK(hipMemcpy(gW, dgW.p, Bw * na * nobs * w, hipMemcpyDeviceToHost));
-    if (gbias) HIPCHK(hipMemcpy(gbias, dgb.p, Bw * na * w, hipMemcpyDeviceToHost));
-    if (gU) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
-    return DOJO_OK;
+    return st.finish(s, dZ, H);
 }
 
 // ---- closed-loop rollouts with a network policy, forward and reverse mode (dojo_mlp.hpp) ----
@@ -1907,7 +1911,8 @@ int dojo_rollout_mlp_dev(DojoHandle s, const void* z0, const DojoMlpPolicy* poli
     TRY(refuse_mlp(s, z0, policy, H, "dojo_rollout_mlp_dev", &c.shape));
     const DojoMlpPolicy p = *policy;      // (the caller's struct is read during the call only)
     c.mlp = &p; c.ACT = c.shape.nh ? ACT : nullptr;
-    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, nullptr, nullptr, &c, OBS, U_out);
+    RolloutIO io; io.z0 = z0; io.U = p.U_ff; io.Z = Z; io.status = status; io.controller = &c; io.OBS = OBS; io.U_out = U_out;
+    return rollout_core(s, H, io, stream);
 }
 
 // host pointers (the members of *policy too): upload, roll out on the device, download
@@ -1918,31 +1923,16 @@ int dojo_rollout_mlp(DojoHandle s, const void* z0, const DojoMlpPolicy* policy, 
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, Bw = policy->per_env ? B : 1, P = (size_t)c.shape.P;
     const size_t nobs = 2 * nu + (policy->contact_forces ? (size_t)s->M.Nc : 0);
-    DojoMlpPolicy p = *policy;
-    DevBuf dz0, dth, dm, dsc, dUff, dZ, dO, dU, dS;
-    auto up = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
-        *dst = nullptr;
-        if (!src) return DOJO_OK;
-        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-        *dst = d.p;
-        return DOJO_OK;
-    };
-    const void* z0d = nullptr;
-    TRY(up(dz0, z0, B * nz * w, &z0d)); TRY(up(dth, policy->theta, Bw * P * w, &p.theta));
-    TRY(up(dm, policy->mean, nobs * w, &p.mean)); TRY(up(dsc, policy->scale, nobs * w, &p.scale)); TRY(up(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
-    if (Z) HIPCHK(dZ.alloc(HB * nz * w));
-    if (OBS) HIPCHK(dO.alloc((HB + B) * nobs * w));
-    if (U_out) HIPCHK(dU.alloc(HB * nu * w));
-    if (status) HIPCHK(dS.alloc(HB * sizeof(int)));
+    Staging st;
+    const auto &dz0 = st.input(B * nz * w, z0), &dth = st.input(Bw * P * w, policy->theta);
+    const auto &dm = st.input(nobs * w, policy->mean), &dsc = st.input(nobs * w, policy->scale), &dUff = st.input(HB * nu * w, policy->U_ff);
+    const auto &dZ = st.output(HB * nz * w, Z), &dO = st.output((HB + B) * nobs * w, OBS), &dU = st.output(HB * nu * w, U_out), &dS = st.output(HB * sizeof(int), status);
+    TRY(st.allocate());
+    DojoMlpPolicy p = *policy; p.theta = dth.p; p.mean = dm.p; p.scale = dsc.p; p.U_ff = dUff.p;
     c.mlp = &p;
-    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, nullptr, nullptr, &c, dO.p, dU.p));
-    HIPCHK(hipDeviceSynchronize());
-    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
-    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
-    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
-    if (Z) HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
-    return DOJO_OK;
+    RolloutIO io; io.z0 = dz0.p; io.U = p.U_ff; io.Z = dZ.p; io.status = (int32_t*)dS.p; io.controller = &c; io.OBS = dO.p; io.U_out = dU.p;
+    TRY(rollout_core(s, H, io, nullptr));
+    return st.finish(s, dZ, H);
 }
 
 int dojo_rollout_mlp_record_dev(DojoHandle s, const void* z0, const DojoMlpPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, double* ACT, int32_t* status,
@@ -1956,7 +1946,8 @@ int dojo_rollout_mlp_record_dev(DojoHandle s, const void* z0, const DojoMlpPolic
     TRY(refuse_record(s, who));
     const DojoMlpPolicy p = *policy;
     c.mlp = &p; c.ACT = c.shape.nh ? ACT : nullptr;
-    return rollout_core(s, z0, p.U_ff, H, Z, status, nullptr, stream, DZ, DU, &c, OBS, U_out);
+    RolloutIO io; io.z0 = z0; io.U = p.U_ff; io.Z = Z; io.status = status; io.DZ = DZ; io.DU = DU; io.controller = &c; io.OBS = OBS; io.U_out = U_out;
+    return rollout_core(s, H, io, stream);
 }
 
 // everything the network sweep refuses, before anything is launched or allocated (z0 of refuse_mlp: not this entry's -- the policy stands in)
@@ -1976,31 +1967,20 @@ static int refuse_mlp_adjoint(DojoHandle s, const DojoMlpPolicy* p, int32_t H, c
 int dojo_rollout_mlp_adjoint_dev(DojoHandle s, const DojoMlpPolicy* policy, int32_t H, const DojoMlpAdjoint* a_, void* stream) {
     Enter enter_(s);
     const char* who = "dojo_rollout_mlp_adjoint_dev";
-    const std::string w_ = std::string(who) + ": ";
     dj::mlp::Shape sh{};
     TRY(refuse_mlp_adjoint(s, policy, H, who, &sh));
-    if (!a_) { g_err = w_ + "the argument record must not be NULL"; return DOJO_ERR_INVALID; }
+    if (!a_) { g_err = std::string(who) + ": the argument record must not be NULL"; return DOJO_ERR_INVALID; }
     const DojoMlpPolicy p = *policy; const DojoMlpAdjoint a = *a_;      // (the caller's structs are read during the call only)
-    if (!a.DZ || !a.OBS || !a.G) { g_err = w_ + "DZ, OBS and G must not be NULL"; return DOJO_ERR_INVALID; }
-    if (!a.DU) { g_err = w_ + "gU, gtheta and gz need DU"; return DOJO_ERR_INVALID; }
-    if (p.n_layers > 1 && !a.ACT) { g_err = w_ + "ACT is required with n_layers > 1 (the recorded activations)"; return DOJO_ERR_INVALID; }
-    if (a.cot_space != 0 && a.cot_space != 1) { g_err = w_ + "cot_space must be 0 (tangent) or 1 (state)"; return DOJO_ERR_INVALID; }
-    if (a.cot_space == 1 && !a.Z) { g_err = w_ + "cot_space = 1 needs the states Z"; return DOJO_ERR_INVALID; }
-    if (!a.M && (!a.z0 || !a.Z)) { g_err = w_ + "M = NULL needs z0 and Z (the observation Jacobians are computed from them)"; return DOJO_ERR_INVALID; }
-    if ((((uintptr_t)a.DZ) | (uintptr_t)a.DU) & 15) { g_err = w_ + "DZ and DU must be 16-byte aligned (the kernel reads them in 16-byte pieces)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_sweep(who, H, {{!a.DZ || !a.OBS || !a.G, "DZ, OBS and G must not be NULL"}, {!a.DU, "gU, gtheta and gz need DU"},
+                              {p.n_layers > 1 && !a.ACT, "ACT is required with n_layers > 1 (the recorded activations)"}}, a.cot_space, a.Z,
+                     {{!a.M && (!a.z0 || !a.Z), "M = NULL needs z0 and Z (the observation Jacobians are computed from them)"}}, a.DZ, a.DU, "DZ and DU"));
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the record)
     if (!a.gtheta && !a.gU && !a.gz) return DOJO_OK;
-    const size_t B = s->B, nobs = 2 * s->M.nu;
     const double* M = a.M;
-    if (!M) {
-        const long long n = (long long)H + (a.G_obs ? 1 : 0);
-        TRY(ensure_at_least(s, &s->d_pM, &s->pM_bytes, ((size_t)H + 1) * B * nobs * 24 * sizeof(double)));
-        TRY(launch_observation_jacobian(s, a.z0, a.Z, n, (double*)s->d_pM, st));
-        M = (const double*)s->d_pM;
-    }
-    TRY(ensure_at_least(s, (void**)&s->d_macc, &s->macc_bytes, B * (size_t)sh.P * sizeof(double)));
+    if (!M) TRY(observation_jacobians(s, H, a.z0, a.Z, a.G_obs != nullptr, st, &M));
+    TRY(ensure_macc(s, (size_t)sh.P));
     return s->dtype == DOJO_DTYPE_F32 ? launch_mlp_adjoint<float>(s, p, sh, H, a, M, s->d_macc, st) : launch_mlp_adjoint<double>(s, p, sh, H, a, M, s->d_macc, st);
 }
 
@@ -2017,58 +1997,45 @@ int dojo_rollout_mlp_gradients(DojoHandle s, const void* z0, const DojoMlpPolicy
     TRY(refuse_record(s, who));
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B, ng = cot_space ? nz : nx;
-    const size_t Bw = policy->per_env ? B : 1, nobs = 2 * nu, P = (size_t)c.shape.P, nh = (size_t)c.shape.nh;
-    const size_t record = HB * nx * (nx + nu) * w, mbytes = (HB + B) * nobs * 24 * sizeof(double), abytes = HB * nh * sizeof(double), wsbytes = B * P * sizeof(double);
-    auto up = [](size_t n) { return (std::max<size_t>(n, 8) + 4095) / 4096 * 4096; };
-    size_t need = up(B * nz * w) + up(HB * ng * w) + up(HB * nz * w) + up(HB * sizeof(int)) + up(HB * nx * nx * w) + up(HB * nx * nu * w) + 3 * up(HB * nu * w) + up(B * nx * w)
-                  + 2 * up((HB + B) * nobs * w) + 2 * up(Bw * P * w) + 2 * up(nobs * w) + (policy->U_ff ? up(HB * nu * w) : 0)
-                  + ((s->d_pM && s->pM_bytes >= mbytes) ? 0 : up(mbytes)) + (nh ? up(abytes) : 0) + ((s->d_macc && s->macc_bytes >= wsbytes) ? 0 : up(wsbytes));
-    need += record_workspaces(s);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b) {
-        g_err = w_ + "the record of " + std::to_string(record) + " bytes, the observation Jacobians of " + std::to_string(mbytes) + " bytes, the activations of " + std::to_string(abytes)
-                + " bytes and the accumulators of " + std::to_string(wsbytes) + " bytes (" + std::to_string(need) + " bytes with the other buffers of the call) do not fit into the "
-                + std::to_string(free_b) + " bytes of free device memory";
-        return DOJO_ERR_INVALID;
+    const size_t Bw = policy->per_env ? B : 1, nobs = 2 * nu, P = (size_t)c.shape.P, abytes = HB * (size_t)c.shape.nh * sizeof(double);
+    Staging st;
+    const auto &dz0 = st.input(B * nz * w, z0), &dth = st.input(Bw * P * w, policy->theta);
+    const auto &dm = st.input(nobs * w, policy->mean), &dsc = st.input(nobs * w, policy->scale), &dUff = st.input(HB * nu * w, policy->U_ff);
+    const auto &dG = st.input(HB * ng * w, G), &dGu = st.input(HB * nu * w, G_u), &dGo = st.input((HB + B) * nobs * w, G_obs);
+    const auto &dZ = st.kept(HB * nz * w, Z), &dO = st.kept((HB + B) * nobs * w, OBS), &dU = st.kept(HB * nu * w, U_out), &dS = st.kept(HB * sizeof(int), status);
+    const auto &dA = st.kept(abytes, nullptr, abytes != 0);      // (a single layer has no activations)
+    const auto &dDZ = st.kept(HB * nx * nx * w), &dDU = st.kept(HB * nx * nu * w);
+    const auto &dgth = st.kept(Bw * P * w, gtheta), &dgU = st.kept(HB * nu * w, gU), &dgz = st.kept(B * nx * w, gz);
+    {
+        Measuring handle(s);
+        TRY(ensure_record(s)); TRY(ensure_pM(s, (size_t)H)); TRY(ensure_macc(s, P));
+        TRY(refuse_memory(w_ + "the record of " + std::to_string(HB * nx * (nx + nu) * w) + " bytes, the observation Jacobians of " + std::to_string(pM_size(s, (size_t)H)) + " bytes, the activations of "
+                          + std::to_string(abytes) + " bytes and the accumulators of " + std::to_string(macc_size(s, P)) + " bytes (", st, handle, "do"));
     }
-    DojoMlpPolicy p = *policy;
-    DevBuf dz0, dth, dm, dsc, dUff, dG, dGu, dGo, dZ, dO, dU, dS, dA, dDZ, dDU, dgth, dgU, dgz;
-    auto upl = [&](DevBuf& d, const void* src, size_t bytes, const void** dst) -> int {
-        *dst = nullptr;
-        if (!src) return DOJO_OK;
-        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
-        *dst = d.p;
-        return DOJO_OK;
-    };
+    TRY(st.allocate());
+    DojoMlpPolicy p = *policy; p.theta = dth.p; p.mean = dm.p; p.scale = dsc.p; p.U_ff = dUff.p;
+    c.mlp = &p; c.ACT = (double*)dA.p;
+    RolloutIO io; io.z0 = dz0.p; io.U = p.U_ff; io.Z = dZ.p; io.status = (int32_t*)dS.p; io.DZ = dDZ.p; io.DU = dDU.p; io.controller = &c; io.OBS = dO.p; io.U_out = dU.p;
+    TRY(rollout_core(s, H, io, nullptr));
     DojoMlpAdjoint a{};
-    const void* z0d = nullptr;
-    TRY(upl(dz0, z0, B * nz * w, &z0d)); TRY(upl(dth, policy->theta, Bw * P * w, &p.theta));
-    TRY(upl(dm, policy->mean, nobs * w, &p.mean)); TRY(upl(dsc, policy->scale, nobs * w, &p.scale)); TRY(upl(dUff, policy->U_ff, HB * nu * w, &p.U_ff));
-    TRY(upl(dG, G, HB * ng * w, &a.G)); TRY(upl(dGu, G_u, HB * nu * w, &a.G_u)); TRY(upl(dGo, G_obs, (HB + B) * nobs * w, &a.G_obs));
-    HIPCHK(dZ.alloc(HB * nz * w)); HIPCHK(dO.alloc((HB + B) * nobs * w)); HIPCHK(dU.alloc(HB * nu * w)); HIPCHK(dS.alloc(HB * sizeof(int)));
-    if (nh) HIPCHK(dA.alloc(abytes));
-    HIPCHK(dDZ.alloc(HB * nx * nx * w)); HIPCHK(dDU.alloc(HB * nx * nu * w));
-    HIPCHK(dgth.alloc(Bw * P * w)); HIPCHK(dgU.alloc(HB * nu * w)); HIPCHK(dgz.alloc(B * nx * w));
-    c.mlp = &p; c.ACT = nh ? (double*)dA.p : nullptr;
-    TRY(rollout_core(s, z0d, p.U_ff, H, dZ.p, (int32_t*)dS.p, nullptr, nullptr, dDZ.p, dDU.p, &c, dO.p, dU.p));
-    a.DZ = dDZ.p; a.DU = dDU.p; a.OBS = dO.p; a.ACT = c.ACT; a.status = (const int32_t*)dS.p; a.z0 = z0d; a.Z = dZ.p; a.M = nullptr; a.cot_space = cot_space;
+    a.G = dG.p; a.G_u = dGu.p; a.G_obs = dGo.p; a.DZ = dDZ.p; a.DU = dDU.p; a.OBS = dO.p; a.ACT = c.ACT; a.status = (const int32_t*)dS.p; a.z0 = dz0.p; a.Z = dZ.p; a.M = nullptr; a.cot_space = cot_space;
     a.gtheta = dgth.p; a.gU = dgU.p; a.gz = dgz.p;
     TRY(dojo_rollout_mlp_adjoint_dev(s, &p, H, &a, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, HB * nz * w, hipMemcpyDeviceToHost));
-    if (OBS) HIPCHK(hipMemcpy(OBS, dO.p, (HB + B) * nobs * w, hipMemcpyDeviceToHost));
-    if (U_out) HIPCHK(hipMemcpy(U_out, dU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dS.p, HB * sizeof(int), hipMemcpyDeviceToHost));
-    if (gtheta) HIPCHK(hipMemcpy(gtheta, dgth.p, Bw * P * w, hipMemcpyDeviceToHost));
-    if (gU) HIPCHK(hipMemcpy(gU, dgU.p, HB * nu * w, hipMemcpyDeviceToHost));
-    if (gz) HIPCHK(hipMemcpy(gz, dgz.p, B * nx * w, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
-    return DOJO_OK;
+    return st.finish(s, dZ, H);
 }
 
-static int rollout_host(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, void* storage, int32_t* status);
+static int rollout_host(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, void* storage, int32_t* status) {
+    if (!s || !z0 || H < 1) { g_err = "dojo_rollout: bad argument"; return DOJO_ERR_INVALID; }
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu, HB = (size_t)H * B;
+    Staging st;
+    const auto &dSt = st.output(HB * 25 * s->M.Nb * w, storage), &dz0 = st.input(B * nz * w, z0), &dU = st.input(HB * nu * w, nu ? U : nullptr);
+    const auto &dZ = st.output(HB * nz * w, Z), &dS = st.output(HB * sizeof(int), status);
+    TRY(st.allocate());
+    RolloutIO io; io.z0 = dz0.p; io.U = dU.p; io.Z = dZ.p; io.status = (int32_t*)dS.p; io.storage = dSt.p;
+    TRY(rollout_core(s, H, io, nullptr));
+    return st.finish(s, dZ, H);
+}
 
 int dojo_rollout(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, int32_t* status) {
     Enter enter_(s);
@@ -2079,28 +2046,6 @@ int dojo_simulate(DojoHandle s, const void* z0, const void* U, int32_t H, void* 
     Enter enter_(s);
     if (!storage) { g_err = "dojo_simulate: storage must not be NULL (use dojo_rollout for record = false)"; return DOJO_ERR_INVALID; }
     return rollout_host(s, z0, U, H, Z, storage, status);
-}
-
-static int rollout_host(DojoHandle s, const void* z0, const void* U, int32_t H, void* Z, void* storage, int32_t* status) {
-    if (!s || !z0 || H < 1) { g_err = "dojo_rollout: bad argument"; return DOJO_ERR_INVALID; }
-    HIPCHK(hipSetDevice(s->device));
-    size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nu = s->M.nu;
-    DevBuf dz0, dU, dZ, dSt, dS;
-    const size_t nst = (size_t)H * B * 25 * s->M.Nb * w;
-    if (storage) HIPCHK(dSt.alloc(nst));
-    HIPCHK(dz0.alloc(B * nz * w));
-    HIPCHK(hipMemcpy(dz0.p, z0, B * nz * w, hipMemcpyHostToDevice));
-    if (U && nu) { HIPCHK(dU.alloc((size_t)H * B * nu * w)); HIPCHK(hipMemcpy(dU.p, U, (size_t)H * B * nu * w, hipMemcpyHostToDevice)); }
-    if (Z) HIPCHK(dZ.alloc((size_t)H * B * nz * w));
-    if (status) HIPCHK(dS.alloc((size_t)H * B * sizeof(int)));
-    int rc = rollout_core(s, dz0.p, dU.p, H, dZ.p, (int32_t*)dS.p, dSt.p, nullptr);
-    if (rc != DOJO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    if (storage) HIPCHK(hipMemcpy(storage, dSt.p, nst, hipMemcpyDeviceToHost));
-    if (Z) HIPCHK(hipMemcpy(Z, dZ.p, (size_t)H * B * nz * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, dS.p, (size_t)H * B * sizeof(int), hipMemcpyDeviceToHost));
-    if (Z) HIPCHK(hipMemcpy(s->d_zn, (char*)dZ.p + (size_t)(H - 1) * B * nz * w, B * nz * w, hipMemcpyDeviceToDevice));
-    return DOJO_OK;
 }
 
 int dojo_get_state(DojoHandle s, void* z) {

@@ -43,24 +43,61 @@ def lift_tangent(gz, z0):
     return torch.cat([g[..., 0:6], gq, g[..., 9:12]], -1).reshape(B, -1).to(z0.dtype)
 
 
+def _addr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _dtype(mech):
+    return torch.float32 if mech.dtype_code == 1 else torch.float64
+
+
+def _want(t, what, dt, shapes, shown=None):
+    """None, or the device tensor t of dtype dt and one of `shapes`, contiguous (shown: how the message writes the shape)"""
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != dt or tuple(t.shape) not in shapes:
+        raise ValueError("%s must be a %s device tensor of shape %s" % (what, dt, shown or " or ".join(str(x) for x in shapes)))
+    return t.contiguous()
+
+
+def _horizon(U, what, steps, dt, B, nu, shown=None):
+    """-> (H, U contiguous): the horizon is the leading dimension of the controls [H,B,nu], or `steps` without them"""
+    if U is None:
+        return int(steps), None
+    H = int(U.shape[0]) if U.dim() else 0
+    return H, _want(U, what, dt, [(H, B, nu)], shown)
+
+
+def _controls(mech, U, steps):
+    """-> (H, U contiguous) of an open-loop rollout (a mechanism without inputs takes no controls)"""
+    s, B = mech.spec, mech.batch
+    return _horizon(U if s.nu else None, "U", steps, _dtype(mech), B, s.nu, "(H, %d, %d)" % (B, s.nu))
+
+
+def _record(mech, H, dev, closed_loop=False):
+    """-> Z, status, DZ, DU (and OBS, U of a closed loop): the tensors a recording rollout writes; the Jacobians are freed with the graph"""
+    s, B, dt = mech.spec, mech.batch, _dtype(mech)
+    Z = torch.empty((H, B, s.nz), dtype=dt, device=dev)
+    status = torch.empty((H, B), dtype=torch.int32, device=dev)
+    DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)
+    DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev) if (s.nu or closed_loop) else None
+    if not closed_loop:
+        return Z, status, DZ, DU
+    return Z, status, DZ, DU, torch.empty((H + 1, B, 2 * s.nu), dtype=dt, device=dev), torch.empty((H, B, s.nu), dtype=dt, device=dev)
+
+
+def _cotangents(Z, gZ, *optional):
+    """the incoming cotangents, contiguous; one torch leaves out is a zero: the state's is required by the ABI, the others are optional (None)"""
+    return (torch.zeros_like(Z) if gZ is None else gZ.contiguous(),) + tuple(None if g is None else g.contiguous() for g in optional)
+
+
 class _Rollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mech, z0, U, steps):
-        s, B = mech.spec, mech.batch
-        dt = torch.float32 if mech.dtype_code == 1 else torch.float64
-        if not z0.is_cuda or z0.dtype != dt or tuple(z0.shape) != (B, s.nz):
-            raise ValueError("z0 must be a %s device tensor of shape %s" % (dt, (B, s.nz)))
-        if U is not None and s.nu:
-            if not U.is_cuda or U.dtype != dt or U.dim() != 3 or tuple(U.shape[1:]) != (B, s.nu):
-                raise ValueError("U must be a %s device tensor of shape (H, %d, %d)" % (dt, B, s.nu))
-            H = int(U.shape[0]); Uc = U.contiguous()
-        else:
-            H = int(steps); Uc = None
-        dev = z0.device; z0c = z0.contiguous()
-        Z = torch.empty((H, B, s.nz), dtype=dt, device=dev)
-        status = torch.empty((H, B), dtype=torch.int32, device=dev)
-        DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)          # the record: freed with the graph
-        DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev) if s.nu else None
+        z0c = _want(z0, "z0", _dtype(mech), [(mech.batch, mech.spec.nz)])
+        H, Uc = _controls(mech, U, steps)
+        dev = z0.device
+        Z, status, DZ, DU = _record(mech, H, dev)
         api._chk(api.lib().dojo_rollout_record_dev(mech.h, _ptr(z0c), _ptr(Uc), H, _ptr(Z), _ptr(status), _ptr(DZ), _ptr(DU), _stream(dev)))
         ctx.mech, ctx.H, ctx.has_u = mech, H, U is not None
         ctx.save_for_backward(z0c, Z, status, DZ, *([DU] if DU is not None else []))
@@ -73,7 +110,7 @@ class _Rollout(torch.autograd.Function):
         s, B = mech.spec, mech.batch
         z0, Z, status, DZ = ctx.saved_tensors[:4]
         DU = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
-        gZ = gZ.contiguous()
+        gZ, = _cotangents(Z, gZ)
         want_u = ctx.has_u and s.nu > 0 and ctx.needs_input_grad[2]
         gU = torch.empty((H, B, s.nu), dtype=Z.dtype, device=Z.device) if want_u else None
         gz = torch.empty((B, s.nx), dtype=Z.dtype, device=Z.device) if ctx.needs_input_grad[1] else None
@@ -97,25 +134,15 @@ def differentiable_rollout(mech, z0, U=None, steps=None):
 class _DataRollout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mech, z0, U, theta, steps):
-        s, B = mech.spec, mech.batch
+        s, B, dt = mech.spec, mech.batch, _dtype(mech)
         Nc = len(s.contacts)
-        dt = torch.float32 if mech.dtype_code == 1 else torch.float64
-        if not z0.is_cuda or z0.dtype != dt or tuple(z0.shape) != (B, s.nz):
-            raise ValueError("z0 must be a %s device tensor of shape %s" % (dt, (B, s.nz)))
+        z0c = _want(z0, "z0", dt, [(B, s.nz)])
         if theta is None or theta.dtype != torch.float64 or tuple(theta.shape) != (Nc, 5):
             raise ValueError("theta must be a float64 tensor of shape %s" % ((Nc, 5),))
-        if U is not None and s.nu:
-            if not U.is_cuda or U.dtype != dt or U.dim() != 3 or tuple(U.shape[1:]) != (B, s.nu):
-                raise ValueError("U must be a %s device tensor of shape (H, %d, %d)" % (dt, B, s.nu))
-            H = int(U.shape[0]); Uc = U.contiguous()
-        else:
-            H = int(steps); Uc = None
+        H, Uc = _controls(mech, U, steps)
         mech.set_contact_data(theta.detach().cpu().numpy())      # (waits for the handle's work in flight: the table is mechanism data)
-        dev = z0.device; z0c = z0.contiguous()
-        Z = torch.empty((H, B, s.nz), dtype=dt, device=dev)
-        status = torch.empty((H, B), dtype=torch.int32, device=dev)
-        DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)          # the record: freed with the graph
-        DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev) if s.nu else None
+        dev = z0.device
+        Z, status, DZ, DU = _record(mech, H, dev)
         DC = torch.empty((H, B, 5 * Nc, s.nx), dtype=dt, device=dev) if Nc else None
         api._chk(api.lib().dojo_rollout_data_record_dev(mech.h, _ptr(z0c), _ptr(Uc), H, _ptr(Z), _ptr(status), _ptr(DZ), _ptr(DU), _ptr(DC), _stream(dev)))
         ctx.mech, ctx.H, ctx.has_u, ctx.theta_device, ctx.layout = mech, H, U is not None, theta.device, (DU is not None, DC is not None)
@@ -132,7 +159,7 @@ class _DataRollout(torch.autograd.Function):
         rest = list(ctx.saved_tensors[4:])
         DU = rest.pop(0) if ctx.layout[0] else None
         DC = rest.pop(0) if ctx.layout[1] else None
-        gZ = gZ.contiguous()
+        gZ, = _cotangents(Z, gZ)
         need = ctx.needs_input_grad                    # (mech, z0, U, theta, steps)
         want_u = ctx.has_u and s.nu > 0 and need[2]
         gU = torch.empty((H, B, s.nu), dtype=Z.dtype, device=Z.device) if want_u else None
@@ -159,69 +186,92 @@ def differentiable_data_rollout(mech, z0, U, theta, steps=None):
     return Z
 
 
-class _PolicyRollout(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mech, z0, W, bias, U_ff, steps, mean, scale, act_off):
-        s, B = mech.spec, mech.batch
-        dt = torch.float32 if mech.dtype_code == 1 else torch.float64
-        nobs = 2 * s.nu
+# The two policies of a closed-loop rollout, as _ClosedLoopRollout sees them: how the parameter tensors are checked, the policy struct of the ABI, and the
+# recording and sweeping entries (nh: the hidden units whose activations are recorded, None = the entries have no ACT)
+class _Affine:
+    nh = None
 
-        def want(t, what, shapes):
-            if t is None:
-                return None
-            if not t.is_cuda or t.dtype != dt or tuple(t.shape) not in shapes:
-                raise ValueError("%s must be a %s device tensor of shape %s" % (what, dt, " or ".join(str(x) for x in shapes)))
-            return t.contiguous()
-        z0c = want(z0, "z0", [(B, s.nz)])
+    def check(self, params, dt, B, nobs):
+        W, bias = params
         if W is None or W.dim() not in (2, 3):
             raise ValueError("W must be [na, nobs] or [B, na, nobs]")
-        per_env = W.dim() == 3
-        na = int(W.shape[-2])
-        Wc = want(W, "W", [(B, na, nobs) if per_env else (na, nobs)])
-        bc = want(bias, "bias", [(B, na) if per_env else (na,)])
-        mc, sc = want(mean, "mean", [(nobs,)]), want(scale, "scale", [(nobs,)])
-        if U_ff is not None:
-            H = int(U_ff.shape[0]); Uc = want(U_ff, "U_ff", [(H, B, s.nu)])
-        else:
-            H = int(steps); Uc = None
+        self.per_env, self.na = W.dim() == 3, int(W.shape[-2])
+        lead = (B,) if self.per_env else ()
+        return _want(W, "W", dt, [lead + (self.na, nobs)]), _want(bias, "bias", dt, [lead + (self.na,)])
+
+    def struct(self, W, mean, scale, U_ff, act_off, bias=None):
+        return api.DojoPolicy(_addr(W), _addr(bias), _addr(mean), _addr(scale), _addr(U_ff), int(self.per_env), int(act_off), self.na, 0, 0, 0)
+
+    def record(self, h, z0, pol, H, Z, OBS, U, ACT, *rest):
+        return api.lib().dojo_rollout_policy_record_dev(h, z0, pol, H, Z, OBS, U, *rest)
+
+    def sweep(self, h, pol, H, DZ, DU, OBS, ACT, rest, stream):
+        a = api.DojoPolicyAdjoint(DZ, DU, OBS, *rest, 1, 0)
+        return api.lib().dojo_rollout_policy_adjoint_dev(h, pol, H, C.byref(a), stream)
+
+
+class _Mlp:
+    def __init__(self, widths):
+        self.widths = [int(n) for n in widths]
+        self.P, self.nh = api.mlp_sizes(self.widths)
+
+    def check(self, params, dt, B, nobs):
+        theta, = params
+        if theta is None or theta.dim() not in (1, 2):
+            raise ValueError("theta must be [P] or [B, P]")
+        self.per_env = theta.dim() == 2
+        return _want(theta, "theta", dt, [(B, self.P) if self.per_env else (self.P,)]),
+
+    def struct(self, theta, mean, scale, U_ff, act_off):
+        return api.mlp_policy_struct(_addr(theta), _addr(mean), _addr(scale), _addr(U_ff), self.per_env, act_off, self.widths)
+
+    def record(self, h, z0, pol, H, Z, OBS, U, ACT, *rest):
+        return api.lib().dojo_rollout_mlp_record_dev(h, z0, pol, H, Z, OBS, U, ACT, *rest)
+
+    def sweep(self, h, pol, H, DZ, DU, OBS, ACT, rest, stream):
+        a = api.DojoMlpAdjoint(DZ, DU, OBS, ACT, *rest, 1, 0)
+        return api.lib().dojo_rollout_mlp_adjoint_dev(h, pol, H, C.byref(a), stream)
+
+
+class _ClosedLoopRollout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mech, policy, z0, U_ff, steps, mean, scale, act_off, *params):
+        s, B, dt = mech.spec, mech.batch, _dtype(mech)
+        nobs = 2 * s.nu
+        z0c = _want(z0, "z0", dt, [(B, s.nz)])
+        params = policy.check(params, dt, B, nobs)
+        mc, sc = _want(mean, "mean", dt, [(nobs,)]), _want(scale, "scale", dt, [(nobs,)])
+        H, Uc = _horizon(U_ff, "U_ff", steps, dt, B, s.nu)
         dev = z0.device
-        Z = torch.empty((H, B, s.nz), dtype=dt, device=dev); OBS = torch.empty((H + 1, B, nobs), dtype=dt, device=dev)
-        U = torch.empty((H, B, s.nu), dtype=dt, device=dev); status = torch.empty((H, B), dtype=torch.int32, device=dev)
-        DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)          # the record: freed with the graph
-        DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev)
-        p = lambda t: None if t is None else t.data_ptr()
-        pol = api.DojoPolicy(p(Wc), p(bc), p(mc), p(sc), p(Uc), int(per_env), int(act_off), na, 0, 0, 0)
-        api._chk(api.lib().dojo_rollout_policy_record_dev(mech.h, _ptr(z0c), C.byref(pol), H, _ptr(Z), _ptr(OBS), _ptr(U), _ptr(status), _ptr(DZ), _ptr(DU),
-                                                          _stream(dev)))
-        ctx.mech, ctx.H, ctx.per_env, ctx.na, ctx.act_off = mech, H, per_env, na, int(act_off)
-        ctx.has = (bias is not None, U_ff is not None, mean is not None, scale is not None)
-        ctx.save_for_backward(z0c, Wc, Z, OBS, status, DZ, DU, *[t for t in (mc, sc) if t is not None])
+        Z, status, DZ, DU, OBS, U = _record(mech, H, dev, closed_loop=True)
+        ACT = None if policy.nh is None else torch.empty((H, B, policy.nh), dtype=torch.float64, device=dev)
+        pol = policy.struct(params[0], mc, sc, Uc, act_off, *params[1:])
+        api._chk(policy.record(mech.h, _ptr(z0c), C.byref(pol), H, _ptr(Z), _ptr(OBS), _ptr(U), _ptr(ACT), _ptr(status), _ptr(DZ), _ptr(DU), _stream(dev)))
+        ctx.mech, ctx.policy, ctx.H, ctx.act_off, ctx.has_uff = mech, policy, H, int(act_off), U_ff is not None
+        optional = (ACT, mc, sc) + tuple(params[1:])
+        ctx.has = [t is not None for t in optional]
+        ctx.save_for_backward(z0c, params[0], Z, OBS, status, DZ, DU, *[t for t in optional if t is not None])
         ctx.mark_non_differentiable(status)
         return Z, OBS, U, status
 
     @staticmethod
     def backward(ctx, gZ, gOBS, gU_out, _gstatus):
-        mech, H = ctx.mech, ctx.H
+        mech, policy, H = ctx.mech, ctx.policy, ctx.H
         s, B = mech.spec, mech.batch
-        z0, W, Z, OBS, status, DZ, DU = ctx.saved_tensors[:7]
+        z0, theta, Z, OBS, status, DZ, DU = ctx.saved_tensors[:7]
         rest = list(ctx.saved_tensors[7:])
-        mean = rest.pop(0) if ctx.has[2] else None
-        scale = rest.pop(0) if ctx.has[3] else None
-        dt, dev, nobs = Z.dtype, Z.device, 2 * s.nu
-        # (a cotangent torch leaves out is a zero: the state's is required by the ABI, the other two are optional)
-        gZ = torch.zeros_like(Z) if gZ is None else gZ.contiguous()
-        gOBS = None if gOBS is None else gOBS.contiguous()
-        gU_out = None if gU_out is None else gU_out.contiguous()
-        need = ctx.needs_input_grad                    # (mech, z0, W, bias, U_ff, steps, mean, scale, act_off)
-        gW = torch.empty_like(W) if need[2] else None
-        gb = torch.empty((B, ctx.na) if ctx.per_env else (ctx.na,), dtype=dt, device=dev) if (ctx.has[0] and need[3]) else None
-        gU = torch.empty((H, B, s.nu), dtype=dt, device=dev) if (ctx.has[1] and need[4]) else None
-        gz = torch.empty((B, s.nx), dtype=dt, device=dev) if need[1] else None
-        p = lambda t: None if t is None else t.data_ptr()
-        pol = api.DojoPolicy(p(W), None, p(mean), p(scale), None, int(ctx.per_env), ctx.act_off, ctx.na, 0, 0, 0)
-        a = api.DojoPolicyAdjoint(p(DZ), p(DU), p(OBS), p(status), p(z0), p(Z), None, p(gZ), p(gU_out), p(gOBS), p(gW), p(gb), p(gU), p(gz), 1, 0)
-        api._chk(api.lib().dojo_rollout_policy_adjoint_dev(mech.h, C.byref(pol), H, C.byref(a), _stream(dev)))
-        return None, (lift_tangent(gz, z0) if gz is not None else None), gW, gb, gU, None, None, None, None
+        ACT, mean, scale, *others = [rest.pop(0) if has else None for has in ctx.has]
+        dt, dev = Z.dtype, Z.device
+        gZ, gOBS, gU_out = _cotangents(Z, gZ, gOBS, gU_out)
+        need = ctx.needs_input_grad                    # (mech, policy, z0, U_ff, steps, mean, scale, act_off, *params)
+        gparams = [torch.empty_like(t) if (t is not None and n) else None for t, n in zip([theta] + others, need[8:])]
+        gU = torch.empty((H, B, s.nu), dtype=dt, device=dev) if (ctx.has_uff and need[3]) else None
+        gz = torch.empty((B, s.nx), dtype=dt, device=dev) if need[2] else None
+        pol = policy.struct(theta, mean, scale, None, ctx.act_off)
+        record = [_addr(status), _addr(z0), _addr(Z), None, _addr(gZ), _addr(gU_out), _addr(gOBS)]      # .., M = None: computed from z0 and Z
+        api._chk(policy.sweep(mech.h, C.byref(pol), H, _addr(DZ), _addr(DU), _addr(OBS), _addr(ACT) if ACT is not None and ACT.numel() else None,
+                              record + [_addr(g) for g in gparams + [gU, gz]], _stream(dev)))
+        return (None, None, (lift_tangent(gz, z0) if gz is not None else None), gU, None, None, None, None) + tuple(gparams)
 
 
 def differentiable_policy_rollout(mech, z0, W, bias=None, U_ff=None, steps=None, mean=None, scale=None, act_off=0):
@@ -230,73 +280,9 @@ def differentiable_policy_rollout(mech, z0, W, bias=None, U_ff=None, steps=None,
     torch-owned tensors; backward: ONE dojo_rollout_policy_adjoint_dev call with the cotangents of all three outputs.  Gradients flow to z0 (lifted
     to state shape as in differentiable_rollout), W, bias and U_ff; mean and scale are frozen.  A shared W receives the sum over the batch.
     Z.status [H,B] (int32, non-differentiable) is the solver status of every step; nothing flows through a failed step's Jacobians."""
-    Z, OBS, U, status = _PolicyRollout.apply(mech, z0, W, bias, U_ff, steps, mean, scale, act_off)
+    Z, OBS, U, status = _ClosedLoopRollout.apply(mech, _Affine(), z0, U_ff, steps, mean, scale, act_off, W, bias)
     Z.status = status
     return Z, OBS, U
-
-
-class _MlpRollout(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mech, z0, theta, widths, U_ff, steps, mean, scale, act_off):
-        s, B = mech.spec, mech.batch
-        dt = torch.float32 if mech.dtype_code == 1 else torch.float64
-        nobs = 2 * s.nu
-        w = [int(n) for n in widths]
-        P, nh = api.mlp_sizes(w)
-
-        def want(t, what, shapes):
-            if t is None:
-                return None
-            if not t.is_cuda or t.dtype != dt or tuple(t.shape) not in shapes:
-                raise ValueError("%s must be a %s device tensor of shape %s" % (what, dt, " or ".join(str(x) for x in shapes)))
-            return t.contiguous()
-        z0c = want(z0, "z0", [(B, s.nz)])
-        if theta is None or theta.dim() not in (1, 2):
-            raise ValueError("theta must be [P] or [B, P]")
-        per_env = theta.dim() == 2
-        thc = want(theta, "theta", [(B, P) if per_env else (P,)])
-        mc, sc = want(mean, "mean", [(nobs,)]), want(scale, "scale", [(nobs,)])
-        if U_ff is not None:
-            H = int(U_ff.shape[0]); Uc = want(U_ff, "U_ff", [(H, B, s.nu)])
-        else:
-            H = int(steps); Uc = None
-        dev = z0.device
-        Z = torch.empty((H, B, s.nz), dtype=dt, device=dev); OBS = torch.empty((H + 1, B, nobs), dtype=dt, device=dev)
-        U = torch.empty((H, B, s.nu), dtype=dt, device=dev); status = torch.empty((H, B), dtype=torch.int32, device=dev)
-        ACT = torch.empty((H, B, nh), dtype=torch.float64, device=dev)      # the record: freed with the graph
-        DZ = torch.empty((H, B, s.nx, s.nx), dtype=dt, device=dev)
-        DU = torch.empty((H, B, s.nu, s.nx), dtype=dt, device=dev)
-        p = lambda t: None if t is None else t.data_ptr()
-        pol = api.mlp_policy_struct(p(thc), p(mc), p(sc), p(Uc), per_env, act_off, w)
-        api._chk(api.lib().dojo_rollout_mlp_record_dev(mech.h, _ptr(z0c), C.byref(pol), H, _ptr(Z), _ptr(OBS), _ptr(U), _ptr(ACT), _ptr(status), _ptr(DZ), _ptr(DU),
-                                                       _stream(dev)))
-        ctx.mech, ctx.H, ctx.per_env, ctx.widths, ctx.act_off = mech, H, per_env, w, int(act_off)
-        ctx.has = (U_ff is not None, mean is not None, scale is not None)
-        ctx.save_for_backward(z0c, thc, Z, OBS, status, DZ, DU, ACT, *[t for t in (mc, sc) if t is not None])
-        ctx.mark_non_differentiable(status)
-        return Z, OBS, U, status
-
-    @staticmethod
-    def backward(ctx, gZ, gOBS, gU_out, _gstatus):
-        mech, H = ctx.mech, ctx.H
-        s, B = mech.spec, mech.batch
-        z0, theta, Z, OBS, status, DZ, DU, ACT = ctx.saved_tensors[:8]
-        rest = list(ctx.saved_tensors[8:])
-        mean = rest.pop(0) if ctx.has[1] else None
-        scale = rest.pop(0) if ctx.has[2] else None
-        dt, dev = Z.dtype, Z.device
-        gZ = torch.zeros_like(Z) if gZ is None else gZ.contiguous()
-        gOBS = None if gOBS is None else gOBS.contiguous()
-        gU_out = None if gU_out is None else gU_out.contiguous()
-        need = ctx.needs_input_grad                    # (mech, z0, theta, widths, U_ff, steps, mean, scale, act_off)
-        gth = torch.empty_like(theta) if need[2] else None
-        gU = torch.empty((H, B, s.nu), dtype=dt, device=dev) if (ctx.has[0] and need[4]) else None
-        gz = torch.empty((B, s.nx), dtype=dt, device=dev) if need[1] else None
-        p = lambda t: None if t is None else t.data_ptr()
-        pol = api.mlp_policy_struct(p(theta), p(mean), p(scale), None, ctx.per_env, ctx.act_off, ctx.widths)
-        a = api.DojoMlpAdjoint(p(DZ), p(DU), p(OBS), p(ACT) if ACT.numel() else None, p(status), p(z0), p(Z), None, p(gZ), p(gU_out), p(gOBS), p(gth), p(gU), p(gz), 1, 0)
-        api._chk(api.lib().dojo_rollout_mlp_adjoint_dev(mech.h, C.byref(pol), H, C.byref(a), _stream(dev)))
-        return None, (lift_tangent(gz, z0) if gz is not None else None), gth, None, gU, None, None, None, None
 
 
 def differentiable_mlp_rollout(mech, z0, theta, widths, U_ff=None, steps=None, mean=None, scale=None, act_off=0):
@@ -307,6 +293,6 @@ def differentiable_mlp_rollout(mech, z0, theta, widths, U_ff=None, steps=None, m
     dojo_rollout_mlp_adjoint_dev call with the cotangents of all three outputs.  Gradients flow to z0 (lifted to state shape as in
     differentiable_rollout), theta and U_ff; mean and scale are frozen.  A shared theta receives the sum over the batch.  Z.status [H,B] (int32,
     non-differentiable) is the solver status of every step; nothing flows through a failed step's Jacobians."""
-    Z, OBS, U, status = _MlpRollout.apply(mech, z0, theta, widths, U_ff, steps, mean, scale, act_off)
+    Z, OBS, U, status = _ClosedLoopRollout.apply(mech, _Mlp(widths), z0, U_ff, steps, mean, scale, act_off, theta)
     Z.status = status
     return Z, OBS, U

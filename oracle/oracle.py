@@ -22,9 +22,14 @@ def build(force=False, fast=False):
     name = "liboracle_fast.so" if fast else "liboracle.so"
     so = os.path.join(_HERE, name)
     srcs = [os.path.join(_HERE, f) for f in ("capi.cpp", "dojo_oracle.hpp", "oracle_math.hpp", "Makefile")]
-    if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs if os.path.exists(s)):
-        if all(os.path.exists(s) for s in srcs):
-            subprocess.check_call(["make", "-C", _HERE, name] + (["-B"] if force else []), stdout=subprocess.DEVNULL)
+    # once, whoever comes first (pytest-xdist workers race here, as in tests/emu_wrap.py): under a file lock, and the Makefile links into a
+    # temporary name that it renames into place, so that no process ever loads a half-written library
+    import fcntl
+    with open(so + ".lock", "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs if os.path.exists(s)):
+            if all(os.path.exists(s) for s in srcs):
+                subprocess.check_call(["make", "-C", _HERE, name] + (["-B"] if force else []), stdout=subprocess.DEVNULL)
     return so
 
 

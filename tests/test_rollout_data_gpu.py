@@ -593,3 +593,53 @@ def test_argument_errors():
         assert "dojo_rollout_data_gradients" in gl.last_error()
     finally:
         gl.close()
+
+
+# ---------------------------------------------------------------- the memory refusal of the four *_gradients host entries ----------------------------------------------------------------
+def _gradients_call(entry, gm, spec, H, z0, G, theta, status, gz):
+    """one raw call of a *_gradients host entry on host arrays: no controls, tangent-space cotangents, a shared policy on input 0 (theta: W, or the network's
+    parameters for the widths [2 nu, 3, 1]); of the outputs, status and gz alone are asked for"""
+    L, p, nobs = api.lib(), api._p, 2 * spec.nu
+    if entry == "dojo_rollout_gradients":
+        return L.dojo_rollout_gradients(gm.h, p(z0), None, H, p(G), 0, None, p(status), None, p(gz))
+    if entry == "dojo_rollout_data_gradients":
+        return L.dojo_rollout_data_gradients(gm.h, p(z0), None, H, p(G), 0, None, p(status), None, None, None, p(gz))
+    if entry == "dojo_rollout_policy_gradients":
+        pol = api.DojoPolicy(theta.ctypes.data, None, None, None, None, 0, 0, 1, 0, 0, 0)
+        return L.dojo_rollout_policy_gradients(gm.h, p(z0), C.byref(pol), H, p(G), 0, None, None, None, None, None, p(status), None, None, None, p(gz))
+    pol = api.mlp_policy_struct(theta.ctypes.data, None, None, None, 0, 0, [nobs, 3, 1])
+    return L.dojo_rollout_mlp_gradients(gm.h, p(z0), C.byref(pol), H, p(G), 0, None, None, None, None, None, p(status), None, None, p(gz))
+
+
+@pytest.mark.parametrize("entry", ["dojo_rollout_gradients", "dojo_rollout_data_gradients", "dojo_rollout_policy_gradients", "dojo_rollout_mlp_gradients"])
+def test_record_larger_than_the_device_is_refused(entry):
+    """A horizon whose record -- H B nx (nx + nu) scalars, plus 5 Nc columns for the data entry -- is at least twice the device's total memory: the entry
+    refuses with DOJO_ERR_INVALID before it reads, allocates or launches anything (the host arrays are one-element dummies), names itself, the record's byte
+    count and the free device memory; the same handle then completes the entry at H = 2.  H stays below 2^31 and the record below 2^50, so that no size of
+    the call (none exceeds the record) comes near 2^63."""
+    B, w = 3, 8
+    data = entry == "dojo_rollout_data_gradients"
+    spec = d.get_mechanism("sphere") if data else d.get_mechanism("cartpole")
+    nx, nu, Nc = spec.nx, spec.nu, len(spec.contacts)
+    assert Nc > 0 or not data
+    per_step = B * nx * (nx + nu + (5 * Nc if data else 0)) * w
+    total = torch.cuda.mem_get_info()[1]
+    H = -(-2 * total // per_step)
+    record = H * per_step
+    assert record >= 2 * total and H < 2 ** 31 and record < 2 ** 50
+    theta = np.zeros(2 * nu if entry == "dojo_rollout_policy_gradients" else api.mlp_sizes([2 * nu, 3, 1])[0])
+    gm = api.BatchedMechanism(spec, B, dtype="f64")
+    try:
+        one, gz1 = np.zeros(1), np.full(1, 77.0)
+        rc = _gradients_call(entry, gm, spec, H, one, one, theta[:1], None, gz1)
+        err = gm.last_error()
+        print(entry, "H", H, "record", record, "rc", rc, err)
+        assert rc == INVALID and entry in err and str(record) in err and "free device memory" in err, (rc, err)
+        assert gz1[0] == 77.0
+        z0 = floor_states(spec, B)[0] if data else d.synthetic_inputs(spec, B)[0]
+        status = np.full((2, B), -77, dtype=np.int32); gz = np.full((B, nx), np.nan)
+        rc = _gradients_call(entry, gm, spec, 2, z0, np.ones((2, B, nx)), theta, status, gz)
+        assert rc == 0, (rc, gm.last_error())
+        assert (status != -77).all() and np.isfinite(gz).all()
+    finally:
+        gm.close()
