@@ -110,13 +110,14 @@ def out_tensors(gm, H, per_env, na, fill=float("nan")):
     return {"gW": f((B, na, nobs) if per_env else (na, nobs)), "gbias": f((B, na) if per_env else (na,)), "gU": f((H, B, s.nu)), "gz": f((B, s.nx))}
 
 
-def sweep(gm, H, inp, per_env, act_off, na, cot_space=0):
-    """NumPy in, NumPy out (dict over OUTS); the outputs start as NaN so that an entry the kernels leave out shows"""
+def sweep(gm, H, inp, per_env, act_off, na, cot_space=0, outs=None):
+    """NumPy in, NumPy out (dict over OUTS); the outputs start as NaN so that an entry the kernels leave out shows.
+    outs: the caller's own device tensors instead (a missing key = NULL, and missing from the result)"""
     t = {k: _dev(v) for k, v in inp.items()}
-    t.update(out_tensors(gm, H, per_env, na))
+    t.update(out_tensors(gm, H, per_env, na) if outs is None else outs)
     api._chk(sweep_raw(gm, H, t, per_env, act_off, na, cot_space))
     torch.cuda.synchronize()
-    return {k: t[k].cpu().numpy() for k in OUTS}
+    return {k: t[k].cpu().numpy() for k in OUTS if t.get(k) is not None}
 
 
 def recursion(spec, inp, act_off, na, absolute=False):
@@ -169,11 +170,14 @@ def check(out, ref, abs_, H, n_step, f32, n_red=0, what=""):
     assert worst <= 0.0, "%s: error exceeds the bound by %.3e (max error %.3e, max |ref| %.3e)" % (what, worst, err.max(), np.abs(ref).max())
 
 
-def check_all(spec, out, inp, act_off, na, H, f32, per_env=True, extra=0):
+def check_all(spec, out, inp, act_off, na, H, f32, per_env=True, extra=0, abs_G=None):
+    """every output in `out` against the recursion on inp.  abs_G: what stands for |G| in the bound's recursion where G was pulled back from state
+    coordinates (the sum of the magnitudes of the terms of every entry, pull_back's second result)"""
     nx, nobs = spec.nx, 2 * spec.nu
-    ref, abs_ = recursion(spec, inp, act_off, na), recursion(spec, absolute(inp), act_off, na, absolute=True)
+    ainp = absolute(inp) if abs_G is None else dict(absolute(inp), G=abs_G)
+    ref, abs_ = recursion(spec, inp, act_off, na), recursion(spec, ainp, act_off, na, absolute=True)
     n_step = nx + nobs + na + 8 + extra
-    for k in OUTS:
+    for k in out:
         shared = (not per_env) and k in ("gW", "gbias")
         r, a = (ref[k].sum(0), abs_[k].sum(0)) if shared else (ref[k], abs_[k])
         check(out[k], r, a, H, n_step, f32, n_red=spec_batch(inp) if shared else 0, what=k)

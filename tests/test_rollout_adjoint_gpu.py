@@ -67,17 +67,21 @@ def adjoint_raw(gm, H, DZ, DU, G, cot_space=0, Z=None, status=None, gU=None, gz=
     return api.lib().dojo_rollout_adjoint_dev(gm.h, int(H), _ptr(DZ), _ptr(DU), _ptr(G), int(cot_space), _ptr(Z), _ptr(status), _ptr(gU), _ptr(gz), _stream())
 
 
-def adjoint(gm, DZ, DU, G, cot_space=0, Z=None, status=None):
-    """NumPy in, NumPy out: (gU [H,B,nu] or None, gz [B,nx]); the outputs start as NaN so that an entry the kernel leaves out shows"""
+def adjoint(gm, DZ, DU, G, cot_space=0, Z=None, status=None, outs=None):
+    """NumPy in, NumPy out: (gU [H,B,nu] or None, gz [B,nx]); the outputs start as NaN so that an entry the kernel leaves out shows.
+    outs: the caller's own device tensors {"gU": .., "gz": ..} instead (a missing key = NULL, returned as None); DU = None is then passed as NULL"""
     H, B = G.shape[:2]
     nx, nu = gm.spec.nx, gm.spec.nu
     tdt = torch.float32 if gm.dtype_code else torch.float64
-    gU = torch.full((H, B, nu), float("nan"), dtype=tdt, device="cuda") if nu else None
-    gz = torch.full((B, nx), float("nan"), dtype=tdt, device="cuda")
+    if outs is None:
+        gU = torch.full((H, B, nu), float("nan"), dtype=tdt, device="cuda") if nu else None
+        gz = torch.full((B, nx), float("nan"), dtype=tdt, device="cuda")
+    else:
+        gU, gz = (outs.get("gU") if nu else None), outs.get("gz")
     keep = [_dev(DZ), _dev(DU) if nu else None, _dev(G), _dev(Z), _dev(status)]
     api._chk(adjoint_raw(gm, H, keep[0], keep[1], keep[2], cot_space, keep[3], keep[4], gU, gz))
     torch.cuda.synchronize()
-    return (gU.cpu().numpy() if nu else None), gz.cpu().numpy()
+    return (None if gU is None else gU.cpu().numpy()), (None if gz is None else gz.cpu().numpy())
 
 
 def recursion(DZ, DU, G, status=None):

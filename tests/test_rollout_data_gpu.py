@@ -90,16 +90,15 @@ def data_adjoint_raw(gm, H, DZ, DC, G, cot_space=0, Z=None, status=None, gte=Non
     return api.lib().dojo_rollout_data_adjoint_dev(gm.h, int(H), _ptr(DZ), _ptr(DC), _ptr(G), int(cot_space), _ptr(Z), _ptr(status), _ptr(gte), _ptr(gt), _ptr(gz), _stream())
 
 
-def data_adjoint(gm, DZ, DC, G, cot_space=0, Z=None, status=None, want=("env", "sum", "gz")):
+def data_adjoint(gm, DZ, DC, G, cot_space=0, Z=None, status=None, want=("env", "sum", "gz"), outs=None):
     """NumPy in, NumPy out: (gtheta_env [B,nth], gtheta [nth], gz [B,nx]), None where not asked for; the outputs start as NaN so that an entry
-    the kernels leave out shows"""
+    the kernels leave out shows.  outs: the caller's own device tensors {"env": .., "sum": .., "gz": ..} for the outputs in `want` instead"""
     H, B = G.shape[:2]
     nx, nth = gm.spec.nx, _nth(gm)
     tdt = torch.float32 if gm.dtype_code else torch.float64
     nan = lambda *shape: torch.full(shape, float("nan"), dtype=tdt, device="cuda")
-    gte = nan(B, nth) if "env" in want else None
-    gt = nan(nth) if "sum" in want else None
-    gz = nan(B, nx) if "gz" in want else None
+    own = lambda k, *shape: None if k not in want else nan(*shape) if outs is None else outs[k]
+    gte, gt, gz = own("env", B, nth), own("sum", nth), own("gz", B, nx)
     keep = [_dev(DZ), _dev(DC), _dev(G), _dev(Z), _dev(status)]
     api._chk(data_adjoint_raw(gm, H, keep[0], keep[1], keep[2], cot_space, keep[3], keep[4], gte, gt, gz))
     torch.cuda.synchronize()

@@ -153,13 +153,14 @@ def mlp_out_tensors(gm, H, per_env, widths, fill_=float("nan")):
     return {"gtheta": f((B, Pn) if per_env else (Pn,)), "gU": f((H, B, s.nu)), "gz": f((B, s.nx))}
 
 
-def mlp_sweep(gm, H, inp, per_env, act_off, widths, cot_space=0):
-    """NumPy in, NumPy out (dict over OUTS); the outputs start as NaN so that an entry the kernels leave out shows"""
+def mlp_sweep(gm, H, inp, per_env, act_off, widths, cot_space=0, outs=None):
+    """NumPy in, NumPy out (dict over OUTS); the outputs start as NaN so that an entry the kernels leave out shows.
+    outs: the caller's own device tensors instead (a missing key = NULL, and missing from the result)"""
     t = {k: _dev(v) for k, v in inp.items() if v is not None}
-    t.update(mlp_out_tensors(gm, H, per_env, widths))
+    t.update(mlp_out_tensors(gm, H, per_env, widths) if outs is None else outs)
     api._chk(mlp_sweep_raw(gm, H, t, per_env, act_off, widths, cot_space))
     torch.cuda.synchronize()
-    return {k: t[k].cpu().numpy() for k in OUTS}
+    return {k: t[k].cpu().numpy() for k in OUTS if t.get(k) is not None}
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -322,11 +323,13 @@ def n_step_of(spec, widths, extra=0):
     return spec.nx + widths[0] + sum(n + 3 for n in widths[1:]) + 8 + extra
 
 
-def check_all(spec, out, inp, act_off, widths, H, f32, per_env=True, extra=0):
-    ref, abs_ = recursion(spec, inp, act_off, widths), recursion(spec, P.absolute(inp), act_off, widths, absolute=True)
+def check_all(spec, out, inp, act_off, widths, H, f32, per_env=True, extra=0, abs_G=None):
+    """every output in `out` against the recursion on inp; abs_G as in test_policy_adjoint_gpu.check_all"""
+    ainp = P.absolute(inp) if abs_G is None else dict(P.absolute(inp), G=abs_G)
+    ref, abs_ = recursion(spec, inp, act_off, widths), recursion(spec, ainp, act_off, widths, absolute=True)
     n_step = n_step_of(spec, widths, extra)
     B = np.asarray(inp["G"]).shape[1]
-    for k in OUTS:
+    for k in out:
         shared = (not per_env) and k == "gtheta"
         r, a = (ref[k].sum(0), abs_[k].sum(0)) if shared else (ref[k], abs_[k])
         P.check(out[k], r, a, H, n_step, f32, n_red=B if shared else 0, what=k)
