@@ -14,6 +14,7 @@
 #include "dojo_policy_adjoint.hpp"
 #include "dojo_mlp.hpp"
 #include "dojo_data_adjoint.hpp"
+#include "dojo_tangent.hpp"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -1093,6 +1094,17 @@ int launch_data_adjoint(const DojoSim* s, int H, const void* DZ, const void* DC,
     return DOJO_OK;
 }
 
+// dojo_rollout_tangent_dev: the forward sweep over recorded Jacobians (dojo_tangent.hpp), one workgroup per environment and chunk of NT tangents, one launch
+template <class TIO>
+int launch_tangent(const DojoSim* s, int H, int T, const void* DZ, const void* DU, const void* DC, const void* dz0, const void* dU, const void* dth, int tan_space, const void* Z,
+                   const int* status, void* dZ, hipStream_t st) {
+    const int nx = 12 * s->M.Nb, nu = (int)s->M.nu, nth = 5 * s->M.Nc, nchunk = (T + dj::tangent::NT - 1) / dj::tangent::NT;
+    const dj::tangent::Args<TIO> A{(const TIO*)DZ, (const TIO*)DU, (const TIO*)DC, (const TIO*)dz0, (const TIO*)dU, (const TIO*)dth, (const TIO*)Z, status, (TIO*)dZ, H, s->B, T, nx, nu, nth, tan_space};
+    hipLaunchKernelGGL((dj::tangent::rollout_tangent_kernel<TIO>), dim3((unsigned)((size_t)s->B * nchunk)), dim3(dj::tangent::THREADS), dj::tangent::lds_bytes(nx, nu, nth, sizeof(TIO)), st, A);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
+
 int launch_policy_any(const DojoSim* s, const DojoPolicy& p, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
     return s->dtype == DOJO_DTYPE_F32 ? launch_policy<float>(s, p, z, csg, uff, obs, u, sp) : launch_policy<double>(s, p, z, csg, uff, obs, u, sp);
 }
@@ -1763,6 +1775,64 @@ int dojo_rollout_data_gradients(DojoHandle s, const void* z0, const void* U, int
     TRY(dojo_rollout_data_adjoint_dev(s, H, dDZ.p, dDC.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, gtheta_env ? dgte.p : nullptr, gtheta ? dgt.p : nullptr, dgz.p, nullptr));
     if (gU && nu) TRY(dojo_rollout_adjoint_dev(s, H, dDZ.p, dDU.p, dG.p, cot_space, dZ.p, (const int32_t*)dS.p, dgU.p, nullptr, nullptr));
     return st.finish(s, dZ, H);
+}
+
+// ---- forward mode over the same records (dojo_tangent.hpp): T tangent directions in one pass, the chain of examples/system_identification/utilities.jl:42-90 ----
+int dojo_rollout_tangent_dev(DojoHandle s, int32_t H, int32_t T, const void* DZ, const void* DU, const void* DC, const void* dz0, const void* dU, const void* dtheta,
+                             int32_t tan_space, const void* Z, const int32_t* status, void* dZ, void* stream) {
+    Enter enter_(s);
+    const char* who = "dojo_rollout_tangent_dev";
+    if (!s) { g_err = std::string(who) + ": bad argument"; return DOJO_ERR_INVALID; }
+    const int nx = 12 * s->M.Nb, nu = (int)s->M.nu, nth = 5 * s->M.Nc;
+    if (nu == 0) dU = nullptr;
+    if (nth == 0) dtheta = nullptr;
+    // (the space of the output is this entry's own argument: refuse_sweep's cot_space rule is given nothing to object to, the two tan_space rules are `further` ones;
+    //  its second Jacobian pointer carries the low bits of both DU and DC, which is all the alignment rule looks at)
+    TRY(refuse_sweep(who, H, {{T < 1, "T must be >= 1"}, {!DZ || !dZ, "DZ and dZ must not be NULL"},
+                              {!dz0 && !dU && !dtheta, "dz0, dU and dtheta are all NULL (or ignored: dU with nu = 0, dtheta with Nc = 0)"}}, 0, nullptr,
+                     {{dU && !DU, "dU needs DU"}, {dtheta && !DC, "dtheta needs DC"}, {tan_space != 0 && tan_space != 1, "tan_space must be 0 (tangent) or 1 (state)"},
+                      {tan_space == 1 && !Z, "tan_space = 1 needs the states Z"}},
+                     DZ, (const void*)((uintptr_t)(dU ? DU : nullptr) | (uintptr_t)(dtheta ? DC : nullptr)), "DZ, DU and DC"));
+    if (!dj::tangent::fits(nx, s->w) || dj::tangent::lds_bytes(nx, nu, nth, s->w) > 65536) {
+        g_err = std::string(who) + ": a column of 16-byte pieces must fit a workgroup's 256 lanes (nx <= 512 in fp64, 1024 in fp32) and the step's inputs and partial sums into 64 KB of LDS";
+        return DOJO_ERR_UNSUPPORTED;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the Jacobians)
+    return s->dtype == DOJO_DTYPE_F32 ? launch_tangent<float>(s, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, st)
+                                      : launch_tangent<double>(s, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, st);
+}
+
+// host pointers: upload, record on the device (DU only for dU, DC only for dtheta), forward sweep, download -- the Jacobians never cross PCIe
+int dojo_rollout_tangents(DojoHandle s, const void* z0, const void* U, int32_t H, int32_t T, const void* dz0, const void* dU, const void* dtheta, int32_t tan_space,
+                          void* Z, int32_t* status, void* dZ) {
+    Enter enter_(s);
+    const std::string who = "dojo_rollout_tangents";
+    if (!s || !z0 || !dZ || H < 1 || T < 1 || (tan_space != 0 && tan_space != 1)) { g_err = who + ": bad argument (z0 and dZ are required, H >= 1, T >= 1, tan_space 0 or 1)"; return DOJO_ERR_INVALID; }
+    const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu, nth = 5 * (size_t)s->M.Nc, HB = (size_t)H * B, nout = tan_space ? nz : nx;
+    if (!nu) dU = nullptr;
+    if (!nth) dtheta = nullptr;
+    if (!dz0 && !dU && !dtheta) { g_err = who + ": dz0, dU and dtheta are all NULL (or ignored: dU with nu = 0, dtheta with Nc = 0)"; return DOJO_ERR_INVALID; }
+    TRY(refuse_record(s, who.c_str(), dtheta != nullptr));
+    HIPCHK(hipSetDevice(s->device));
+    Staging st;
+    const auto &dz = st.input(B * nz * w, z0), &dUc = st.input(HB * nu * w, nu ? U : nullptr);
+    const auto &ddz0 = st.input(B * T * nx * w, dz0), &ddU = st.input(HB * T * nu * w, dU), &ddth = st.input((size_t)T * nth * w, dtheta);
+    const auto &dZs = st.kept(HB * nz * w, Z), &dS = st.kept(HB * sizeof(int), status);
+    const auto &dDZ = st.kept(HB * nx * nx * w), &dDU = st.kept(HB * nx * nu * w, nullptr, dU != nullptr), &dDC = st.kept(HB * nx * nth * w, nullptr, dtheta != nullptr);
+    const auto &ddZ = st.kept(HB * T * nout * w, dZ);
+    {
+        Measuring handle(s);
+        TRY(ensure_record(s));
+        TRY(refuse_memory(who + ": the record of " + std::to_string(HB * nx * (nx + (dU ? nu : 0) + (dtheta ? nth : 0)) * w) + " bytes (H B nx (nx + nu + 5 Nc) scalars, DU and DC as far as dU and dtheta ask for them; ",
+                          st, handle, "does"));
+    }
+    TRY(st.allocate());
+    RolloutIO io; io.z0 = dz.p; io.U = dUc.p; io.Z = dZs.p; io.status = (int32_t*)dS.p; io.DZ = dDZ.p; io.DU = dDU.p; io.DC = dDC.p;
+    TRY(rollout_core(s, H, io, nullptr));
+    TRY(dojo_rollout_tangent_dev(s, H, T, dDZ.p, dDU.p, dDC.p, ddz0.p, ddU.p, ddth.p, tan_space, dZs.p, (const int32_t*)dS.p, ddZ.p, nullptr));
+    return st.finish(s, dZs, H);
 }
 
 // ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----

@@ -45,8 +45,12 @@ def lib():
                   "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
                   "dojo_rollout_policy_gradients",
                   "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
-                  "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients"):
+                  "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients",
+                  "dojo_rollout_tangent_dev", "dojo_rollout_tangents"):
             getattr(L, f).restype = C.c_int
+        vp, i32 = C.c_void_p, C.c_int32
+        L.dojo_rollout_tangent_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]      # h, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, stream
+        L.dojo_rollout_tangents.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]                 # h, z0, U, H, T, dz0, dU, dtheta, tan_space, Z, status, dZ
         L.dojo_destroy.restype = None
         _lib = L
     return _lib
@@ -65,7 +69,8 @@ EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error",
                     "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
                     "dojo_rollout_policy_gradients",
                     "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
-                    "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients"]
+                    "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients",
+                    "dojo_rollout_tangent_dev", "dojo_rollout_tangents"]
 
 
 class DojoPolicy(C.Structure):
@@ -381,6 +386,44 @@ class BatchedMechanism:
         _chk(lib().dojo_rollout_data_gradients(self.h, _p(z0), _p(U), H, _p(G), cs, _p(Z), _p(st), _p(gth) if Nc else None,
                                                _p(gte) if (per_env and Nc) else None, _p(gU) if s.nu else None, _p(gz)))
         return Z, st, gth, gte, gU, gz
+
+    def rollout_tangents(self, z0, U=None, dz0=None, dU=None, dtheta=None, steps=None, tan_space="tangent"):
+        """Forward-mode rollout (dojo_rollout_tangents): the rollout of `rollout`, and T tangent directions pushed through the recorded IFT Jacobians of
+        every step in one pass over the record, which stays on the device.  dz0 [B,T,nx] (tangent coordinates [x; v; phi; omega] per body), dU [H,B,T,nu],
+        dtheta [T,Nc,5] or [T,5Nc] (directions of `contact_data()`, shared by the batch); each may be None (= zeros), not all three; T is taken from
+        whichever is given.  Returns (Z [H,B,13Nb], status [H,B], dZ [H,B,T,nx] -- or [H,B,T,13Nb] with tan_space "state": the tangent of the state
+        vector itself, dq = q (x) (0, phi)).  Nothing flows through a failed step: the tangent of the state after it is 0."""
+        B, s = self.batch, self.spec
+        nth = 5 * len(s.contacts)
+        z0 = self._arr(z0, (B, s.nz))
+        if tan_space not in ("tangent", "state", 0, 1):
+            raise ValueError("tan_space must be 'tangent' or 'state'")
+        ts = 1 if tan_space in ("state", 1) else 0
+        dz0 = None if dz0 is None else np.ascontiguousarray(dz0, dtype=self.np_dtype)
+        dU = None if (dU is None or not s.nu) else np.ascontiguousarray(dU, dtype=self.np_dtype)
+        dtheta = None if (dtheta is None or not nth) else np.ascontiguousarray(dtheta, dtype=self.np_dtype)
+        if dtheta is not None:
+            dtheta = dtheta.reshape(dtheta.shape[0], -1)
+        Ts = [a.shape[i] for a, i in ((dz0, 1), (dU, 2), (dtheta, 0)) if a is not None and a.ndim > i]
+        if not Ts:
+            raise ValueError("rollout_tangents needs at least one of dz0, dU, dtheta (dU counts only with nu > 0, dtheta only with contacts)")
+        T = int(Ts[0])
+        if any(int(t) != T for t in Ts):
+            raise ValueError("dz0, dU and dtheta hold different numbers of tangents: %s" % Ts)
+        Hs = [np.shape(a)[0] for a in (U if s.nu else None, dU) if a is not None] + ([int(steps)] if steps is not None else [])
+        if not Hs:
+            raise ValueError("rollout_tangents needs the horizon: U, dU or steps")
+        H = int(Hs[0])
+        if any(int(h) != H for h in Hs):
+            raise ValueError("U, dU and steps disagree about the horizon: %s" % Hs)
+        U = self._arr(U, (H, B, s.nu)) if (U is not None and s.nu) else None
+        for name, a, shape in (("dz0", dz0, (B, T, s.nx)), ("dU", dU, (H, B, T, s.nu)), ("dtheta", dtheta, (T, nth))):
+            if a is not None and a.shape != shape:
+                raise ValueError("expected %s of shape %s, got %s" % (name, shape, a.shape))
+        Z = np.empty((H, B, s.nz), self.np_dtype); st = np.empty((H, B), np.int32)
+        dZ = np.empty((H, B, T, s.nz if ts else s.nx), self.np_dtype)
+        _chk(lib().dojo_rollout_tangents(self.h, _p(z0), _p(U), H, T, _p(dz0), _p(dU), _p(dtheta), ts, _p(Z), _p(st), _p(dZ)))
+        return Z, st, dZ
 
     def rollout_policy(self, z0, W, steps, bias=None, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):
         """Closed-loop rollout (dojo_rollout_policy): simulate! with the affine feedback policy u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale))

@@ -208,6 +208,28 @@ function rollout_data_gradients(bm::BatchedMechanism{T}, z0::Matrix{T}, U::Array
     return Z, status, gθ, gθ_env, gU, gz
 end
 
+"""
+forward-mode rollout: `rollout` plus T tangent directions pushed through the recorded step Jacobians in one pass over the record (dojo_rollout_tangents) --
+the chain of examples/system_identification/utilities.jl:42-90 on the device.  dz0[nx, T, B] (tangent coordinates), dU[nu, T, B, H], dθ[5Nc, T] (shared by the
+batch); each may be `nothing` (= zeros), not all three.  -> Z[nz, B, H], status[B, H], dZ[nx, T, B, H] (or [nz, T, B, H] with tan_space = :state: dq = q ⊗ (0, φ)).
+Nothing flows through a failed step: the tangent of the state after it is 0.
+"""
+function rollout_tangents(bm::BatchedMechanism{T}, z0::Matrix{T}, U::Union{Nothing,Array{T,3}}, H::Integer; dz0::Union{Nothing,Array{T,3}}=nothing,
+                          dU::Union{Nothing,Array{T,4}}=nothing, dθ::Union{Nothing,Matrix{T}}=nothing, tan_space::Symbol=:tangent, opts=Dojo.SolverOptions{Float64}()) where T
+    set_options!(bm, opts)
+    given = [(a, d) for (a, d) in ((dz0, 2), (dU, 2), (dθ, 2)) if a !== nothing]
+    isempty(given) && error("rollout_tangents needs at least one of dz0, dU, dθ")
+    nT = size(given[1][1], given[1][2])
+    all(size(a, d) == nT for (a, d) in given) || error("dz0, dU and dθ hold different numbers of tangents")
+    ptr(a) = a === nothing ? Ptr{T}(C_NULL) : pointer(a)
+    Z = Array{T}(undef, bm.nz, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    dZ = Array{T}(undef, tan_space === :state ? bm.nz : bm.nx, nT, bm.batch, H)
+    check(@ccall $(fn(:dojo_rollout_tangents))(bm.handle::Ptr{Cvoid}, z0::Ptr{T}, ((U !== nothing && bm.nu > 0) ? pointer(U) : C_NULL)::Ptr{T}, Int32(H)::Int32, Int32(nT)::Int32,
+                                               ptr(dz0)::Ptr{T}, ptr(dU)::Ptr{T}, ptr(dθ)::Ptr{T}, Int32(tan_space === :state ? 1 : 0)::Int32,
+                                               Z::Ptr{T}, status::Ptr{Int32}, dZ::Ptr{T})::Cint)
+    return Z, status, dZ
+end
+
 "mirror of `DojoPolicy` (include/dojo_hip.h): five pointers, six Int32"
 struct DojoPolicy
     W::Ptr{Cvoid}; bias::Ptr{Cvoid}; mean::Ptr{Cvoid}; scale::Ptr{Cvoid}; U_ff::Ptr{Cvoid}

@@ -20,9 +20,16 @@ cost evaluation builds a handle for its θ (set_data!(mechanism.contacts, θ), u
 Jacobians of every step on the device (∂z'/∂z, ∂z'/∂θ), its gradient one sweep over them (`dojo_amd.autograd.differentiable_data_rollout`:
 dojo_rollout_data_record_dev + dojo_rollout_data_adjoint_dev); θ changes between evaluations through `set_contact_data`, no handle is rebuilt and
 no Jacobian is downloaded.  The optimiser is torch.optim.LBFGS.  (The reference's Gauss-Newton Hessian JᵀQJ needs the forward-mode sensitivities
-∂z/∂θ themselves, which a reverse sweep does not produce: that path stays the default one above.)
+∂z/∂θ themselves, which a reverse sweep does not produce: `--gauss-newton` below is the path that has them.)
 
     python examples/sphere_system_identification_device.py --rollout
+
+`--gauss-newton`: the reference's own loop (`quasi_newton_solve`, unchanged) with cost, gradient and JᵀQJ from ONE handle in forward mode.  Per
+evaluation: `set_contact_data(θ)`, then one `rollout_tangents` call (dojo_rollout_tangents: the recording rollout and one forward sweep over the record
+with dθ = the five unit vectors, tan_space "state"), whose dZ [3, 10, 5, 13] is `attitude_jacobian @ dc` of the default path for every step and
+trajectory; g = Σ JᵀQe and H = Σ JᵀQJ are formed on the host from those numbers.  No handle is rebuilt and no Jacobian is downloaded.
+
+    python examples/sphere_system_identification_device.py --gauss-newton
 """
 import os
 import sys
@@ -156,8 +163,48 @@ def rollout_solve(Z, guess=(0.0, 1.0), lower=(0.0, 0.05), upper=(0.8, 1.0), grad
     return sol.numpy(), f
 
 
+class ForwardModeLoss:
+    """the cost of `loss`, its gradient and its Gauss-Newton Hessian from one handle: θ changes through set_contact_data, the sensitivities ∂z/∂θ of every
+    step come from one forward sweep over the recorded Jacobians (rollout_tangents) and never leave the device as Jacobians"""
+
+    def __init__(self, Z, grad_mode=0, opts=None):
+        self.gm = api.BatchedMechanism(sphere(np.array([0.2, 0.5])), len(Z), dtype="f64", opts=opts)
+        self.gm.set_gradient_mode(grad_mode)
+        self.z0 = Z[:, TIMESTEPS[0] - 1].copy()
+        self.Zt = np.ascontiguousarray(Z[:, list(TIMESTEPS)].transpose(1, 0, 2))      # [H, B, 13]
+        self.q = np.diag(Q).copy()
+
+    def cost(self, theta):
+        self.gm.set_contact_data(np.asarray(theta, float).reshape(1, 5))
+        Zp, st = self.gm.rollout(self.z0, steps=len(TIMESTEPS))
+        assert (st == 0).all()
+        e = Zp - self.Zt
+        return 0.5 * float((e * e * self.q).sum())
+
+    def fgH(self, theta):
+        self.gm.set_contact_data(np.asarray(theta, float).reshape(1, 5))
+        Zp, st, J = self.gm.rollout_tangents(self.z0, dtheta=np.eye(5), steps=len(TIMESTEPS), tan_space="state")      # J [H, B, 5, 13] = (∂z_k/∂θ)ᵀ
+        assert (st == 0).all()
+        e = Zp - self.Zt
+        cost = 0.5 * float((e * e * self.q).sum())
+        g = np.einsum("kbti,i,kbi->t", J, self.q, e)
+        H = np.einsum("kbti,i,kbui->tu", J, self.q, J)
+        return cost, g[:2], H[:2, :2]
+
+    def close(self):
+        self.gm.close()
+
+
 def main():
     Z = dataset()
+    if "--gauss-newton" in sys.argv[1:]:
+        fm = ForwardModeLoss(Z)
+        f0 = lambda th: fm.cost(np.concatenate([th, np.zeros(3)]))
+        fgH0 = lambda th: fm.fgH(np.concatenate([th, np.zeros(3)]))
+        sol = quasi_newton_solve(f0, fgH0, np.array([0.0, 1.0]))
+        print("solution (forward mode, one handle): friction_coefficient %.6f (0.2), contact_radius %.6f (0.5), cost %.3e" % (sol[0], sol[1], f0(sol)))
+        fm.close()
+        return
     if "--rollout" in sys.argv[1:]:
         sol, f = rollout_solve(Z)
         print("solution (reverse mode, one handle): friction_coefficient %.6f (0.2), contact_radius %.6f (0.5), cost %.3e" % (sol[0], sol[1], f))

@@ -429,6 +429,41 @@ int  dojo_rollout_data_adjoint_dev(DojoHandle h, int32_t H, const void* DZ, cons
 int  dojo_rollout_data_gradients(DojoHandle h, const void* z0, const void* U, int32_t H, const void* G, int32_t cot_space,
                                  void* Z, int32_t* status, void* gtheta, void* gtheta_env, void* gU, void* gz);
 
+/* Forward-mode rollouts: T tangent directions swept over a record in ONE pass (csrc/dojo_tangent.hpp) -- the chain that the reference's system
+ * identification runs on the host, step by step (examples/system_identification/utilities.jl:42-90): J v next to the J^T w of the entries above
+ * (Gauss-Newton / Levenberg-Marquardt products J^T Q J v: two sweeps over one record; the sensitivities of a whole trajectory to a few parameters).
+ *
+ * dojo_rollout_tangent_dev: ONE launch for all H steps on `stream`, no synchronization.  DZ, DU, DC are plain device buffers in the handle's
+ * dtype, as dojo_rollout_record_dev / dojo_rollout_data_record_dev (or the caller's own step loop) leave them.  Per environment b, tangent t:
+ *     delta <- dz0[b][t]                                                        dz0 [B][T][nx], tangent coordinates [x; v; phi; omega] per body
+ *     for k = 0 .. H-1:   if status && status[k][b] != 0:  delta <- 0           (DZ_k, DU_k, DC_k are not read: they may be NaN)
+ *                         else:  delta <- DZ_k[b] delta + DU_k[b] dU[k][b][t] + DC_k[b] dtheta[t]      dU [H][B][T][nu], dtheta [T][5Nc] (shared by the batch)
+ *                         dZ[k][b][t] <- delta
+ * This is the transpose of the failure rule of the reverse sweeps: nothing flows through a failed step, the tangent of the state after it is 0,
+ * later controls act again.  tan_space = 0: dZ [H][B][T][nx].  tan_space = 1: dZ [H][B][T][13Nb], the push-forward per body -- x, v, omega copied,
+ * dq = q (x) (0, phi) with q from Z[k][b] (fp32 handles: q / |q|) --, the transpose of what cot_space = 1 does to a cotangent.
+ * Each of dz0, dU, dtheta may be NULL (= zeros; the matching Jacobian array -- DU for dU, DC for dtheta -- is then not read and may be NULL); dU is
+ * ignored when nu = 0, dtheta when Nc = 0.  Every product and sum is fp64, delta stays fp64 between the steps, outputs are rounded once.  No
+ * atomics; the summation order is fixed by (nx, nu, 5Nc, dtype) alone: a tangent's result is bit-identical from run to run and does not depend on
+ * B, on the environment's position in the batch, on T or on the tangent's position among the T.
+ * DOJO_ERR_INVALID (text on the handle, nothing launched): H < 1 or T < 1; NULL DZ or dZ; dz0, dU and dtheta all NULL (after the two rules
+ * above); dU without DU (nu > 0); dtheta without DC (Nc > 0); tan_space not 0 or 1; tan_space = 1 without Z; DZ, DU or DC not 16-byte aligned.
+ * DOJO_ERR_UNSUPPORTED: a column of more than 256 16-byte pieces (one team of lanes sweeps a column: nx <= 512 in fp64, 1024 in fp32), or inputs
+ * and partial sums of a step -- 32 (nx + nu + 5Nc + nteams nx) bytes, nteams = min(256 / pieces, 16) -- beyond 64 KB of LDS.  Atlas (nx 372) needs 40 KB.
+ *
+ * dojo_rollout_tangents (host pointers): uploads z0, U (NULL = zeros), dz0, dU, dtheta; allocates the record on the device -- DZ, DU only when dU
+ * is given, DC only when dtheta is given --, runs the recording rollout and the sweep above, downloads Z [H][B][13Nb], status [H][B] (each may be
+ * NULL) and dZ.  The Jacobians never cross PCIe.  Mechanisms the recording rollouts refuse are refused the same way.
+ * Memory of the call, exactly what it allocates: the record, H B nx (nx + [nu] + [5Nc]) w bytes ([nu] with dU, [5Nc] with dtheta) -- Ant (nx 156,
+ * nu 14, Nc 4), fp32, B = 4096, H = 20, all three: 9.7 GB --, the output H B T nout w (nout = nx or 13Nb), the states and status H B (13Nb w + 4),
+ * the inputs that are given (z0 B 13Nb w, U H B nu w, dz0 B T nx w, dU H B T nu w, dtheta T 5Nc w), and the handle's workspaces on first use.  A
+ * call that does not fit into the free device memory: DOJO_ERR_INVALID with the byte counts in the text, before any launch. */
+int  dojo_rollout_tangent_dev(DojoHandle h, int32_t H, int32_t T, const void* DZ, const void* DU, const void* DC,
+                              const void* dz0 /* [B][T][nx] or NULL */, const void* dU /* [H][B][T][nu] or NULL */, const void* dtheta /* [T][5Nc] or NULL */,
+                              int32_t tan_space, const void* Z, const int32_t* status, void* dZ /* [H][B][T][nx or 13Nb] */, void* stream);
+int  dojo_rollout_tangents(DojoHandle h, const void* z0, const void* U, int32_t H, int32_t T,
+                           const void* dz0, const void* dU, const void* dtheta, int32_t tan_space, void* Z, int32_t* status, void* dZ);
+
 /* Closed-loop rollouts: simulate!(mechanism, steps, storage, control!) (src/simulation/simulate.jl:16-37) with a controller that looks at the
  * state -- an affine feedback policy per environment, evaluated ON THE DEVICE between the steps (csrc/dojo_policy.hpp: observation, normalisation,
  * policy and control assembly in one launch), so that the call keeps the choreography of dojo_rollout_dev: environment groups chained on internal
