@@ -20,6 +20,10 @@
 // the loads of item i + 1 are issued before the arithmetic of item i -- across the barrier too: the first loads of step k - 1 leave before step k ends.
 // The summation order is fixed by (nx, dtype) alone: no atomics, results are bit-identical from run to run and do not depend on the batch size or on
 // where in the batch an environment sits.
+//
+// What the other reverse sweeps take from here (dojo_data_adjoint.hpp, dojo_policy_adjoint.hpp, dojo_mlp.hpp): cotangent() and its record Cot, the column
+// pipeline (columns, items, issue, consume) and sweep(), the loop over the steps that drives it -- the g buffers, the two piece buffers, which item
+// is issued next across a step boundary, the failed steps, the barrier.  A kernel is its set-up, four callables for sweep() and its write-out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dojo_math.hpp"
@@ -27,11 +31,18 @@
 namespace dj {
 namespace adjoint {
 
+// what cotangent() reads: the cotangents of the states of a rollout, in either space.  Every sweep builds one from its own argument record.
+template <class TIO> struct Cot {
+    const TIO* G;           // [H][B][nx] (cot_space 0) or [H][B][13 Nb] (cot_space 1)
+    const TIO* Z;           // [H][B][13 Nb], cot_space 1 only
+    int B, nx, cot_space;
+};
+
 template <class TIO> struct Args {
     const TIO* DZ;          // [H][B][nx][nx]
     const TIO* DU;          // [H][B][nu][nx] (unused when gU is null)
-    const TIO* G;           // [H][B][nx] (cot_space 0) or [H][B][13 Nb] (cot_space 1)
-    const TIO* Z;           // [H][B][13 Nb], cot_space 1 only
+    const TIO* G;           // as Cot
+    const TIO* Z;
     const int* status;      // [H][B] or null
     TIO* gU;                // [H][B][nu] or null
     TIO* gz;                // [B][nx] or null
@@ -63,7 +74,11 @@ __device__ __forceinline__ double row_sum(double v) {
 // g_k[c] of environment b in tangent coordinates.  cot_space 1: the cotangent is given w.r.t. the state (x, v, q, omega) and pulled back through
 // dq = q (x) (0, phi) (dojo_math.hpp: LVᵀmat), i.e. g_phi = vector part of conj(q) (x) g_q; x, v, omega are copied.  A 4-byte state stands for
 // q / |q| (as the step kernels read it).
-template <class TIO> __device__ __forceinline__ double cotangent(const Args<TIO>& A, const TIO* G, const TIO* Z, int k, int b, int c) {
+template <class TIO, class A_> __device__ __forceinline__ Cot<TIO> cot_of(const A_& A) {      // from any record with these five fields
+    return Cot<TIO>{DJ_GLOBAL_PTR(const TIO, A.G), DJ_GLOBAL_PTR(const TIO, A.Z), A.B, A.nx, A.cot_space};
+}
+template <class TIO> __device__ __forceinline__ double cotangent(const Cot<TIO>& A, int k, int b, int c) {
+    const TIO* const G = A.G; const TIO* const Z = A.Z;
     const size_t kb = (size_t)k * A.B + b;
     if (A.cot_space == 0) return (double)G[kb * A.nx + c];
     const int body = c / 12, i = c % 12;
@@ -81,7 +96,7 @@ template <class TIO> __device__ __forceinline__ double cotangent(const Args<TIO>
     return q[0] * g[1 + a] - g[0] * q[1 + a] - (q[1 + a1] * g[1 + a2] - q[1 + a2] * g[1 + a1]);
 }
 
-// ---- the column pipeline: what this sweep and the closed-loop one (dojo_policy_adjoint.hpp) stream DZ and DU with ----
+// ---- the column pipeline: what sweep() below streams DZ and DU with ----
 // The columns of a step are [c0, nx) of DZ followed by ncol - nx columns of DU; its work is a flat list of (column group, piece) items.
 template <class TIO> struct Columns {
     const TIO *DZ, *DU;     // the record (global address space)
@@ -136,24 +151,25 @@ __device__ __forceinline__ void consume(const Columns<TIO>& C, int c0, int it, i
     }
 }
 
-template <class TIO>
-__global__ void __launch_bounds__(THREADS) rollout_adjoint_kernel(const Args<TIO> A) {
+// ---- the step loop: what the four reverse sweeps (this one, dojo_data_adjoint.hpp, dojo_policy_adjoint.hpp, dojo_mlp.hpp) walk the record with ----
+// Called by all 256 lanes of environment b's workgroup with lambda (what flows into step H-1 next to g_{H-1}; the open-loop sweeps: 0) in lam_[0 .. nx).
+// It owns g_k in LDS (double-buffered; g_{k-1} is fetched through cotangent() while step k runs), the two piece buffers and which item is issued
+// next, the failed steps (status != 0: no item is issued, nothing of DZ_k or DU_k is read) and the barrier that ends a step.  The kernel hands it
+//     first_col(k)                     where the step's columns start (uniform over the workgroup)
+//     put(k, c, value, lam_next)       a finished column c of step k: one lane per column
+//     on_failed(k, lam_next)           what a failed step writes in their place: all lanes
+//     after(k, lam_next)               behind the step's barrier, all lanes: uniform over the workgroup, may contain barriers of its own and must end
+//                                      with one if it writes what the next step reads (lam_next is lambda of step k-1, less g_{k-1})
+// lam_ [2][nx] and g_ [2][nx] are LDS.  Everything is inlined into the kernel: the callables cost no registers of their own.
+template <class TIO, class FirstCol, class Put, class OnFailed, class After>
+__device__ __forceinline__ void sweep(const Columns<TIO>& C, const Cot<TIO>& cot, const int* status, int H, int b, double* lam_, double* g_,
+                                      FirstCol&& first_col, Put&& put, OnFailed&& on_failed, After&& after) {
     typedef typename Piece<TIO>::type P;
-    extern __shared__ __align__(16) double lds_[];                          // lambda [2][nx] | g [2][nx]
-    const int b = (int)blockIdx.x, tid = (int)threadIdx.x, team = tid / ROW, j = tid % ROW;
-    const int H = A.H, B = A.B, nx = A.nx, nu = A.gU ? A.nu : 0;
-    const TIO* const G = DJ_GLOBAL_PTR(const TIO, A.G);   const TIO* const Z = DJ_GLOBAL_PTR(const TIO, A.Z);
-    const int* const status = DJ_GLOBAL_PTR(const int, A.status);
-    TIO* const gU = DJ_GLOBAL_PTR(TIO, A.gU); TIO* const gz = DJ_GLOBAL_PTR(TIO, A.gz);
-    const Columns<TIO> C = columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DU), B, nx, A.nu, nu);
-    double* const lam_ = lds_; double* const g_ = lds_ + 2 * nx;
-
-    // the columns of step k: [c0, nx) of DZ (lambda; step 0 feeds gz alone), then the nu columns of DU (gU).  All of it is uniform over the workgroup.
-    auto first_col = [&](int k) { return (k == 0 && !gz) ? nx : 0; };
+    const int tid = (int)threadIdx.x, team = tid / ROW, j = tid % ROW, B = C.B, nx = C.nx;
     auto failed = [&](int k) { return status != nullptr && status[(size_t)k * B + b] != 0; };
     auto items_of = [&](int k) { return (k < 0 || failed(k)) ? 0 : items(C, first_col(k)); };
 
-    for (int c = tid; c < nx; c += THREADS) { lam_[c] = 0.0; g_[((H - 1) & 1) * nx + c] = cotangent(A, G, Z, H - 1, b, c); }
+    for (int c = tid; c < nx; c += THREADS) g_[((H - 1) & 1) * nx + c] = cotangent(cot, H - 1, b, c);
     // Two piece buffers take turns: a copy from "next" to "current" would have to wait for the loads it is meant to leave in flight.
     int p = 0, nit = items_of(H - 1);
     P buf0[COLS], buf1[COLS];
@@ -163,35 +179,55 @@ __global__ void __launch_bounds__(THREADS) rollout_adjoint_kernel(const Args<TIO
         // lambda_k = (what step k + 1 left) + g_k, formed where it is read; g_{k-1} goes to LDS for the next step meanwhile
         const double* lam = lam_ + p * nx; const double* gk = g_ + (k & 1) * nx; double* lam_next = lam_ + (p ^ 1) * nx;
         const int nit_next = items_of(k - 1), c0 = first_col(k);
-        const size_t kb = (size_t)k * B + b;
-        if (k > 0) for (int c = tid; c < nx; c += THREADS) g_[((k - 1) & 1) * nx + c] = cotangent(A, G, Z, k - 1, b, c);
+        if (k > 0) for (int c = tid; c < nx; c += THREADS) g_[((k - 1) & 1) * nx + c] = cotangent(cot, k - 1, b, c);
         double acc[COLS];
 #pragma unroll
         for (int i = 0; i < COLS; ++i) acc[i] = 0.0;
-        auto put = [&](int c, double mine) {
-            if (c >= nx) gU[kb * A.nu + (c - nx)] = (TIO)mine;
-            else if (k > 0) lam_next[c] = mine;
-            else gz[(size_t)b * nx + c] = (TIO)mine;
-        };
+        auto put_k = [&](int c, double mine) { put(k, c, mine, lam_next); };
         auto stage = [&](int it, const P (&cur)[COLS], P (&nxt)[COLS]) {
             // the next item: of this step, else the first of step k - 1 -- else this one again, so that a wait always has COLS younger loads to count
             const bool more = it + 1 < nit;
             const int kn = (more || !nit_next) ? k : k - 1;
             issue(C, kn, b, first_col(kn), more ? it + 1 : nit_next ? 0 : it, team, j, nxt);
-            consume(C, c0, it, team, j, lam, gk, cur, acc, put);
+            consume(C, c0, it, team, j, lam, gk, cur, acc, put_k);
         };
         for (int it = 0; it < nit; it += 2) { stage(it, buf0, buf1); stage(it + 1, buf1, buf0); }
         if (failed(k)) {                                                    // nothing flows through a failed step
+            on_failed(k, lam_next);
+            if (nit_next) issue(C, k - 1, b, first_col(k - 1), 0, team, j, buf0);
+        }
+        __syncthreads();
+        after(k, lam_next);
+        p ^= 1; nit = nit_next;
+    }
+}
+
+template <class TIO>
+__global__ void __launch_bounds__(THREADS) rollout_adjoint_kernel(const Args<TIO> A) {
+    extern __shared__ __align__(16) double lds_[];                          // lambda [2][nx] | g [2][nx]
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int nx = A.nx, nu = A.gU ? A.nu : 0;
+    TIO* const gU = DJ_GLOBAL_PTR(TIO, A.gU); TIO* const gz = DJ_GLOBAL_PTR(TIO, A.gz);
+    const Columns<TIO> C = columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DU), A.B, nx, A.nu, nu);
+    double* const lam_ = lds_;
+
+    for (int c = tid; c < nx; c += THREADS) lam_[c] = 0.0;
+    sweep(C, cot_of<TIO>(A), DJ_GLOBAL_PTR(const int, A.status), A.H, b, lam_, lds_ + 2 * nx,
+        // the columns of step k: [c0, nx) of DZ (lambda; step 0 feeds gz alone), then the nu columns of DU (gU)
+        [&](int k) { return (k == 0 && !gz) ? nx : 0; },
+        [&](int k, int c, double mine, double* lam_next) {
+            if (c >= nx) gU[((size_t)k * A.B + b) * A.nu + (c - nx)] = (TIO)mine;
+            else if (k > 0) lam_next[c] = mine;
+            else gz[(size_t)b * nx + c] = (TIO)mine;
+        },
+        [&](int k, double* lam_next) {
             for (int c = tid; c < nx; c += THREADS) {
                 if (k > 0) lam_next[c] = 0.0;
                 else if (gz) gz[(size_t)b * nx + c] = (TIO)0.0;
             }
-            for (int c = tid; c < nu; c += THREADS) gU[kb * A.nu + c] = (TIO)0.0;
-            if (nit_next) issue(C, k - 1, b, first_col(k - 1), 0, team, j, buf0);
-        }
-        __syncthreads();
-        p ^= 1; nit = nit_next;
-    }
+            for (int c = tid; c < nu; c += THREADS) gU[((size_t)k * A.B + b) * A.nu + c] = (TIO)0.0;
+        },
+        [](int, double*) {});
 }
 #endif
 

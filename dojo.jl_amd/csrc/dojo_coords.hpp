@@ -115,6 +115,17 @@ template <class S> DJ_HD PoseVel<S> origin_body() {
     PoseVel<S> p; for (int i = 0; i < 3; ++i) { p.x[i] = S(0.0); p.v[i] = S(0.0); p.w[i] = S(0.0); } p.q[0] = S(1.0); p.q[1] = S(0.0); p.q[2] = S(0.0); p.q[3] = S(0.0); return p;
 }
 
+// a body state seeded with its 12 tangent directions [x, v, phi, omega] starting at direction d0 of N: q (x) (1, phi).  What the Jacobian kernels of
+// dojo_hip.hip and observation_jacobian_kernel (dojo_policy_adjoint.hpp) differentiate the maps below at.
+template <int N> DJ_HD PoseVel<Dual<N>> seed_body(const PoseVel<double>& p, int d0) {
+    typedef Dual<N> D;
+    PoseVel<D> s;
+    for (int i = 0; i < 3; ++i) { s.x[i] = D::seed(p.x[i], d0 + i); s.v[i] = D::seed(p.v[i], d0 + 3 + i); s.w[i] = D::seed(p.w[i], d0 + 9 + i); }
+    D e[4] = {D(1.0), D::seed(0.0, d0 + 6), D::seed(0.0, d0 + 7), D::seed(0.0, d0 + 8)}, q0[4] = {D(p.q[0]), D(p.q[1]), D(p.q[2]), D(p.q[3])};
+    qmulS(s.q, q0, e);
+    return s;
+}
+
 // child body state from the parent's state and the joint's minimal coordinates / velocities (minimal.jl:205-232)
 template <class S>
 DJ_HD void joint_min2max(PoseVel<S>& b, const NodeP<double>& P, double dt, const PoseVel<S>& a, const S* dx, const S* dth, const S* dv, const S* dw) {

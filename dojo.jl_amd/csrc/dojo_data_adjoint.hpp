@@ -15,8 +15,8 @@
 //
 // DC is in the layout dojo_contact_gradients_dev writes: [H][B][5Nc][nx], column-major per environment like DZ, so that (DC^T lambda)[c] is the dot
 // product of a contiguous column with lambda -- "a block of columns of nx rows behind DZ", which is what adjoint::Columns calls DU.  The sweep is
-// therefore rollout_adjoint_kernel with DC in DU's place and the column pipeline of dojo_adjoint.hpp as it stands (columns, items, issue, consume,
-// cotangent, row_sum: the same loads, the same waits, the same summation order inside a column).  What differs is where a finished column goes: a
+// therefore rollout_adjoint_kernel with DC in DU's place, on the same step loop (adjoint::sweep: the same loads, the same waits, the same summation
+// order inside a column).  What differs is where a finished column goes, i.e. the `put` this kernel hands to the loop: a
 // column c >= nx is ADDED to the fp64 accumulator a[c - nx] in LDS (5Nc doubles next to lambda and g).  An accumulator is written by exactly one lane
 // per step and the barrier that ends a step orders the steps, so the order of the additions over k is fixed (H-1 down to 0): no atomics.  Which lane
 // owns a column may differ at step 0 (gz == NULL: the columns of the step then start at nx) -- the accumulators live in LDS, not in registers, for that.
@@ -27,7 +27,7 @@
 // with the few entries there are here that is two workgroups walking B / 16 dependent additions.)  gtheta_env and gz do not depend on where an
 // environment sits in the batch; gtheta is bit-identical from run to run.
 //
-// The gradient w.r.t. the controls is not an output: a third column block would mean generalising the shared pipeline, and DU is a small share of the
+// The gradient w.r.t. the controls is not an output: a third column block would be a change to adjoint::Columns / issue, and DU is a small share of the
 // traffic (nx nu next to nx^2).  A caller who wants both runs dojo_rollout_adjoint_dev over the same record (dojo_rollout_data_gradients does).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,59 +58,30 @@ inline size_t lds_bytes(int nx, int nth) { return ((size_t)4 * nx + (size_t)nth)
 template <class TIO>
 __global__ void __launch_bounds__(THREADS) rollout_data_adjoint_kernel(const Args<TIO> A) {
     using namespace adjoint;
-    typedef typename Piece<TIO>::type P;
     extern __shared__ __align__(16) double lds_[];                          // lambda [2][nx] | g [2][nx] | a [nth]
-    const int b = (int)blockIdx.x, tid = (int)threadIdx.x, team = tid / ROW, j = tid % ROW;
-    const int H = A.H, B = A.B, nx = A.nx, nth = (A.gtheta_env || A.acc_out) ? A.nth : 0;
-    const TIO* const G = DJ_GLOBAL_PTR(const TIO, A.G);   const TIO* const Z = DJ_GLOBAL_PTR(const TIO, A.Z);
-    const int* const status = DJ_GLOBAL_PTR(const int, A.status);
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int nx = A.nx, nth = (A.gtheta_env || A.acc_out) ? A.nth : 0;
     TIO* const gz = DJ_GLOBAL_PTR(TIO, A.gz);
-    const Columns<TIO> C = columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DC), B, nx, A.nth, nth);
-    double* const lam_ = lds_; double* const g_ = lds_ + 2 * nx; double* const a_ = lds_ + 4 * nx;
-    // the cotangent of the state is the open-loop sweep's (adjoint::cotangent reads G, Z, B, nx, cot_space)
-    const adjoint::Args<TIO> AG{nullptr, nullptr, A.G, A.Z, nullptr, nullptr, nullptr, H, B, nx, 0, A.cot_space};
-
-    // the columns of step k: [c0, nx) of DZ (lambda; step 0 feeds gz alone), then the nth columns of DC (the accumulators).  Uniform over the workgroup.
-    auto first_col = [&](int k) { return (k == 0 && !gz) ? nx : 0; };
-    auto failed = [&](int k) { return status != nullptr && status[(size_t)k * B + b] != 0; };
-    auto items_of = [&](int k) { return (k < 0 || failed(k)) ? 0 : items(C, first_col(k)); };
+    const Columns<TIO> C = columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DC), A.B, nx, A.nth, nth);
+    double* const lam_ = lds_; double* const a_ = lds_ + 4 * nx;
 
     for (int e = tid; e < nth; e += THREADS) a_[e] = 0.0;
-    for (int c = tid; c < nx; c += THREADS) { lam_[c] = 0.0; g_[((H - 1) & 1) * nx + c] = cotangent(AG, G, Z, H - 1, b, c); }
-    int p = 0, nit = items_of(H - 1);
-    P buf0[COLS], buf1[COLS];
-    if (nit) issue(C, H - 1, b, first_col(H - 1), 0, team, j, buf0);
-    __syncthreads();
-    for (int k = H - 1; k >= 0; --k) {
-        const double* lam = lam_ + p * nx; const double* gk = g_ + (k & 1) * nx; double* lam_next = lam_ + (p ^ 1) * nx;
-        const int nit_next = items_of(k - 1), c0 = first_col(k);
-        if (k > 0) for (int c = tid; c < nx; c += THREADS) g_[((k - 1) & 1) * nx + c] = cotangent(AG, G, Z, k - 1, b, c);
-        double acc[COLS];
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) acc[i] = 0.0;
-        auto put = [&](int c, double mine) {
+    for (int c = tid; c < nx; c += THREADS) lam_[c] = 0.0;
+    sweep(C, cot_of<TIO>(A), DJ_GLOBAL_PTR(const int, A.status), A.H, b, lam_, lds_ + 2 * nx,
+        // the columns of step k: [c0, nx) of DZ (lambda; step 0 feeds gz alone), then the nth columns of DC (the accumulators)
+        [&](int k) { return (k == 0 && !gz) ? nx : 0; },
+        [&](int k, int c, double mine, double* lam_next) {
             if (c >= nx) a_[c - nx] += mine;                                // one lane per column and step; the step's barrier orders the steps
             else if (k > 0) lam_next[c] = mine;
             else gz[(size_t)b * nx + c] = (TIO)mine;
-        };
-        auto stage = [&](int it, const P (&cur)[COLS], P (&nxt)[COLS]) {
-            // the next item: of this step, else the first of step k - 1 -- else this one again, so that a wait always has COLS younger loads to count
-            const bool more = it + 1 < nit;
-            const int kn = (more || !nit_next) ? k : k - 1;
-            issue(C, kn, b, first_col(kn), more ? it + 1 : nit_next ? 0 : it, team, j, nxt);
-            consume(C, c0, it, team, j, lam, gk, cur, acc, put);
-        };
-        for (int it = 0; it < nit; it += 2) { stage(it, buf0, buf1); stage(it + 1, buf1, buf0); }
-        if (failed(k)) {                                                    // nothing flows through a failed step; the accumulators keep what they hold
+        },
+        [&](int k, double* lam_next) {                                      // the accumulators keep what they hold
             for (int c = tid; c < nx; c += THREADS) {
                 if (k > 0) lam_next[c] = 0.0;
                 else if (gz) gz[(size_t)b * nx + c] = (TIO)0.0;
             }
-            if (nit_next) issue(C, k - 1, b, first_col(k - 1), 0, team, j, buf0);
-        }
-        __syncthreads();
-        p ^= 1; nit = nit_next;
-    }
+        },
+        [](int, double*) {});
     // the accumulators: rounded once per environment, and / or handed to the reduction over the batch as fp64
     TIO* const ge = DJ_GLOBAL_PTR(TIO, A.gtheta_env); double* const out = DJ_GLOBAL_PTR(double, A.acc_out);
     for (int e = tid; e < nth; e += THREADS) {

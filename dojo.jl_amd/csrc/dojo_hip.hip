@@ -274,14 +274,6 @@ __global__ void storage_kernel(const NodeP<double>* nodes, const ContactP<double
 
 // ---- Jacobians by forward-mode differentiation of the same maps ----
 typedef Dual<24> D24;
-// a body state seeded with its 12 attitude-reduced directions [x, v, phi, omega] starting at direction d0
-template <class TIO> __device__ __forceinline__ PoseVel<D24> seed_body(const PoseVel<double>& p, int d0) {
-    PoseVel<D24> s;
-    for (int i = 0; i < 3; ++i) { s.x[i] = D24::seed(p.x[i], d0 + i); s.v[i] = D24::seed(p.v[i], d0 + 3 + i); s.w[i] = D24::seed(p.w[i], d0 + 9 + i); }
-    D24 e[4] = {D24(1.0), D24::seed(0.0, d0 + 6), D24::seed(0.0, d0 + 7), D24::seed(0.0, d0 + 8)}, q0[4] = {D24(p.q[0]), D24(p.q[1]), D24(p.q[2]), D24(p.q[3])};
-    qmulS(s.q, q0, e);                                                        // q (x) (1, phi)
-    return s;
-}
 // minimal_to_maximal_jacobian (src/gradients/state.jl:136-181): one thread per environment, root -> leaves;
 // Jm[env][12 Nb rows][2 nu columns] row-major.  z must already hold minimal_to_maximal(x).
 template <class TIO>
@@ -303,7 +295,7 @@ __global__ void min2max_jac_kernel(const NodeP<double>* nodes, const int* order,
             dth[i] = i < nr ? D24::seed((double)xm[nt + i], 12 + nt + i) : D24(0.0);    dw[i] = i < nr ? D24::seed((double)xm[n + nt + i], 12 + n + nt + i) : D24(0.0);
         }
         const PoseVel<double> a0 = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
-        PoseVel<D24> a = seed_body<TIO>(a0, 0), b;
+        PoseVel<D24> a = seed_body<24>(a0, 0), b;
         joint_min2max(b, P, dt, a, dx, dth, dv, dw);
         // rows of the child: x, v, phi = V(q_b^-1 (x) dq_b), omega
         double Pm[12][24];
@@ -338,7 +330,7 @@ __global__ void max2min_jac_kernel(const NodeP<double>* nodes, int Nb, double dt
     const int nt = P.nu_t, nr = P.nu_r, n = nt + nr;
     PoseVel<double> b0 = load_body<double>(ze, k), a0 = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
     if (advance) { advance_body(b0, dt); if (P.parent >= 0) advance_body(a0, dt); }
-    PoseVel<D24> a = seed_body<TIO>(a0, 0), b = seed_body<TIO>(b0, 12);
+    PoseVel<D24> a = seed_body<24>(a0, 0), b = seed_body<24>(b0, 12);
     D24 ct[3], cr[3], vt[3], vr[3];
     joint_max2min(ct, cr, vt, vr, P, dt, a, b);
     double* o = Jb + ((size_t)env * Nb + k) * 12 * 24;
@@ -1006,25 +998,34 @@ int launch_observation_jacobian(const DojoSim* s, const void* z_first, const voi
     HIPCHK(hipGetLastError());
     return DOJO_OK;
 }
+// what the two closed-loop sweeps are given alike (padjoint::Common), from the ABI records of either entry: a is a DojoPolicyAdjoint or a DojoMlpAdjoint, p its policy
+template <class TIO, class Rec, class Pol>
+dj::padjoint::Common<TIO> closed_loop_common(const DojoSim* s, const Pol& p, int H, const Rec& a, const double* M) {
+    dj::padjoint::Common<TIO> c{};
+    c.DZ = (const TIO*)a.DZ; c.DU = (const TIO*)a.DU; c.OBS = (const TIO*)a.OBS; c.M = M; c.G = (const TIO*)a.G; c.Z = (const TIO*)a.Z;
+    c.G_u = (const TIO*)a.G_u; c.G_obs = (const TIO*)a.G_obs; c.status = a.status; c.mean = (const TIO*)p.mean; c.scale = (const TIO*)p.scale;
+    c.touch = dj::padjoint::Touch{s->d_touch_ptr, s->d_touch_ent};
+    c.gU = (TIO*)a.gU; c.gz = (TIO*)a.gz;
+    c.H = H; c.B = s->B; c.nx = 12 * s->M.Nb; c.nu = (int)s->M.nu; c.nobs = 2 * c.nu; c.act_off = p.act_off; c.per_env = p.per_env ? 1 : 0; c.cot_space = a.cot_space;
+    return c;
+}
+// shared policy: the sum over the batch of the per-environment accumulators acc [B][nacc]; the entries [0, nW) go to gW, the rest to gbias (each may be null)
+template <class TIO>
+int launch_policy_reduce(const DojoSim* s, const double* acc, int nacc, int nW, void* gW, void* gbias, hipStream_t st) {
+    const int per = dj::padjoint::THREADS / dj::adjoint::ROW;
+    hipLaunchKernelGGL((dj::padjoint::policy_reduce_kernel<TIO>), dim3((unsigned)((nacc + per - 1) / per)), dim3(dj::padjoint::THREADS), 0, st, acc, s->B, nacc, nW, (TIO*)gW, (TIO*)gbias);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
 // dojo_rollout_policy_adjoint_dev: the closed-loop reverse sweep (one workgroup per environment, one launch) and, for a shared policy, the reduction over the batch
 template <class TIO>
 int launch_policy_adjoint(const DojoSim* s, const DojoPolicy& p, int H, const DojoPolicyAdjoint& a, const double* M, double* acc, hipStream_t st) {
-    const int nx = 12 * s->M.Nb, nu = (int)s->M.nu, nobs = 2 * nu, na = p.na;
     dj::padjoint::Args<TIO> A{};
-    A.DZ = (const TIO*)a.DZ; A.DU = (const TIO*)a.DU; A.OBS = (const TIO*)a.OBS; A.M = M; A.G = (const TIO*)a.G; A.Z = (const TIO*)a.Z;
-    A.G_u = (const TIO*)a.G_u; A.G_obs = (const TIO*)a.G_obs; A.status = a.status; A.W = (const TIO*)p.W; A.mean = (const TIO*)p.mean; A.scale = (const TIO*)p.scale;
-    A.touch = dj::padjoint::Touch{s->d_touch_ptr, s->d_touch_ent};
-    A.gW = acc ? nullptr : (TIO*)a.gW; A.gbias = acc ? nullptr : (TIO*)a.gbias; A.acc_out = acc; A.gU = (TIO*)a.gU; A.gz = (TIO*)a.gz;
-    A.H = H; A.B = s->B; A.nx = nx; A.nu = nu; A.nobs = nobs; A.act_off = p.act_off; A.na = na; A.per_env = p.per_env ? 1 : 0; A.cot_space = a.cot_space;
-    hipLaunchKernelGGL((dj::padjoint::rollout_policy_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::padjoint::THREADS), dj::padjoint::lds_bytes(nx, nu, nobs, na), st, A);
+    A.c = closed_loop_common<TIO>(s, p, H, a, M);
+    A.W = (const TIO*)p.W; A.gW = acc ? nullptr : (TIO*)a.gW; A.gbias = acc ? nullptr : (TIO*)a.gbias; A.acc_out = acc; A.na = p.na;
+    hipLaunchKernelGGL((dj::padjoint::rollout_policy_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::padjoint::THREADS), dj::padjoint::lds_bytes(A.c.nx, A.c.nu, A.c.nobs, A.na), st, A);
     HIPCHK(hipGetLastError());
-    if (acc) {
-        const int nacc = na * (nobs + 1), per = dj::padjoint::THREADS / dj::adjoint::ROW;
-        hipLaunchKernelGGL((dj::padjoint::policy_reduce_kernel<TIO>), dim3((unsigned)((nacc + per - 1) / per)), dim3(dj::padjoint::THREADS), 0, st, (const double*)acc, s->B, nacc, na * nobs,
-                           (TIO*)a.gW, (TIO*)a.gbias);
-        HIPCHK(hipGetLastError());
-    }
-    return DOJO_OK;
+    return acc ? launch_policy_reduce<TIO>(s, acc, A.na * (A.c.nobs + 1), A.na * A.c.nobs, a.gW, a.gbias, st) : DOJO_OK;
 }
 // a workspace of the handle whose size depends on the call: kept while it is large enough, replaced (hipFree waits for the device) when it is not
 int ensure_at_least(DojoSim* s, void** p, size_t* have, size_t bytes) {
@@ -1140,24 +1141,13 @@ int launch_controller(const DojoSim* s, const Controller& c, int k, const void* 
 // dojo_rollout_mlp_adjoint_dev: the sweep (one workgroup per environment, one launch) and, for a shared policy, the reduction over the batch
 template <class TIO>
 int launch_mlp_adjoint(const DojoSim* s, const DojoMlpPolicy& p, const dj::mlp::Shape& sh, int H, const DojoMlpAdjoint& a, const double* M, double* ws, hipStream_t st) {
-    const int nx = 12 * s->M.Nb, nu = (int)s->M.nu, nobs = 2 * nu;
     dj::mlp::AdjointArgs<TIO> A{};
-    A.DZ = (const TIO*)a.DZ; A.DU = (const TIO*)a.DU; A.OBS = (const TIO*)a.OBS; A.ACT = a.ACT; A.M = M; A.G = (const TIO*)a.G; A.Z = (const TIO*)a.Z;
-    A.G_u = (const TIO*)a.G_u; A.G_obs = (const TIO*)a.G_obs; A.status = a.status; A.theta = (const TIO*)p.theta; A.mean = (const TIO*)p.mean; A.scale = (const TIO*)p.scale;
-    A.touch = dj::padjoint::Touch{s->d_touch_ptr, s->d_touch_ent};
-    A.ws = ws; A.gtheta = (TIO*)a.gtheta; A.gU = (TIO*)a.gU; A.gz = (TIO*)a.gz;
-    A.H = H; A.B = s->B; A.nx = nx; A.nu = nu; A.nobs = nobs; A.act_off = p.act_off; A.per_env = p.per_env ? 1 : 0; A.shared = p.per_env ? 0 : 1; A.cot_space = a.cot_space;
-    A.P = (int)sh.P; A.s = sh;
-    hipLaunchKernelGGL((dj::mlp::rollout_mlp_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::padjoint::THREADS), dj::mlp::adjoint_lds_bytes(nx, nu, nobs, sh.wmax, sh.nh), st, A);
+    A.c = closed_loop_common<TIO>(s, p, H, a, M);
+    A.ACT = a.ACT; A.theta = (const TIO*)p.theta; A.ws = ws; A.gtheta = (TIO*)a.gtheta; A.shared = p.per_env ? 0 : 1; A.P = (int)sh.P; A.s = sh;
+    hipLaunchKernelGGL((dj::mlp::rollout_mlp_adjoint_kernel<TIO>), dim3((unsigned)s->B), dim3(dj::padjoint::THREADS), dj::mlp::adjoint_lds_bytes(A.c.nx, A.c.nu, A.c.nobs, sh.wmax, sh.nh), st, A);
     HIPCHK(hipGetLastError());
-    if (!p.per_env && a.gtheta) {
-        const int nacc = (int)sh.P, per = dj::padjoint::THREADS / dj::adjoint::ROW;
-        // at n_layers = 1 theta is [W | bias], the order of the affine sweep's accumulators: every entry goes to the one output
-        hipLaunchKernelGGL((dj::padjoint::policy_reduce_kernel<TIO>), dim3((unsigned)((nacc + per - 1) / per)), dim3(dj::padjoint::THREADS), 0, st, (const double*)ws, s->B, nacc, nacc,
-                           (TIO*)a.gtheta, (TIO*)nullptr);
-        HIPCHK(hipGetLastError());
-    }
-    return DOJO_OK;
+    // at n_layers = 1 theta is [W | bias], the order of the affine sweep's accumulators: every entry goes to the one output
+    return (!p.per_env && a.gtheta) ? launch_policy_reduce<TIO>(s, ws, (int)sh.P, (int)sh.P, a.gtheta, nullptr, st) : DOJO_OK;
 }
 
 } // namespace

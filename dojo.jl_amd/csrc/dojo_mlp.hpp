@@ -13,14 +13,15 @@
 // theta is one flat vector per policy, layer after layer: W_l row-major [n_l][n_{l-1}], then b_l [n_l]; P = sum_l n_l (n_{l-1} + 1) entries.
 //
 // rollout_mlp_kernel  one wavefront per environment, four per 256-lane workgroup (the mapping of rollout_policy_kernel).
-//   Phase A  the observation, as rollout_policy_kernel forms it (restated in observe() below, so that that kernel's code does not move); h_0 to LDS.
+//   Phase A  the observation: policy::observe, the function rollout_policy_kernel calls; h_0 to LDS.
 //   Layers   per output i of a layer: lane j accumulates W_l[i][j] h_{l-1}[j], W_l[i][j + 64] h_{l-1}[j + 64], ... with fma in ascending order, the 64
 //            partial sums meet in policy::wave_sum, b_l[i] is added in front.  Lane i mod 64 keeps p_l[i]; after 64 outputs (or the layer's last) every
 //            lane takes the tanh of its own at once -- one tanh per 64 outputs, not one per output -- and h_l goes to LDS and to ACT.  A barrier
 //            separates the layers.  The output layer is phase B of rollout_policy_kernel.
 //   LDS: [4][nobs + nh] doubles, nh = n_1 + .. + n_{L-1}.  No atomics; the summation order is fixed by the widths alone.
 //
-// rollout_mlp_adjoint_kernel  one workgroup of 256 lanes per environment, one launch for all H steps: rollout_policy_adjoint_kernel with phase (i)
+// rollout_mlp_adjoint_kernel  one workgroup of 256 lanes per environment, one launch for all H steps: rollout_policy_adjoint_kernel (its argument
+//   record padjoint::Common, its per-workgroup padjoint::Closed, the step loop adjoint::sweep) with the middle of phase (i)
 //   replaced by back-propagation through the layers, h_l read from the recorded ACT[k][b] (no tanh, no forward pass):
 //
 //     delta_L = gu[act_off .. act_off + na - 1]          (gu = DU_k^T lambda + GU_k -> gU[k])
@@ -94,55 +95,18 @@ template <class TIO> struct Args {
 };
 
 template <class TIO> struct AdjointArgs {
-    const TIO* DZ;          // [H][B][nx][nx]
-    const TIO* DU;          // [H][B][nu][nx]
-    const TIO* OBS;         // [H+1][B][nobs]
+    padjoint::Common<TIO> c;
     const double* ACT;      // [H][B][nh] (null with L = 1)
-    const double* M;        // [H+1][B][nobs][24] compact observation Jacobians (M[H] is read only with G_obs)
-    const TIO* G;           // [H][B][nx] (cot_space 0) or [H][B][13 Nb] (cot_space 1)
-    const TIO* Z;           // [H][B][13 Nb], cot_space 1 only
-    const TIO* G_u;         // [H][B][nu] or null
-    const TIO* G_obs;       // [H+1][B][nobs] or null
-    const int* status;      // [H][B] or null
-    const TIO *theta, *mean, *scale;    // [Bw][P], [nobs] or null, [nobs] or null
-    padjoint::Touch touch;
+    const TIO* theta;       // [Bw][P]
     double* ws;             // [B][P] fp64: the accumulators between the steps; with `shared` the result as well
     TIO* gtheta;            // [B][P], one policy per environment (may be null); unused with `shared`
-    TIO* gU;                // [H][B][nu] or null
-    TIO* gz;                // [B][nx] or null
-    int H, B, nx, nu, nobs, act_off, per_env, shared, cot_space, P;
+    int shared, P;
     Shape s;
 };
 
 #if defined(__HIPCC__)
 // the activation of the hidden layers: the device library's fp64 tanh
 __device__ __forceinline__ double activation(double p) { return ::tanh(p); }
-
-// Phase A of rollout_policy_kernel for one live wavefront: o rounded to the ABI type goes to obs (if given), (o - mean) .* scale to oh
-template <class TIO, class A_>
-__device__ __forceinline__ void observe(const A_& A, const NodeP<double>* nodes, const TIO* ze, const TIO* csg, const TIO* mean, const TIO* scale, size_t env, int lane,
-                                        TIO* obs, double* oh) {
-    using namespace coords;
-    constexpr int WAVE = policy::WAVE;
-    const int Nb = A.Nb, nu = A.nu, Nc = A.Nc;
-    auto put = [&](int j, double v) {
-        const TIO r = (TIO)v;
-        if (obs) obs[j] = r;
-        oh[j] = ((double)r - (mean ? (double)mean[j] : 0.0)) * (scale ? (double)scale[j] : 1.0);
-    };
-    for (int k = lane; k < Nb; k += WAVE) {
-        const NodeP<double>& P = nodes[k];
-        const int nt = P.nu_t, nr = P.nu_r, n = nt + nr, o = 2 * P.u_off;
-        double ct[3], cr[3], vt[3], vr[3];
-        const PoseVel<double> b = load_body<double>(ze, k), a = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
-        joint_max2min(ct, cr, vt, vr, P, A.dt, a, b);
-        for (int i = 0; i < 3; ++i) { if (i < nt) { put(o + i, ct[i]); put(o + n + i, vt[i]); } if (i < nr) { put(o + nt + i, cr[i]); put(o + n + nt + i, vr[i]); } }
-    }
-    for (int c = lane; c < Nc; c += WAVE) {
-        const double g = csg ? (double)csg[env * 8 * Nc + 8 * c + 4] : 1.0;
-        put(2 * nu + c, g < -1.0 ? -1.0 : g > 1.0 ? 1.0 : g);
-    }
-}
 
 template <class TIO>
 __global__ void __launch_bounds__(policy::THREADS) rollout_mlp_kernel(const Args<TIO> A) {
@@ -159,7 +123,7 @@ __global__ void __launch_bounds__(policy::THREADS) rollout_mlp_kernel(const Args
     const TIO* const mean = DJ_GLOBAL_PTR(const TIO, A.mean); const TIO* const scale = DJ_GLOBAL_PTR(const TIO, A.scale);
     TIO* const obs = A.obs ? DJ_GLOBAL_PTR(TIO, A.obs) + env * nobs : nullptr;
     double* const hs = lds_ + (size_t)wave * (nobs + nh);
-    if (live) observe<TIO>(A, nodes, ze, csg, mean, scale, env, lane, obs, hs);
+    if (live) policy::observe<TIO>(A, nodes, ze, csg, mean, scale, env, lane, obs, hs);
     if (!A.u) return;                                                       // (uniform over the launch)
     __syncthreads();
     // (a wavefront whose environment does not exist does no work below, but reaches every barrier; `live` is uniform over the wavefront, so the DPP
@@ -213,122 +177,65 @@ __global__ void __launch_bounds__(policy::THREADS) rollout_mlp_kernel(const Args
 
 template <class TIO>
 __global__ void __launch_bounds__(padjoint::THREADS) rollout_mlp_adjoint_kernel(const AdjointArgs<TIO> A) {
-    using namespace adjoint;
-    typedef typename Piece<TIO>::type P;
+    constexpr int THREADS = padjoint::THREADS;
     extern __shared__ __align__(16) double lds_[];      // lambda [2][nx] | g [2][nx] | gu [nu] | go [nobs] | h_0 [nobs] | delta [2][wmax] | h_1 .. h_{L-1} [nh]
-    const int b = (int)blockIdx.x, tid = (int)threadIdx.x, team = tid / ROW, j = tid % ROW;
-    const int H = A.H, B = A.B, nx = A.nx, nu = A.nu, nobs = A.nobs, act_off = A.act_off, L = A.s.L, nh = A.s.nh, wmax = A.s.wmax, na = A.s.width[L];
-    const TIO* const G = DJ_GLOBAL_PTR(const TIO, A.G);   const TIO* const Z = DJ_GLOBAL_PTR(const TIO, A.Z);
-    const TIO* const OBS = DJ_GLOBAL_PTR(const TIO, A.OBS); const double* const M = DJ_GLOBAL_PTR(const double, A.M);
+    const padjoint::Closed<TIO> S(A.c, lds_);
+    const int b = S.b, tid = S.tid, H = A.c.H, B = S.B, nx = S.nx, L = A.s.L, nh = A.s.nh, wmax = A.s.wmax, na = A.s.width[L];
     const double* const ACT = DJ_GLOBAL_PTR(const double, A.ACT);
-    const TIO* const GU = DJ_GLOBAL_PTR(const TIO, A.G_u); const TIO* const GO = DJ_GLOBAL_PTR(const TIO, A.G_obs);
-    const TIO* const theta = DJ_GLOBAL_PTR(const TIO, A.theta) + (A.per_env ? (size_t)b : (size_t)0) * (size_t)A.P;
-    const TIO* const mean = DJ_GLOBAL_PTR(const TIO, A.mean); const TIO* const scale = DJ_GLOBAL_PTR(const TIO, A.scale);
-    const int* const status = DJ_GLOBAL_PTR(const int, A.status);
-    const int* const tptr = DJ_GLOBAL_PTR(const int, A.touch.ptr); const int* const tent = DJ_GLOBAL_PTR(const int, A.touch.ent);
-    TIO* const gU = DJ_GLOBAL_PTR(TIO, A.gU); TIO* const gz = DJ_GLOBAL_PTR(TIO, A.gz);
+    const TIO* const theta = DJ_GLOBAL_PTR(const TIO, A.theta) + (A.c.per_env ? (size_t)b : (size_t)0) * (size_t)A.P;
     double* const ws = DJ_GLOBAL_PTR(double, A.ws) + (size_t)b * (size_t)A.P;
     TIO* const gth = (!A.shared && A.gtheta) ? DJ_GLOBAL_PTR(TIO, A.gtheta) + (size_t)b * (size_t)A.P : nullptr;
-    const Columns<TIO> C = columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DU), B, nx, nu, nu);
-    double* const lam_ = lds_; double* const g_ = lds_ + 2 * nx; double* const gu_ = lds_ + 4 * nx; double* const go_ = gu_ + nu;
-    double* const oh_ = go_ + nobs; double* const dl_ = oh_ + nobs; double* const hk_ = dl_ + 2 * wmax;
-    const adjoint::Args<TIO> AG{nullptr, nullptr, A.G, A.Z, nullptr, nullptr, nullptr, H, B, nx, nu, A.cot_space};
+    double* const dl_ = S.rest(); double* const hk_ = dl_ + 2 * wmax;
+    // h_1 .. h_{L-1} of step k from the recorded ACT[k] (h_0 is the affine sweep's ohat)
+    auto put_act = [&](int k) { for (int i = tid; i < nh; i += THREADS) hk_[i] = ACT[((size_t)k * B + b) * nh + i]; };
 
-    auto failed = [&](int k) { return status != nullptr && status[(size_t)k * B + b] != 0; };
-    auto items_of = [&](int k) { return (k < 0 || failed(k)) ? 0 : items(C, 0); };
-    // M_k^T go for column c: the rows that touch the column's body, in the order of the table
-    auto pull = [&](int k, int c) {
-        const int body = c / 12, col = c - 12 * body;
-        const double* const Mk = M + ((size_t)k * B + b) * nobs * 24;
-        double s = 0.0;
-        for (int e = tptr[body]; e < tptr[body + 1]; ++e) { const int rh = tent[e], r = rh >> 1; s = fma(Mk[(size_t)r * 24 + (rh & 1) * 12 + col], go_[r], s); }
-        return s;
-    };
-    // h_0 of step k from the recorded OBS[k], h_1 .. h_{L-1} from the recorded ACT[k]
-    auto put_h = [&](int k) {
-        for (int i = tid; i < nobs; i += THREADS)
-            oh_[i] = ((double)OBS[((size_t)k * B + b) * nobs + i] - (mean ? (double)mean[i] : 0.0)) * (scale ? (double)scale[i] : 1.0);
-        for (int i = tid; i < nh; i += THREADS) hk_[i] = ACT[((size_t)k * B + b) * nh + i];
-    };
-
-    for (int c = tid; c < nx; c += THREADS) g_[((H - 1) & 1) * nx + c] = cotangent(AG, G, Z, H - 1, b, c);
-    put_h(H - 1);
-    if (GO) {                                                               // lambda <- M_H^T GO_H  (+ g_{H-1}, where it is read)
-        for (int i = tid; i < nobs; i += THREADS) go_[i] = (double)GO[((size_t)H * B + b) * nobs + i];
-        __syncthreads();
-        for (int c = tid; c < nx; c += THREADS) lam_[c] = pull(H, c);
-    } else
-        for (int c = tid; c < nx; c += THREADS) lam_[c] = 0.0;
-    int p = 0, nit = items_of(H - 1);
-    P buf0[COLS], buf1[COLS];
-    if (nit) issue(C, H - 1, b, 0, 0, team, j, buf0);
-    __syncthreads();
-    for (int k = H - 1; k >= 0; --k) {
-        const double* lam = lam_ + p * nx; const double* gk = g_ + (k & 1) * nx; double* lam_next = lam_ + (p ^ 1) * nx;
-        const int nit_next = items_of(k - 1);
-        const size_t kb = (size_t)k * B + b;
-        if (k > 0) for (int c = tid; c < nx; c += THREADS) g_[((k - 1) & 1) * nx + c] = cotangent(AG, G, Z, k - 1, b, c);
-        double acc[COLS];
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) acc[i] = 0.0;
-        auto put = [&](int c, double mine) { if (c >= nx) gu_[c - nx] = mine; else lam_next[c] = mine; };
-        auto stage = [&](int it, const P (&cur)[COLS], P (&nxt)[COLS]) {
-            const bool more = it + 1 < nit;
-            issue(C, (more || !nit_next) ? k : k - 1, b, 0, more ? it + 1 : nit_next ? 0 : it, team, j, nxt);
-            consume(C, 0, it, team, j, lam, gk, cur, acc, put);
-        };
-        for (int it = 0; it < nit; it += 2) { stage(it, buf0, buf1); stage(it + 1, buf1, buf0); }
-        if (failed(k)) {                                                    // nothing flows through a failed step: DZ^T lambda = 0, DU^T lambda = 0
-            for (int c = tid; c < nx; c += THREADS) lam_next[c] = 0.0;
-            for (int c = tid; c < nu; c += THREADS) gu_[c] = 0.0;
-            if (nit_next) issue(C, k - 1, b, 0, 0, team, j, buf0);
-        }
-        __syncthreads();
-        // ---- phase (i): gu -> gU; delta_L = gu[act_off ..] + GU[act_off ..] to LDS ----
-        if (gU) for (int c = tid; c < nu; c += THREADS) gU[kb * nu + c] = (TIO)(gu_[c] + (GU ? (double)GU[kb * nu + c] : 0.0));
-        int cur = 0;
-        for (int i = tid; i < na; i += THREADS) dl_[i] = gu_[act_off + i] + (GU ? (double)GU[kb * nu + act_off + i] : 0.0);
-        __syncthreads();
-        // ---- back-propagation, l = L .. 1: the accumulators of layer l, then delta_{l-1} (l = 1: go) ----
-        const bool first = k == H - 1, last = k == 0;
-        for (int l = L; l >= 1; --l) {
-            const int nin = A.s.width[l - 1], nout = A.s.width[l], t0 = A.s.toff[l - 1], nW = nout * nin;
-            const double* const dl = dl_ + cur * wmax; double* const dprev = dl_ + (cur ^ 1) * wmax;
-            const double* const hin = l == 1 ? oh_ : hk_ + A.s.hoff[l - 1];
-            // entry e = r nin + c of W_l: (r, c) advance by 256 without a division inside the loop
-            {
-                const int qs = THREADS / nin, rs = THREADS - qs * nin;
-                int r = tid / nin, c = tid - r * nin;
-                for (int e = tid; e < nW; e += THREADS) {
-                    const double v = fma(dl[r], hin[c], first ? 0.0 : ws[t0 + e]);
-                    if (!last || A.shared) ws[t0 + e] = v; else if (gth) gth[t0 + e] = (TIO)v;
-                    r += qs; c += rs; if (c >= nin) { c -= nin; ++r; }
-                }
-                for (int e = tid; e < nout; e += THREADS) {
-                    const double v = (first ? 0.0 : ws[t0 + nW + e]) + dl[e];
-                    if (!last || A.shared) ws[t0 + nW + e] = v; else if (gth) gth[t0 + nW + e] = (TIO)v;
-                }
-            }
-            const TIO* const W = theta + t0;
-            for (int i = tid; i < nin; i += THREADS) {
-                double s = 0.0;
-                for (int r = 0; r < nout; ++r) s = fma((double)W[(size_t)r * nin + i], dl[r], s);
-                if (l > 1) dprev[i] = s * fma(-hin[i], hin[i], 1.0);
-                else go_[i] = (scale ? (double)scale[i] : 1.0) * s + (GO ? (double)GO[kb * nobs + i] : 0.0);
-            }
-            cur ^= 1;
+    S.put_ohat(H - 1); put_act(H - 1);
+    S.first_lambda(H, lds_);
+    adjoint::sweep(S.columns(A.c), adjoint::cot_of<TIO>(A.c), DJ_GLOBAL_PTR(const int, A.c.status), H, b, lds_, lds_ + 2 * nx,
+        [](int) { return 0; },
+        [&](int, int c, double mine, double* lam_next) { S.put(c, mine, lam_next); },
+        [&](int, double* lam_next) { S.failed_step(lam_next); },
+        [&](int k, double* lam_next) {
+            // ---- phase (i): gu -> gU; delta_L = gu[act_off ..] + GU[act_off ..] to LDS ----
+            S.round_gU(k);
+            int cur = 0;
+            for (int i = tid; i < na; i += THREADS) dl_[i] = S.act(k, i);
             __syncthreads();
-        }
-        // ---- phase (ii): lam_next += M_k^T go; the activations of the next step to come go to LDS (their last reader was the loop above) ----
-        for (int c = tid; c < nx; c += THREADS) {
-            const double v = lam_next[c] + pull(k, c);
-            if (k > 0) lam_next[c] = v;
-            else if (gz) gz[(size_t)b * nx + c] = (TIO)v;
-        }
-        if (k > 0) put_h(k - 1);
-        __syncthreads();
-        p ^= 1; nit = nit_next;
-    }
+            // ---- back-propagation, l = L .. 1: the accumulators of layer l, then delta_{l-1} (l = 1: go) ----
+            const bool first = k == H - 1, last = k == 0;
+            for (int l = L; l >= 1; --l) {
+                const int nin = A.s.width[l - 1], nout = A.s.width[l], t0 = A.s.toff[l - 1], nW = nout * nin;
+                const double* const dl = dl_ + cur * wmax; double* const dprev = dl_ + (cur ^ 1) * wmax;
+                const double* const hin = l == 1 ? S.oh_ : hk_ + A.s.hoff[l - 1];
+                // entry e = r nin + c of W_l: (r, c) advance by 256 without a division inside the loop
+                {
+                    const int qs = THREADS / nin, rs = THREADS - qs * nin;
+                    int r = tid / nin, c = tid - r * nin;
+                    for (int e = tid; e < nW; e += THREADS) {
+                        const double v = fma(dl[r], hin[c], first ? 0.0 : ws[t0 + e]);
+                        if (!last || A.shared) ws[t0 + e] = v; else if (gth) gth[t0 + e] = (TIO)v;
+                        r += qs; c += rs; if (c >= nin) { c -= nin; ++r; }
+                    }
+                    for (int e = tid; e < nout; e += THREADS) {
+                        const double v = (first ? 0.0 : ws[t0 + nW + e]) + dl[e];
+                        if (!last || A.shared) ws[t0 + nW + e] = v; else if (gth) gth[t0 + nW + e] = (TIO)v;
+                    }
+                }
+                const TIO* const W = theta + t0;
+                for (int i = tid; i < nin; i += THREADS) {
+                    double s = 0.0;
+                    for (int r = 0; r < nout; ++r) s = fma((double)W[(size_t)r * nin + i], dl[r], s);
+                    if (l > 1) dprev[i] = s * fma(-hin[i], hin[i], 1.0);
+                    else S.set_go(k, i, s);
+                }
+                cur ^= 1;
+                __syncthreads();
+            }
+            // ---- phase (ii); the activations of the next step to come go to LDS as well (their last reader was the loop above) ----
+            S.phase_ii(k, lam_next);
+            if (k > 0) put_act(k - 1);
+            __syncthreads();
+        });
 }
 #endif
 

@@ -15,8 +15,8 @@
 //
 // Mapping: one wavefront per environment, four environments per 256-lane workgroup.  The work is tiny (the Ant of AntARS: 13 joint maps, 9 contacts, an 8 x 37
 // mat-vec, 1.2 KB of W), so the goal is one launch without scratch memory and a short latency, not throughput.
-//   Phase A  lane l takes the joints l, l + 64, ...: coords::load_body + coords::joint_max2min, the source max2min_kernel is made of; lanes take the contacts
-//            the way contact_obs_kernel does.  The rounded o goes to OBS (if given), ohat to LDS as fp64 ([4][nobs]).
+//   Phase A  (observe(), shared with the network controller of dojo_mlp.hpp) lane l takes the joints l, l + 64, ...: coords::load_body +
+//            coords::joint_max2min, the source max2min_kernel is made of; lanes take the contacts the way contact_obs_kernel does.  The rounded o goes to OBS (if given), ohat to LDS as fp64 ([4][nobs]).
 //   barrier  (every wavefront of the workgroup reaches it: a wavefront whose environment does not exist does no work, but does not return before it)
 //   Phase B  per action i: lane j accumulates W[i][j] ohat_j, W[i][j + 64] ohat_{j + 64}, ... with fma in ascending order (loads coalesced along nobs);
 //            the 64 partial sums meet in a fixed order: four DPP row rotations inside every 16-lane row (adjoint::row_sum), then the four row sums
@@ -59,41 +59,47 @@ __device__ __forceinline__ double wave_sum(double v) {
     return ((lane_value(v, 0) + lane_value(v, 16)) + lane_value(v, 32)) + lane_value(v, 48);
 }
 
-template <class TIO>
-__global__ void __launch_bounds__(THREADS) rollout_policy_kernel(const Args<TIO> A) {
+// Phase A for one live wavefront, of this controller and of the network's (dojo_mlp.hpp; A: either argument record): o rounded to the ABI type goes to obs
+// (if given) -- recorded, and what the policy consumes -- and (o - mean) .* scale to oh
+template <class TIO, class A_>
+__device__ __forceinline__ void observe(const A_& A, const NodeP<double>* nodes, const TIO* ze, const TIO* csg, const TIO* mean, const TIO* scale, size_t env, int lane,
+                                        TIO* obs, double* oh) {
     using namespace coords;
-    extern __shared__ __align__(16) double lds_[];                          // ohat [ENVS][nobs]
-    const int tid = (int)threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
-    const int e = (int)blockIdx.x * ENVS + wave;
-    const bool live = e < A.nenv;
-    const size_t env = (size_t)A.env0 + (live ? e : 0);
-    const int Nb = A.Nb, nu = A.nu, Nc = A.Nc, nobs = A.nobs;
-    const NodeP<double>* const nodes = DJ_GLOBAL_PTR(const NodeP<double>, A.nodes);
-    const TIO* const ze = DJ_GLOBAL_PTR(const TIO, A.z) + env * 13 * Nb;
-    const TIO* const csg = DJ_GLOBAL_PTR(const TIO, A.csg);
-    const TIO* const mean = DJ_GLOBAL_PTR(const TIO, A.mean); const TIO* const scale = DJ_GLOBAL_PTR(const TIO, A.scale);
-    TIO* const obs = A.obs ? DJ_GLOBAL_PTR(TIO, A.obs) + env * nobs : nullptr;
-    double* const oh = lds_ + wave * nobs;
-    // o[j] rounded to the ABI type: recorded, and what the policy consumes
+    const int Nb = A.Nb, nu = A.nu, Nc = A.Nc;
     auto put = [&](int j, double v) {
         const TIO r = (TIO)v;
         if (obs) obs[j] = r;
         oh[j] = ((double)r - (mean ? (double)mean[j] : 0.0)) * (scale ? (double)scale[j] : 1.0);
     };
-    if (live) {
-        for (int k = lane; k < Nb; k += WAVE) {
-            const NodeP<double>& P = nodes[k];
-            const int nt = P.nu_t, nr = P.nu_r, n = nt + nr, o = 2 * P.u_off;
-            double ct[3], cr[3], vt[3], vr[3];
-            const PoseVel<double> b = load_body<double>(ze, k), a = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
-            joint_max2min(ct, cr, vt, vr, P, A.dt, a, b);
-            for (int i = 0; i < 3; ++i) { if (i < nt) { put(o + i, ct[i]); put(o + n + i, vt[i]); } if (i < nr) { put(o + nt + i, cr[i]); put(o + n + nt + i, vr[i]); } }
-        }
-        for (int c = lane; c < Nc; c += WAVE) {
-            const double g = csg ? (double)csg[env * 8 * Nc + 8 * c + 4] : 1.0;
-            put(2 * nu + c, g < -1.0 ? -1.0 : g > 1.0 ? 1.0 : g);
-        }
+    for (int k = lane; k < Nb; k += WAVE) {
+        const NodeP<double>& P = nodes[k];
+        const int nt = P.nu_t, nr = P.nu_r, n = nt + nr, o = 2 * P.u_off;
+        double ct[3], cr[3], vt[3], vr[3];
+        const PoseVel<double> b = load_body<double>(ze, k), a = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
+        joint_max2min(ct, cr, vt, vr, P, A.dt, a, b);
+        for (int i = 0; i < 3; ++i) { if (i < nt) { put(o + i, ct[i]); put(o + n + i, vt[i]); } if (i < nr) { put(o + nt + i, cr[i]); put(o + n + nt + i, vr[i]); } }
     }
+    for (int c = lane; c < Nc; c += WAVE) {
+        const double g = csg ? (double)csg[env * 8 * Nc + 8 * c + 4] : 1.0;
+        put(2 * nu + c, g < -1.0 ? -1.0 : g > 1.0 ? 1.0 : g);
+    }
+}
+
+template <class TIO>
+__global__ void __launch_bounds__(THREADS) rollout_policy_kernel(const Args<TIO> A) {
+    extern __shared__ __align__(16) double lds_[];                          // ohat [ENVS][nobs]
+    const int tid = (int)threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
+    const int e = (int)blockIdx.x * ENVS + wave;
+    const bool live = e < A.nenv;
+    const size_t env = (size_t)A.env0 + (live ? e : 0);
+    const int nu = A.nu, nobs = A.nobs;
+    const NodeP<double>* const nodes = DJ_GLOBAL_PTR(const NodeP<double>, A.nodes);
+    const TIO* const ze = DJ_GLOBAL_PTR(const TIO, A.z) + env * 13 * A.Nb;
+    const TIO* const csg = DJ_GLOBAL_PTR(const TIO, A.csg);
+    const TIO* const mean = DJ_GLOBAL_PTR(const TIO, A.mean); const TIO* const scale = DJ_GLOBAL_PTR(const TIO, A.scale);
+    TIO* const obs = A.obs ? DJ_GLOBAL_PTR(TIO, A.obs) + env * nobs : nullptr;
+    double* const oh = lds_ + wave * nobs;
+    if (live) observe<TIO>(A, nodes, ze, csg, mean, scale, env, lane, obs, oh);
     if (!A.u) return;                                                       // (uniform over the launch)
     __syncthreads();
     if (!live) return;                                                      // (uniform over the wavefront: the DPP sums below see all 64 lanes)

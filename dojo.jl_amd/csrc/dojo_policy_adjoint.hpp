@@ -22,9 +22,9 @@
 //       0..11 the derivative w.r.t. the tangent coordinates of the PARENT body of the joint that owns the row, 12..23 w.r.t. its CHILD body.  One thread
 //       per (state, environment, joint): the Dual<24> evaluation of coords::joint_max2min that max2min_jac_kernel is made of, rows placed where
 //       rollout_policy_kernel::put places the observation.  It is off the serial chain of the sweep, so its register cost is paid once.
-//   rollout_policy_adjoint_kernel  one workgroup of 256 lanes per environment, one launch for all H steps.  DZ and DU go through the column pipeline of
-//       dojo_adjoint.hpp (adjoint::issue / adjoint::consume: 16-byte loads, two register buffers that take turns, row_sum, the next item in flight across
-//       the barriers); gu lands in LDS as fp64.  Two short phases follow per step, each behind a barrier:
+//   rollout_policy_adjoint_kernel  one workgroup of 256 lanes per environment, one launch for all H steps.  DZ and DU go through the step loop of
+//       dojo_adjoint.hpp (adjoint::sweep: 16-byte loads, two register buffers that take turns, row_sum, the next item in flight across the barriers);
+//       gu lands in LDS as fp64.  Two short phases follow per step (the loop's `after` hook), each behind a barrier:
 //         (i)  lanes c < nu round gu to gU; lanes j < nobs form go_j = scale_j sum_i W[i][j] a_i + GO_j (i ascending, W read coalesced along nobs); the
 //              na nobs + na accumulators of gW / gbias live in LDS as fp64, entry e owned by lane e mod 256 (no races); ohat_k is in LDS, formed from the
 //              recorded OBS[k] one phase earlier.
@@ -33,6 +33,8 @@
 //              ohat_{k-1} goes to LDS.
 //       LDS: lambda and g double-buffered (4 nx), gu (nu), go and ohat (2 nobs), the accumulators (na (nobs + 1)) doubles: Ant 7 KB, Atlas 30 KB.
 //       All arithmetic is fp64, outputs are rounded once, no atomics: the summation order is fixed by (nx, nu, na, nobs, topology, dtype) alone.
+//       Everything but the middle of phase (i) -- W and the accumulators -- is shared with the network's sweep (dojo_mlp.hpp): the argument record
+//       Common and the per-workgroup Closed below.
 //   policy_reduce_kernel  shared policy (per_env = 0): the sweep leaves the per-environment accumulators as fp64 in a workspace [B][na (nobs + 1)]; sixteen
 //       lanes (a DPP row) share an entry, lane j adds the environments j, j + 16, ... in ascending order and the sixteen sums meet in adjoint::row_sum:
 //       an order fixed by B alone.  Rounded once.
@@ -50,7 +52,9 @@ constexpr int THREADS = adjoint::THREADS;
 // rows of M that touch a body, per body (CSR): entry = 2 row + half (half 1: the body is the child of the row's joint, columns 12..23)
 struct Touch { const int* ptr; const int* ent; };
 
-template <class TIO> struct Args {
+// what the two closed-loop sweeps (this one, and the network's in dojo_mlp.hpp) are given alike: the record, the cotangents, the outputs that do not
+// depend on the kind of policy, the sizes
+template <class TIO> struct Common {
     const TIO* DZ;          // [H][B][nx][nx]
     const TIO* DU;          // [H][B][nu][nx]
     const TIO* OBS;         // [H+1][B][nobs]
@@ -60,28 +64,24 @@ template <class TIO> struct Args {
     const TIO* G_u;         // [H][B][nu] or null
     const TIO* G_obs;       // [H+1][B][nobs] or null
     const int* status;      // [H][B] or null
-    const TIO *W, *mean, *scale;    // [Bw][na][nobs], [nobs] or null, [nobs] or null
+    const TIO *mean, *scale;    // [nobs] or null, [nobs] or null
     Touch touch;
-    TIO *gW, *gbias;        // per_env 1: [B][na][nobs], [B][na] (each may be null)
-    double* acc_out;        // per_env 0: [B][na (nobs + 1)] fp64 workspace (gW rows, then gbias), or null
     TIO* gU;                // [H][B][nu] or null
     TIO* gz;                // [B][nx] or null
-    int H, B, nx, nu, nobs, act_off, na, per_env, cot_space;
+    int H, B, nx, nu, nobs, act_off, per_env, cot_space;
+};
+template <class TIO> struct Args {
+    Common<TIO> c;
+    const TIO* W;           // [Bw][na][nobs]
+    TIO *gW, *gbias;        // per_env 1: [B][na][nobs], [B][na] (each may be null)
+    double* acc_out;        // per_env 0: [B][na (nobs + 1)] fp64 workspace (gW rows, then gbias), or null
+    int na;
 };
 
 inline size_t lds_bytes(int nx, int nu, int nobs, int na) { return ((size_t)4 * nx + nu + 2 * (size_t)nobs + (size_t)na * (nobs + 1)) * sizeof(double); }
 
 #if defined(__HIPCC__)
 typedef coords::Dual<24> D24;
-// a body state seeded with its 12 tangent directions [x, v, phi, omega] starting at direction d0: q (x) (1, phi)
-__device__ __forceinline__ coords::PoseVel<D24> seed_body(const coords::PoseVel<double>& p, int d0) {
-    using namespace coords;
-    PoseVel<D24> s;
-    for (int i = 0; i < 3; ++i) { s.x[i] = D24::seed(p.x[i], d0 + i); s.v[i] = D24::seed(p.v[i], d0 + 3 + i); s.w[i] = D24::seed(p.w[i], d0 + 9 + i); }
-    D24 e[4] = {D24(1.0), D24::seed(0.0, d0 + 6), D24::seed(0.0, d0 + 7), D24::seed(0.0, d0 + 8)}, q0[4] = {D24(p.q[0]), D24(p.q[1]), D24(p.q[2]), D24(p.q[3])};
-    qmulS(s.q, q0, e);
-    return s;
-}
 
 // state 0 is read from z_first [B][13 Nb], the states 1 .. n-1 from z_rest [n-1][B][13 Nb] (a trajectory is (z0, Z); one array is (z, z + B 13 Nb))
 constexpr int JAC_THREADS = 128;      // (a bound on the workgroup size: the Dual<24> evaluation wants more than the 128 registers a 1024-lane bound leaves)
@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(JAC_THREADS) observation_jacobian_kernel(const
     const int nt = P.nu_t, nr = P.nu_r, nn = nt + nr;
     const bool has_parent = P.parent >= 0;
     const PoseVel<double> b0 = load_body<double>(ze, k), a0 = has_parent ? load_body<double>(ze, P.parent) : origin_body<double>();
-    const PoseVel<D24> a = seed_body(a0, 0), b = seed_body(b0, 12);
+    const PoseVel<D24> a = seed_body<24>(a0, 0), b = seed_body<24>(b0, 12);
     D24 ct[3], cr[3], vt[3], vr[3];
     joint_max2min(ct, cr, vt, vr, P, dt, a, b);
     double* const o = DJ_GLOBAL_PTR(double, M_) + ((size_t)sb * 2 * nu + 2 * P.u_off) * 24;
@@ -108,99 +108,107 @@ __global__ void __launch_bounds__(JAC_THREADS) observation_jacobian_kernel(const
     }
 }
 
-template <class TIO>
-__global__ void __launch_bounds__(THREADS) rollout_policy_adjoint_kernel(const Args<TIO> A) {
-    using namespace adjoint;
-    typedef typename Piece<TIO>::type P;
-    extern __shared__ __align__(16) double lds_[];      // lambda [2][nx] | g [2][nx] | gu [nu] | go [nobs] | ohat [nobs] | accumulators [na nobs + na]
-    const int b = (int)blockIdx.x, tid = (int)threadIdx.x, team = tid / ROW, j = tid % ROW;
-    const int H = A.H, B = A.B, nx = A.nx, nu = A.nu, nobs = A.nobs, na = A.na, act_off = A.act_off, nacc = na * nobs + na;
-    const TIO* const G = DJ_GLOBAL_PTR(const TIO, A.G);   const TIO* const Z = DJ_GLOBAL_PTR(const TIO, A.Z);
-    const TIO* const OBS = DJ_GLOBAL_PTR(const TIO, A.OBS); const double* const M = DJ_GLOBAL_PTR(const double, A.M);
-    const TIO* const GU = DJ_GLOBAL_PTR(const TIO, A.G_u); const TIO* const GO = DJ_GLOBAL_PTR(const TIO, A.G_obs);
-    const TIO* const W = DJ_GLOBAL_PTR(const TIO, A.W) + (A.per_env ? (size_t)b : (size_t)0) * na * nobs;
-    const TIO* const mean = DJ_GLOBAL_PTR(const TIO, A.mean); const TIO* const scale = DJ_GLOBAL_PTR(const TIO, A.scale);
-    const int* const status = DJ_GLOBAL_PTR(const int, A.status);
-    const int* const tptr = DJ_GLOBAL_PTR(const int, A.touch.ptr); const int* const tent = DJ_GLOBAL_PTR(const int, A.touch.ent);
-    TIO* const gU = DJ_GLOBAL_PTR(TIO, A.gU); TIO* const gz = DJ_GLOBAL_PTR(TIO, A.gz);
-    const Columns<TIO> C = columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DU), B, nx, nu, nu);
-    double* const lam_ = lds_; double* const g_ = lds_ + 2 * nx; double* const gu_ = lds_ + 4 * nx; double* const go_ = gu_ + nu;
-    double* const oh_ = go_ + nobs; double* const acc_ = oh_ + nobs;
-    // the cotangent of the state is the open-loop sweep's (adjoint::cotangent reads G, Z, B, nx, cot_space)
-    const adjoint::Args<TIO> AG{nullptr, nullptr, A.G, A.Z, nullptr, nullptr, nullptr, H, B, nx, nu, A.cot_space};
+// ---- what the two closed-loop sweeps do alike around adjoint::sweep, per workgroup (environment b) ----
+// LDS behind lambda and g: gu [nu] | go [nobs] | ohat [nobs], then the kernel's own (rest()).  A step of either sweep is
+//     the columns (put / failed_step): lam_next <- DZ_k^T lambda, gu <- DU_k^T lambda, or zeros
+//     phase (i), the kernel's own:     round_gU(k); a = act(k, .); the accumulators; set_go(k, j, sum_i W[i][j] a_i or delta_0[j])
+//     phase (ii):                      lam_next += M_k^T go (k = 0: -> gz); ohat_{k-1} to LDS
+// each behind a barrier.
+template <class TIO> struct Closed {
+    const TIO *OBS, *GU, *GO, *mean, *scale;
+    const double* M;
+    const int *tptr, *tent;
+    TIO *gU, *gz;
+    double *gu_, *go_, *oh_;
+    int b, tid, B, nx, nu, nobs, act_off;
 
-    auto failed = [&](int k) { return status != nullptr && status[(size_t)k * B + b] != 0; };
-    auto items_of = [&](int k) { return (k < 0 || failed(k)) ? 0 : items(C, 0); };
+    __device__ __forceinline__ Closed(const Common<TIO>& A, double* lds)
+        : OBS(DJ_GLOBAL_PTR(const TIO, A.OBS)), GU(DJ_GLOBAL_PTR(const TIO, A.G_u)), GO(DJ_GLOBAL_PTR(const TIO, A.G_obs)), mean(DJ_GLOBAL_PTR(const TIO, A.mean)),
+          scale(DJ_GLOBAL_PTR(const TIO, A.scale)), M(DJ_GLOBAL_PTR(const double, A.M)), tptr(DJ_GLOBAL_PTR(const int, A.touch.ptr)), tent(DJ_GLOBAL_PTR(const int, A.touch.ent)),
+          gU(DJ_GLOBAL_PTR(TIO, A.gU)), gz(DJ_GLOBAL_PTR(TIO, A.gz)), gu_(lds + 4 * A.nx), go_(gu_ + A.nu), oh_(go_ + A.nobs),
+          b((int)blockIdx.x), tid((int)threadIdx.x), B(A.B), nx(A.nx), nu(A.nu), nobs(A.nobs), act_off(A.act_off) {}
+    __device__ __forceinline__ double* rest() const { return oh_ + nobs; }
+    __device__ __forceinline__ adjoint::Columns<TIO> columns(const Common<TIO>& A) const {
+        return adjoint::columns<TIO>(DJ_GLOBAL_PTR(const TIO, A.DZ), DJ_GLOBAL_PTR(const TIO, A.DU), B, nx, nu, nu);
+    }
     // M_k^T go for column c: the rows that touch the column's body, in the order of the table
-    auto pull = [&](int k, int c) {
+    __device__ __forceinline__ double pull(int k, int c) const {
         const int body = c / 12, col = c - 12 * body;
         const double* const Mk = M + ((size_t)k * B + b) * nobs * 24;
         double s = 0.0;
         for (int e = tptr[body]; e < tptr[body + 1]; ++e) { const int rh = tent[e], r = rh >> 1; s = fma(Mk[(size_t)r * 24 + (rh & 1) * 12 + col], go_[r], s); }
         return s;
-    };
-    auto put_ohat = [&](int k) {
+    }
+    // ohat_k from the recorded, rounded OBS[k]
+    __device__ __forceinline__ void put_ohat(int k) const {
         for (int i = tid; i < nobs; i += THREADS)
             oh_[i] = ((double)OBS[((size_t)k * B + b) * nobs + i] - (mean ? (double)mean[i] : 0.0)) * (scale ? (double)scale[i] : 1.0);
-    };
-
-    for (int e = tid; e < nacc; e += THREADS) acc_[e] = 0.0;
-    for (int c = tid; c < nx; c += THREADS) g_[((H - 1) & 1) * nx + c] = cotangent(AG, G, Z, H - 1, b, c);
-    put_ohat(H - 1);
-    if (GO) {                                                               // lambda <- M_H^T GO_H  (+ g_{H-1}, where it is read)
-        for (int i = tid; i < nobs; i += THREADS) go_[i] = (double)GO[((size_t)H * B + b) * nobs + i];
-        __syncthreads();
-        for (int c = tid; c < nx; c += THREADS) lam_[c] = pull(H, c);
-    } else
-        for (int c = tid; c < nx; c += THREADS) lam_[c] = 0.0;
-    int p = 0, nit = items_of(H - 1);
-    P buf0[COLS], buf1[COLS];
-    if (nit) issue(C, H - 1, b, 0, 0, team, j, buf0);
-    __syncthreads();
-    for (int k = H - 1; k >= 0; --k) {
-        const double* lam = lam_ + p * nx; const double* gk = g_ + (k & 1) * nx; double* lam_next = lam_ + (p ^ 1) * nx;
-        const int nit_next = items_of(k - 1);
+    }
+    // lam_[0 .. nx) <- M_H^T GO_H  (+ g_{H-1}, where it is read); contains a barrier with G_obs, which is uniform over the launch
+    __device__ __forceinline__ void first_lambda(int H, double* lam_) const {
+        if (GO) {
+            for (int i = tid; i < nobs; i += THREADS) go_[i] = (double)GO[((size_t)H * B + b) * nobs + i];
+            __syncthreads();
+            for (int c = tid; c < nx; c += THREADS) lam_[c] = pull(H, c);
+        } else
+            for (int c = tid; c < nx; c += THREADS) lam_[c] = 0.0;
+    }
+    __device__ __forceinline__ void put(int c, double mine, double* lam_next) const { if (c >= nx) gu_[c - nx] = mine; else lam_next[c] = mine; }
+    __device__ __forceinline__ void failed_step(double* lam_next) const {       // nothing flows through a failed step: DZ^T lambda = 0, DU^T lambda = 0
+        for (int c = tid; c < nx; c += THREADS) lam_next[c] = 0.0;
+        for (int c = tid; c < nu; c += THREADS) gu_[c] = 0.0;
+    }
+    // a_i = gu[act_off + i] + GU[act_off + i], formed by every lane that needs it (the same bits)
+    __device__ __forceinline__ double act(int k, int i) const { return gu_[act_off + i] + (GU ? (double)GU[((size_t)k * B + b) * nu + act_off + i] : 0.0); }
+    __device__ __forceinline__ void round_gU(int k) const {
         const size_t kb = (size_t)k * B + b;
-        if (k > 0) for (int c = tid; c < nx; c += THREADS) g_[((k - 1) & 1) * nx + c] = cotangent(AG, G, Z, k - 1, b, c);
-        double acc[COLS];
-#pragma unroll
-        for (int i = 0; i < COLS; ++i) acc[i] = 0.0;
-        auto put = [&](int c, double mine) { if (c >= nx) gu_[c - nx] = mine; else lam_next[c] = mine; };
-        auto stage = [&](int it, const P (&cur)[COLS], P (&nxt)[COLS]) {
-            const bool more = it + 1 < nit;
-            issue(C, (more || !nit_next) ? k : k - 1, b, 0, more ? it + 1 : nit_next ? 0 : it, team, j, nxt);
-            consume(C, 0, it, team, j, lam, gk, cur, acc, put);
-        };
-        for (int it = 0; it < nit; it += 2) { stage(it, buf0, buf1); stage(it + 1, buf1, buf0); }
-        if (failed(k)) {                                                    // nothing flows through a failed step: DZ^T lambda = 0, DU^T lambda = 0
-            for (int c = tid; c < nx; c += THREADS) lam_next[c] = 0.0;
-            for (int c = tid; c < nu; c += THREADS) gu_[c] = 0.0;
-            if (nit_next) issue(C, k - 1, b, 0, 0, team, j, buf0);
-        }
-        __syncthreads();
-        // ---- phase (i): gu -> gU, go, the accumulators.  a_i = gu[act_off + i] + GU[act_off + i], formed by every lane that needs it (the same bits) ----
-        auto act = [&](int i) { return gu_[act_off + i] + (GU ? (double)GU[kb * nu + act_off + i] : 0.0); };
         if (gU) for (int c = tid; c < nu; c += THREADS) gU[kb * nu + c] = (TIO)(gu_[c] + (GU ? (double)GU[kb * nu + c] : 0.0));
-        for (int i = tid; i < nobs; i += THREADS) {
-            double s = 0.0;
-            for (int r = 0; r < na; ++r) s = fma((double)W[(size_t)r * nobs + i], act(r), s);
-            go_[i] = (scale ? (double)scale[i] : 1.0) * s + (GO ? (double)GO[kb * nobs + i] : 0.0);
-        }
-        for (int e = tid; e < nacc; e += THREADS) {
-            if (e < na * nobs) { const int r = e / nobs, i = e - r * nobs; acc_[e] = fma(act(r), oh_[i], acc_[e]); }
-            else acc_[e] += act(e - na * nobs);
-        }
-        __syncthreads();
-        // ---- phase (ii): lam_next += M_k^T go; the observation of the next step to come goes to LDS (its last reader was phase (i)) ----
+    }
+    __device__ __forceinline__ void set_go(int k, int i, double s) const {
+        go_[i] = (scale ? (double)scale[i] : 1.0) * s + (GO ? (double)GO[((size_t)k * B + b) * nobs + i] : 0.0);
+    }
+    // phase (ii): lam_next += M_k^T go; the observation of the next step to come goes to LDS (its last reader was phase (i)).  The caller's barrier follows.
+    __device__ __forceinline__ void phase_ii(int k, double* lam_next) const {
         for (int c = tid; c < nx; c += THREADS) {
             const double v = lam_next[c] + pull(k, c);
             if (k > 0) lam_next[c] = v;
             else if (gz) gz[(size_t)b * nx + c] = (TIO)v;
         }
         if (k > 0) put_ohat(k - 1);
-        __syncthreads();
-        p ^= 1; nit = nit_next;
     }
+};
+
+template <class TIO>
+__global__ void __launch_bounds__(THREADS) rollout_policy_adjoint_kernel(const Args<TIO> A) {
+    extern __shared__ __align__(16) double lds_[];      // lambda [2][nx] | g [2][nx] | gu [nu] | go [nobs] | ohat [nobs] | accumulators [na nobs + na]
+    const Closed<TIO> S(A.c, lds_);
+    const int b = S.b, tid = S.tid, nx = S.nx, nobs = S.nobs, na = A.na, nacc = na * nobs + na;
+    const TIO* const W = DJ_GLOBAL_PTR(const TIO, A.W) + (A.c.per_env ? (size_t)b : (size_t)0) * na * nobs;
+    double* const acc_ = S.rest();
+
+    for (int e = tid; e < nacc; e += THREADS) acc_[e] = 0.0;
+    S.put_ohat(A.c.H - 1);
+    S.first_lambda(A.c.H, lds_);
+    adjoint::sweep(S.columns(A.c), adjoint::cot_of<TIO>(A.c), DJ_GLOBAL_PTR(const int, A.c.status), A.c.H, b, lds_, lds_ + 2 * nx,
+        [](int) { return 0; },
+        [&](int, int c, double mine, double* lam_next) { S.put(c, mine, lam_next); },
+        [&](int, double* lam_next) { S.failed_step(lam_next); },
+        [&](int k, double* lam_next) {
+            // ---- phase (i): gu -> gU, go, the accumulators ----
+            S.round_gU(k);
+            for (int i = tid; i < nobs; i += THREADS) {
+                double s = 0.0;
+                for (int r = 0; r < na; ++r) s = fma((double)W[(size_t)r * nobs + i], S.act(k, r), s);
+                S.set_go(k, i, s);
+            }
+            for (int e = tid; e < nacc; e += THREADS) {
+                if (e < na * nobs) { const int r = e / nobs, i = e - r * nobs; acc_[e] = fma(S.act(k, r), S.oh_[i], acc_[e]); }
+                else acc_[e] += S.act(k, e - na * nobs);
+            }
+            __syncthreads();
+            S.phase_ii(k, lam_next);
+            __syncthreads();
+        });
     // the accumulators: rounded once (one policy per environment), or handed to the reduction as fp64 (shared policy)
     if (A.acc_out) {
         double* const out = DJ_GLOBAL_PTR(double, A.acc_out) + (size_t)b * nacc;

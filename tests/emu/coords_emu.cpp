@@ -18,14 +18,6 @@ std::vector<int> order_of(const HostModel& M) {
     for (int lev = 0; lev <= M.maxlevel; ++lev) for (int b = 0; b < M.Nb; ++b) if (M.nodes[b].level == lev) order.push_back(b);
     return order;
 }
-// seed_body of dojo_hip.hip / dojo_policy_adjoint.hpp: directions d0 .. d0 + 11 = [x, v, phi, omega], q (x) (1, phi)
-PoseVel<D24> seed_body(const PoseVel<double>& p, int d0) {
-    PoseVel<D24> s;
-    for (int i = 0; i < 3; ++i) { s.x[i] = D24::seed(p.x[i], d0 + i); s.v[i] = D24::seed(p.v[i], d0 + 3 + i); s.w[i] = D24::seed(p.w[i], d0 + 9 + i); }
-    D24 e[4] = {D24(1.0), D24::seed(0.0, d0 + 6), D24::seed(0.0, d0 + 7), D24::seed(0.0, d0 + 8)}, q0[4] = {D24(p.q[0]), D24(p.q[1]), D24(p.q[2]), D24(p.q[3])};
-    qmulS(s.q, q0, e);
-    return s;
-}
 int model_of(const DojoTopology* tp, HostModel& M) {
     const int rc = build_host_model(*tp, M);
     if (rc != DOJO_OK) return rc;
@@ -82,7 +74,7 @@ int coords_min2max_jacobian(const DojoTopology* tp, const double* x, const doubl
             dth[i] = i < nr ? D24::seed(xm[nt + i], 12 + nt + i) : D24(0.0);    dw[i] = i < nr ? D24::seed(xm[n + nt + i], 12 + n + nt + i) : D24(0.0);
         }
         const PoseVel<double> a0 = P.parent >= 0 ? load_body<double>(z, P.parent) : origin_body<double>();
-        PoseVel<D24> a = seed_body(a0, 0), b;
+        PoseVel<D24> a = seed_body<24>(a0, 0), b;
         joint_min2max(b, P, M.dt, a, dx, dth, dv, dw);
         double Pm[12][24];
         for (int d = 0; d < 24; ++d) {
@@ -112,7 +104,7 @@ int coords_max2min_jacobian(const DojoTopology* tp, const double* z, double* JM)
         const NodeP<double>& P = M.nodes[k];
         const int nt = P.nu_t, nr = P.nu_r, n = nt + nr;
         const PoseVel<double> b0 = load_body<double>(z, k), a0 = P.parent >= 0 ? load_body<double>(z, P.parent) : origin_body<double>();
-        const PoseVel<D24> a = seed_body(a0, 0), b = seed_body(b0, 12);
+        const PoseVel<D24> a = seed_body<24>(a0, 0), b = seed_body<24>(b0, 12);
         D24 ct[3], cr[3], vt[3], vr[3];
         joint_max2min(ct, cr, vt, vr, P, M.dt, a, b);
         auto put = [&](int row, const D24& v) {
