@@ -3881,7 +3881,9 @@ struct LaneProgram {
         StepT D2;
         T dva2[6];
         solve_rhs(rk2, R2, rs2, r582, up2, D2, dva2);
-        for (int i = 0; i < 6; ++i) dva[i] += dva2[i];
+        // The correction belongs to the environments that refine.  The solve above is wave-uniform (its cross-lane exchanges need every lane), but an
+        // environment that is not flagged keeps its plain solution: what it computes must not depend on which environments share its wavefront.
+        if (refine) { for (int i = 0; i < 6; ++i) dva[i] += dva2[i]; }
 #ifdef DJ_DEBUG
         if (trace && active && q == 0) {
             T m1 = 0, m2 = 0, mr = 0, mc = 0;
@@ -3894,11 +3896,13 @@ struct LaneProgram {
             std::printf("   refine k=%d |dw| %.2e |corr| %.2e  |res own rows| %.2e |res cone| %.2e lim %.2e %.2e\n", k, (double)m1, (double)m2, (double)mr, (double)mc, (double)R2.lim[0], (double)R2.lim[1]);
         }
 #endif
-        for (int i = 0; i < 3; ++i) { D.dv[i] += D2.dv[i]; D.dw[i] += D2.dw[i]; }
-        for (int i = 0; i < 6; ++i) D.dlam[i] += D2.dlam[i];
-        for (int i = 0; i < 2; ++i) { D.dls[i] += D2.dls[i]; D.dlg[i] += D2.dlg[i]; }
+        if (refine) {
+            for (int i = 0; i < 3; ++i) { D.dv[i] += D2.dv[i]; D.dw[i] += D2.dw[i]; }
+            for (int i = 0; i < 6; ++i) D.dlam[i] += D2.dlam[i];
+            for (int i = 0; i < 2; ++i) { D.dls[i] += D2.dls[i]; D.dlg[i] += D2.dlg[i]; }
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) for (int i = 0; i < 4; ++i) { D.dcs[c][i] += D2.dcs[c][i]; D.dcg[c][i] += D2.dcg[c][i]; }
+            for (int c = 0; c < CPL; ++c) for (int i = 0; i < 4; ++i) { D.dcs[c][i] += D2.dcs[c][i]; D.dcg[c][i] += D2.dcg[c][i]; }
+        }
     }
 
     // cone_line_search!  src/solver/line_search.jl:36-96

@@ -1449,6 +1449,15 @@ int dojo_get_solution(DojoHandle s, void* vel, void* joint_imp, void* contact_sg
     return DOJO_OK;
 }
 
+// which row of g_variants steps this handle: out = [family (the FAM_* order), MAXC, wavefronts per workgroup (0: lane mapping)].  Reads the tables only.
+int dojo_get_kernel_build(DojoHandle s, int32_t out[3]) {
+    if (!s || !out) { g_err = "dojo_get_kernel_build: bad argument"; return DOJO_ERR_INVALID; }
+    const Variant* v = variant_of(s->M, mapping_waves(s->M));
+    if (!v) { g_err = "dojo_get_kernel_build: no kernel build serves this mechanism"; return DOJO_ERR_UNSUPPORTED; }
+    out[0] = v->family; out[1] = v->maxc; out[2] = v->waves;
+    return DOJO_OK;
+}
+
 // mechanism.μ (the central-path parameter, src/solver/mehrotra.jl:45) of every environment when the last step's solve
 // returned: what a mehrotra! drop-in writes back before it calls set_entries! to leave mechanism.system as the reference does
 int dojo_get_mu(DojoHandle s, double* mu) {

@@ -21,6 +21,7 @@ _lib = None
 
 STATUS_SUCCESS, STATUS_FAILED, STATUS_EXCESSIVE_W = 0, 1, 2
 GRAD_REFERENCE, GRAD_CONSISTENT = 0, 1
+KERNEL_FAMILIES = ("plain", "tsd", "gen", "lin", "ss")     # dojo_get_kernel_build's family codes
 
 
 class DojoError(RuntimeError):
@@ -35,7 +36,7 @@ def lib():
         L = C.CDLL(_LIB_PATH)
         L.dojo_last_error.restype = C.c_char_p
         L.dojo_handle_error.restype = C.c_char_p; L.dojo_handle_error.argtypes = [C.c_void_p]
-        for f in ("dojo_device_count", "dojo_create", "dojo_get_dims", "dojo_set_options", "dojo_set_gradient_mode", "dojo_set_refinement", "dojo_set_async", "dojo_set_groups", "dojo_set_iteration_cap", "dojo_set_dispatch_order", "dojo_join", "dojo_comm_unique_id", "dojo_comm_init", "dojo_allgather_dev", "dojo_comm_info", "dojo_step", "dojo_step_impulses", "dojo_get_mu", "dojo_get_diagnostics", "dojo_next_state", "dojo_next_state_dev",
+        for f in ("dojo_device_count", "dojo_create", "dojo_get_dims", "dojo_set_options", "dojo_set_gradient_mode", "dojo_set_refinement", "dojo_set_async", "dojo_set_groups", "dojo_set_iteration_cap", "dojo_set_dispatch_order", "dojo_join", "dojo_comm_unique_id", "dojo_comm_init", "dojo_allgather_dev", "dojo_comm_info", "dojo_step", "dojo_step_impulses", "dojo_get_mu", "dojo_get_diagnostics", "dojo_get_kernel_build", "dojo_next_state", "dojo_next_state_dev",
                   "dojo_get_solution", "dojo_gradients", "dojo_rollout", "dojo_get_state", "dojo_step_dev", "dojo_rollout_dev",
                   "dojo_last_kernel_ms", "dojo_last_kernel_times", "dojo_kernel_time_totals",
                   "dojo_minimal_to_maximal", "dojo_maximal_to_minimal", "dojo_step_minimal",
@@ -56,7 +57,7 @@ def lib():
     return _lib
 
 
-EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error", "dojo_step_impulses", "dojo_get_mu", "dojo_get_diagnostics", "dojo_next_state", "dojo_next_state_dev", "dojo_create", "dojo_destroy", "dojo_get_dims", "dojo_set_options",
+EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error", "dojo_step_impulses", "dojo_get_mu", "dojo_get_diagnostics", "dojo_get_kernel_build", "dojo_next_state", "dojo_next_state_dev", "dojo_create", "dojo_destroy", "dojo_get_dims", "dojo_set_options",
                     "dojo_set_gradient_mode", "dojo_set_refinement", "dojo_set_async", "dojo_set_groups", "dojo_set_iteration_cap", "dojo_set_dispatch_order", "dojo_join", "dojo_comm_unique_id", "dojo_comm_init", "dojo_allgather_dev", "dojo_comm_info", "dojo_step", "dojo_get_solution", "dojo_gradients", "dojo_rollout", "dojo_get_state",
                     "dojo_step_dev", "dojo_rollout_dev", "dojo_last_kernel_ms", "dojo_last_kernel_times", "dojo_kernel_time_totals",
                     "dojo_minimal_to_maximal", "dojo_maximal_to_minimal", "dojo_step_minimal",
@@ -288,6 +289,13 @@ class BatchedMechanism:
         mu = np.empty(self.batch, np.float64)
         _chk(lib().dojo_get_mu(self.h, _p(mu)))
         return mu
+
+    def kernel_build(self):
+        """dojo_get_kernel_build: (family, MAXC, waves) of the kernel build that steps this handle -- family one of KERNEL_FAMILIES,
+        waves 1 / 2 = the quad mapping's wavefronts per workgroup, 0 = the lane mapping"""
+        out = np.zeros(3, np.int32)
+        _chk(lib().dojo_get_kernel_build(self.h, _p(out)))
+        return KERNEL_FAMILIES[int(out[0])], int(out[1]), int(out[2])
 
     def last_error(self):
         return lib().dojo_handle_error(self.h).decode()

@@ -110,6 +110,7 @@ end
 check(rc) = rc == 0 || error("libdojo_hip: " * unsafe_string(@ccall $(fn(:dojo_last_error))()::Cstring))
 "the text of the last failure on this handle (per handle; dojo_last_error is process-wide)"
 last_error(bm) = unsafe_string(@ccall $(fn(:dojo_handle_error))(bm.handle::Ptr{Cvoid})::Cstring)
+kernel_build(bm) = (o = zeros(Int32, 3); check(@ccall $(fn(:dojo_get_kernel_build))(bm.handle::Ptr{Cvoid}, o::Ptr{Int32})::Cint); (o[1], o[2], o[3]))   # (family, MAXC, waves) of the build that steps the handle
 
 function BatchedMechanism(m::Dojo.Mechanism, batch::Int; T=Float32, device::Int=0)
     bodies, joints, contacts = export_topology(m)

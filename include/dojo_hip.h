@@ -237,6 +237,10 @@ int  dojo_get_mu(DojoHandle h, double* mu);
  * [0] is 0 while no refinement threshold is in force (reference-default options and no dojo_set_refinement: the kernels then
  * skip the stiffness arithmetic); [1] is 0 unless the library was built with -DDJ_TRACK_GROWTH=1 (a diagnostics build). */
 int  dojo_get_diagnostics(DojoHandle h, double* diag);
+/* Which kernel build steps this handle (read-only; no GPU work): out = [family, MAXC, waves].  family: 0 plain, 1 translational springs / dampers
+ * (tsd), 2 general (limits on several coordinates, loops), 3 LinearContact, 4 body-body contacts.  MAXC: the build's bound on contacts per body.
+ * waves: wavefronts per workgroup of the quad mapping (1, 2), 0 = lane mapping.  DOJO_ERR_UNSUPPORTED when no build serves the mechanism. */
+int  dojo_get_kernel_build(DojoHandle h, int32_t out[3]);
 
 /* IFT Jacobians of the last dojo_step(..., with_gradient=1):
  * dz [B,12Nb,12Nb] = jacobian_state, du [B,12Nb,nu] = jacobian_control, row-major per environment
