@@ -104,7 +104,7 @@ template <class S, class TIO> DJ_HD PoseVel<S> load_body(const TIO* z, int b) {
     for (int i = 0; i < 3; ++i) { p.x[i] = S((double)z[13 * b + i]); p.v[i] = S((double)z[13 * b + 3 + i]); p.w[i] = S((double)z[13 * b + 10 + i]); }
     double q_[4];
     for (int i = 0; i < 4; ++i) q_[i] = (double)z[13 * b + 6 + i];
-    if (sizeof(TIO) < sizeof(double)) {    // a narrower ABI type cannot hold a unit quaternion: the state it stands for is (x, v, q/|q|, ω), as in the step / IFT kernels (DJ_LANE_SETUP)
+    if (sizeof(TIO) < sizeof(double)) {    // a narrower ABI type cannot hold a unit quaternion: the state it stands for is (x, v, q/|q|, ω), as in the step / IFT kernels (the lane set-up of dojo_entries.hpp)
         const double iq_ = 1.0 / sqrt(q_[0] * q_[0] + q_[1] * q_[1] + q_[2] * q_[2] + q_[3] * q_[3]);
         for (int i = 0; i < 4; ++i) q_[i] *= iq_;
     }

@@ -14,6 +14,8 @@
 //
 // The same source runs under tests/emu (threads + barriers implement the Wave interface) so the
 // device algorithm is checked against the CPU oracle without a GPU.
+// What a kernel wraps around this lane program -- the argument record, the LDS layout, the records
+// between the kernels and the per-lane entries -- is dojo_entries.hpp, which includes this file.
 //
 // Reference functions restated here (all fused into the lane program):
 //   src/simulation/step.jl:11-30, src/mechanism/set.jl:10-53, src/bodies/set.jl:1-36
@@ -80,7 +82,8 @@ constexpr int NCUT = 2;                  // loop-closing joints per mechanism in
 // per-environment workspace of the cut elements in global memory (KernelArgs::cutws): M_c [NCUT][18][18], H [12 NCUT][12 NCUT], the LU of the small
 // system [18 NCUT][18 NCUT] and its row exchanges [18 NCUT] -- written by one lane of the environment, read by all of them
 constexpr int CUTWS_H = NCUT * 324, CUTWS_LU = CUTWS_H + 144 * NCUT * NCUT, CUTWS_PIV = CUTWS_LU + 324 * NCUT * NCUT, CUTWS = CUTWS_PIV + 18 * NCUT;
-constexpr int NLM = DJ_MLIM ? 6 : 1;     // limited coordinates per joint in the DJ_MLIM builds: up to 3 translational + 3 rotational
+constexpr int NLM_GEN = 6;               // limited coordinates per joint in the DJ_MLIM builds: up to 3 translational + 3 rotational
+constexpr int NLM = DJ_MLIM ? NLM_GEN : 1;
 // per supernode (DJ_MLIM builds): how many coordinates of the parent joint's translational / rotational half are limited (0 or all of the half's
 // free ones) and the bounds, translational coordinates first.  Coordinate m keeps its Δκ row in the padded multiplier slot of its own free
 // coordinate: 6 + nl_t + m for a translational one, 9 + nl_r + (m − nt) for a rotational one.
@@ -146,7 +149,7 @@ struct NodeP {
 template <class T>
 struct ContactP { T n[3], t[6], o[3], off[3], r, mu; T r2, o2[3]; int kind, pbody, cbody; };   // kind 1: SphereSphereCollision: (o, r) = (origin_parent, radius_parent), (o2, r2) = the child's; pbody / cbody: its parent body and its child body (the owner; half-space: -1 / the body)
 
-// the node constants of a workgroup's supernode slots in LDS (lock-step quad mappings: StepLds, DJ_LANE_SETUP)
+// the node constants of a workgroup's supernode slots in LDS (lock-step quad mappings: StepLds and the lane set-up of the entries, dojo_entries.hpp)
 template <class T>
 struct NodeSlot { NodeP<T> P; char pad_[(sizeof(NodeP<T>) / 8) % 2 == 0 ? 8 : 16]; };                    // odd stride in 8-byte words
 
@@ -192,8 +195,9 @@ struct Factors {
 // step -> IFT hand-off record, KernelArgs::sol): the scalars of mehrotra!'s loop (src/solver/mehrotra.jl:17-21, 51-60)
 template <class T>
 struct SolveCarry { T undercut, rvio, bvio; int n, no_progress, excessive; };
-constexpr int CARRY_PER_ENV = 8;   // doubles per environment of KernelArgs::resume
-constexpr int CARRY_MARK = 7;      // ... of which this one says whether the environment is on the continuation list
+// ... as they lie in KernelArgs::resume, CARRY_PER_ENV doubles per environment: written by mehrotra() where the cap stops a solve, read back
+// by the continuation kernel's entry; entry CARRY_MARK says whether the environment's workgroup is on the continuation list
+enum { CARRY_UNDERCUT = 0, CARRY_RVIO, CARRY_BVIO, CARRY_N, CARRY_NO_PROGRESS, CARRY_EXCESSIVE, CARRY_MARK = 7, CARRY_PER_ENV = 8 };
 
 template <class T, int MAXC>
 struct SolSnap { T v[3], w[3], lam[6], ls[2], lg[2], cs[MAXC][NCV], cg[MAXC][NCV];     // solution variables at the start of a line search
@@ -4326,7 +4330,8 @@ struct LaneProgram {
                             if (!done) {
                                 status = DJ_STATUS_CONTINUE; done = true;
                                 if (active && q == 0 && k == 0) {
-                                    carry_out[0] = undercut; carry_out[1] = rvio; carry_out[2] = bvio; carry_out[3] = T(n); carry_out[4] = T(no_progress); carry_out[5] = T(excessive);
+                                    carry_out[CARRY_UNDERCUT] = undercut; carry_out[CARRY_RVIO] = rvio; carry_out[CARRY_BVIO] = bvio;
+                                    carry_out[CARRY_N] = T(n); carry_out[CARRY_NO_PROGRESS] = T(no_progress); carry_out[CARRY_EXCESSIVE] = T(excessive);
                                 }
                             }
                             break;
@@ -5068,475 +5073,6 @@ DJ_HD void storage_row(T* row, const NodeP<T>& P, const ContactP<T>* CP, T dt, c
         row[13 + i] = p[i]; row[16 + i] = pw[i]; row[19 + i] = p[i] / P.m; row[22 + i] = wl[i];
     }
     for (int i = 0; i < 4; ++i) row[3 + i] = q2[i];
-}
-
-// ================================================================================================
-// Kernel-level entry: one call per lane.  Shared by the HIP kernel (dojo_hip.hip) and the
-// thread-based SIMT emulator (tests/emu).
-// ================================================================================================
-// TIO = scalar type of the ABI buffers, T = state/residual precision (tables are stored in T)
-template <class TIO, class T>
-struct KernelArgs {
-    typedef TIO io_type;
-    Globals<T> G;
-    const NodeP<T>* nodes;
-    const ContactP<T>* contacts;
-    int B;                       // number of environments
-    const TIO* z;                  // [B,13Nb]
-    const TIO* u;                  // [B,nu] or null
-    const TIO* fext;               // [B,6Nb] or null          external force (world) and torque (body frame) per body
-    TIO* z_next;                   // [B,13Nb]
-    int* status;                 // [B] or null
-    int* iters;                  // [B] or null
-    TIO* vel;                      // [B,6Nb] or null          (v25, ω25)
-    TIO* joint_imp;                // [B,n_joint_imp] or null  (get_solution order)
-    TIO* contact_sg;               // [B,8Nc] or null          ([s; γ] per contact)
-    TIO* dz;                       // [B][12Nb cols][12Nb rows] column-major per env, or null
-    TIO* du;                       // [B][nu cols][12Nb rows] column-major per env, or null
-    TIO* dc;                       // [B][5Nc cols][12Nb rows] contact-data Jacobian (get_contact_gradients), or null
-    TIO* res;                      // [B,6Nb] or null          body residual rows at the solution (for the Storage kernel)
-    T* sol;                        // [B][S][sol_record<MAXC>] converged solution in state precision: step kernel -> IFT kernel (or null)
-    T* fac;                        // [waves][72][64] quad mapping: the final supernode factors of every lane (explicit inverses; or null: nobody reads them)
-    T* lu = nullptr;               // [workgroups][dj::LU_PER_LANE][lanes] quad mapping: the IFT kernel's own LU-form factors between its phases (or null)
-    T* blk = nullptr;              // [workgroups][90][lanes] quad mapping: un-factored supernode rows of refining environments (DJ_REFINE; or null)
-    long long ypark_stride = 0;    // elements per workgroup of ypark
-    T* ypark = nullptr;            // [workgroups][batches][6][3][lanes / 2] quad mapping, ABI type narrower than the arithmetic: the IFT's forward-substituted
-                                   // right-hand sides in full precision between the two sweeps (or null: they wait in the output buffer, in the ABI type)
-    T* msg = nullptr;              // [B][level-1 supernodes][batches][2 roles][18] quad mapping: what the children of a root post to its body rows during the
-    long long msg_stride = 0;      // up-sweep (read back by the root phase, gradient_columns_quad); msg_stride = elements per environment
-    int* flag = nullptr;           // [B] 1: the plain step kernel deferred this environment to the refining kernels (DJ_REFINE; or null)
-    T* mu_out = nullptr;           // [B] or null: mechanism.μ when mehrotra! returned (src/solver/mehrotra.jl:45), fp64
-    T* diag_out = nullptr;         // [B][2] or null: diagnostics of the final linearization: max γ/s of the cones, largest Gauss-Jordan multiplier
-    const TraSD<T>* tsd = nullptr; // [Nb + 1] translational springs / dampers per supernode, or null (read by the DJ_TSD builds only)
-    const MLimP<T>* mlim = nullptr;// [Nb + 1] limits on several coordinates per supernode, or null (read by the DJ_MLIM builds only)
-    const NodeP<T>* cuts = nullptr;// [ncut] loop-closing joints (read by the DJ_CUT builds only): the joint fields of NodeP, parent = body a, child[0] = body b
-    int ncut = 0;
-    T* cutws = nullptr;            // [B][CUTWS] workspace of the cut elements (M_c, H, the factored small system), or null
-    // iteration cap + continuation (Globals::iter_cap > 0; all three set or all null):
-    T* resume = nullptr;           // [B][CARRY_PER_ENV] solver scalars of the environments the step kernel left unfinished (DJ_STATUS_CONTINUE);
-                                   // entry CARRY_MARK: 1 for the environments of a workgroup on the continuation list, 0 for the others (written by
-                                   // the step kernel for every environment, never by the continuation: the IFT kernel of the others runs next to it)
-    int* cont_list = nullptr;      // [workgroups of this launch] workgroup indices with an unfinished environment, in the order they finished
-    int* cont_count = nullptr;     // [1] entries of cont_list (zeroed before the step kernel, atomically advanced by it)
-    int wave_base = 0;             // index of this launch's first workgroup in the batch: cont_list holds batch-level workgroup indices (the
-                                   // continuation kernels run once over the whole batch, behind the step kernels of all environment groups)
-    const int* dispatch = nullptr; // [workgroups of this launch] the step kernel's hardware workgroup -> workgroup of this launch it works for (a permutation:
-                                   // the longest solves of the previous step first, dojo_set_dispatch_order), or null: in order
-#ifdef DJ_DEBUG
-    T* dbg = nullptr;            // [B][Nb][512] test hook
-#endif
-};
-
-// LDS layout of one workgroup (= one wavefront, or NW wavefronts for mechanisms of 17..32 bodies) in the quad mapping.
-// LOCKSTEP (the GPU): everything the four lanes of a supernode hold identically exists once per supernode in LDS; the
-// four lanes read it with broadcast ds_reads and write identical values in the same instruction.  The SIMT emulator's
-// threads are not in lock step, so there NodeP / Lane stay per-lane and Cold is per-lane in "LDS".
-//   phase A (Newton loop; data blocks of the IFT):
-//     [NodeP x NSN][Lane x NSN][Cold x NSN (or per lane)][ContactCold pool][mailbox (step kernel)]
-//   IFT column sweeps (overlay from offset 0: NodeP / Lane / Cold are dead by then, the few NodeP fields the sweeps
-//   need are cached in registers):
-//     [QuadRhs x NSN][mailbox]
-//   [reduction scratch, 64 B] at the end
-template <class T, int MAXC>
-struct LaneSlot { Lane<T, MAXC> L; T pad_[(sizeof(Lane<T, MAXC>) / sizeof(T)) % 2 == 0 ? 1 : 2]; };   // odd stride in 8-byte words
-constexpr int lds_imax(int a, int b) { return a > b ? a : b; }
-// GRAD: 0 = step kernel, 1 = IFT kernel (state + control columns), 2 = IFT kernel for the contact-data columns
-template <class TIO, class T, int MAXC, int GRAD, bool QUAD, bool LOCKSTEP, int NW = 1>
-struct StepLds {
-    static constexpr int NSN = 16 * NW;                                                     // supernode slots of the workgroup
-    static constexpr bool share = QUAD && LOCKSTEP;
-    static constexpr int node_bytes = share ? (int)sizeof(NodeSlot<T>) * NSN : 0;
-    static constexpr int lane_off = node_bytes;
-    static constexpr int lane_bytes = node_bytes + (share ? (int)sizeof(LaneSlot<T, MAXC>) * NSN : 0);   // end of the Lane block
-    static constexpr int cold_n = LOCKSTEP ? NSN : 64 * NW;
-    static constexpr bool cold_in_lds = QUAD;
-    static constexpr int cold_off = lane_bytes;
-    static constexpr int cold_bytes = QUAD ? (int)sizeof(Cold<T, MAXC>) * cold_n : 0;
-    // contact rows: one slot per (supernode, contact) for a single-wave workgroup, one slot per contact of the
-    // environment (at most 16) for NW > 1 -- there the per-supernode array would not fit
-    static constexpr bool pool_by_id = NW > 1;
-    static constexpr int pool_n = !QUAD ? 0 : (pool_by_id ? 16 : cold_n * MAXC);
-    static constexpr int pool_off = cold_off + cold_bytes;
-    static constexpr int pool_bytes = (int)sizeof(ContactCold<T>) * pool_n;
-    // Newton step and the iterate at the start of the line search, once per supernode (step kernel, when there is room:
-    // frees ~100 registers during the residual evaluations of the line search)
-    static constexpr int ls_slot = (int)((sizeof(Step<T, MAXC>) + sizeof(SolSnap<T, MAXC>)) / 8 + (((sizeof(Step<T, MAXC>) + sizeof(SolSnap<T, MAXC>)) / 8) % 2 == 0 ? 1 : 0)) * 8;
-    static constexpr bool ls_in_lds = share && !GRAD && NW == 1 && MAXC == 1;                 // (must match LaneProgram::kLsInLds)
-    static constexpr int ls_off = pool_off + pool_bytes;
-    static constexpr int a_end = ls_off + (ls_in_lds ? ls_slot * NSN : 0);
-    static constexpr int rhs_bytes = !QUAD ? 0 : GRAD == 1 ? (int)sizeof(QuadRhs<TIO>) * NSN : GRAD == 2 ? (int)sizeof(ConRhs<MAXC>) * NSN : 0;
-    static constexpr int mail_need = QUAD ? 2 * NSN * 20 * 8 : 0;
-    static constexpr int rhs_off = 0;
-    // (contact-data kernel: the mailbox keeps its own room behind the phase-A data; packed right behind the ConRhs blocks
-    //  the last supernode's block read back zeros on the GPU -- not understood, the kernel is not LDS-critical)
-    // (IFT kernel: behind both the phase-A data and the right-hand sides -- a workgroup that factors its own LU form
-    //  (gradients) evaluates the linearization, which uses the mailbox while NodeP / Lane / Cold / the contact rows are alive)
-    static constexpr int mail_off = (QUAD && GRAD == 2) ? a_end : (QUAD && GRAD) ? lds_imax(a_end, rhs_off + rhs_bytes) : a_end;
-    static constexpr int red_off = lds_imax(a_end, mail_off + mail_need);
-    static constexpr int qred_off = red_off + 64;                    // per-supernode values of the environment reductions (3 at a time)
-    static constexpr int info_off = qred_off + (QUAD ? 3 * NSN * 8 : 0);   // SweepInfo per supernode (IFT kernels)
-    static constexpr int info_end = info_off + ((QUAD && GRAD) ? NSN * (int)sizeof(SweepInfo) : 0);
-    // Staging areas of the row-layout level passes (LaneProgram::factorize_rows; step kernels of the single-wavefront quad mapping with one
-    // contact per body): A = 4 supernodes x 12 rows of S (stride ROW_RS doubles: odd, so that the 32 lanes of a ds_read_b64 group hit 32
-    // bank pairs), later their 6 rows of L and of Dup; B = their 12 rows of U (stride ROW_US).  On the GPU A lies over the Newton step /
-    // line-search base, which are dead between the line search and the next solve; B takes what is left of the 40 KB a workgroup may
-    // use with four workgroups per CU.
-    static constexpr int ROW_RS = 13, ROW_US = 7;
-    static constexpr bool rows = QUAD && GRAD == 0 && ((NW == 1 && MAXC == 1) || NW == 2);    // (two wavefronts: staging areas per wavefront, behind the layout)
-    static constexpr int stA_bytes = NW * 4 * 12 * ROW_RS * 8, stB_bytes = NW * 4 * 12 * ROW_US * 8;
-    static_assert(4 * 6 * (ROW_RS + ROW_US) * 8 <= stA_bytes / NW, "L and Dup rows reuse area A");
-    static constexpr int stA_off = !rows ? 0 : ls_in_lds ? ls_off : info_end;
-    static constexpr int stB_off = !rows ? 0 : ls_in_lds ? info_end : info_end + stA_bytes;
-    static_assert(!rows || !ls_in_lds || ls_slot * NSN >= stA_bytes, "area A must fit the line-search block it overlays");
-    // ... and of the IFT kernel's LU-form passes (LaneProgram::factorize_rows_lu; GRAD == 1): A = the S rows in and the factor rows out (stride
-    // LU_RS), the rows of L in and of m out over its first half; B = the rows of U in / T out (stride ROW_US) and of Dup in (stride LU_DS).  B
-    // lies where the right-hand-side blocks reach beyond the phase-A data -- nothing of them is alive while the linearization is factored --
-    // when that stretch is long enough (fp32 ABI: exactly), A behind everything else: 40 768 of the 40 960 bytes of four workgroups per CU.
-    static constexpr int LU_RS = 12, LU_DS = 6;
-    static constexpr bool rows_lu = QUAD && NW == 1 && MAXC == 1 && GRAD == 1;
-    static constexpr int luA_bytes = 4 * 12 * LU_RS * 8, luB_bytes = 4 * 12 * ROW_US * 8 + 4 * 6 * LU_DS * 8;
-    static constexpr bool luB_in_rhs = rows_lu && (rhs_off + rhs_bytes - a_end >= luB_bytes) && (mail_off >= a_end + luB_bytes);
-    static constexpr int luA_off = info_end;
-    static constexpr int luB_off = luB_in_rhs ? a_end : info_end + luA_bytes;
-    static constexpr int bytes = rows ? stB_off + stB_bytes : rows_lu ? (luB_in_rhs ? info_end + luA_bytes : info_end + luA_bytes + luB_bytes) : info_end;
-};
-template <class TIO, class T, int MAXC, int GRAD, bool QUAD, bool LOCKSTEP = true, int NW = 1>
-constexpr int step_lds_bytes() { return StepLds<TIO, T, MAXC, GRAD, QUAD, LOCKSTEP, NW>::bytes; }
-
-// doubles per supernode in the step -> IFT hand-off record: v ω λ(6), s,γ of the joint limit, s,γ of the contacts, μ,
-// and the pieces of the final linearization the IFT needs besides the factors: t_a, t_b (limit condensation), G134.
-// NOTE: a step that skips the linearization after its converging iteration (need_factors = false: every launch without the refining
-// kernels) leaves t_a / t_b / G134 -- and KernelArgs::diag_out -- at the LAST linearization it did perform, i.e. one iterate back; the plain
-// IFT kernel never reads them (lu_prepare() evaluates the linearization at the restored solution before any use), the refining one
-// re-evaluates them too (grad_entry MODE 2).  They travel for the explicit-inverse consumers only.
-// (GEN: the general lane-mapping builds -- DJ_MLIM and DJ_CUT together -- append (s_up, s_lo, γ_up, γ_lo) of up to six limited coordinates and the multipliers
-//  of the cut joints; the host sizes the buffer with GEN = true for mechanisms that take those builds)
-static_assert((DJ_MLIM != 0) == (DJ_CUT != 0), "the general lane-mapping builds carry DJ_MLIM and DJ_CUT together");
-template <int MAXC, bool GEN = (DJ_MLIM != 0)> constexpr int sol_record() { return 6 + 6 + 4 + 8 * MAXC + 1 + 12 + 18 * MAXC + (GEN ? 24 + 6 * NCUT : 0) + 1; }   // last: 1.0 if the environment's solves were being refined (DJ_REFINE)
-template <int MAXC> constexpr int sol_flag_off() { return sol_record<MAXC>() - 1; }
-template <int MAXC> constexpr int sol_mlim_off() { return 6 + 6 + 4 + 8 * MAXC + 1 + 12 + 18 * MAXC; }
-template <int MAXC> constexpr int sol_cut_off() { return sol_mlim_off<MAXC>() + 24; }
-// quad mapping: the factors themselves travel too (72 values per lane, stored [wave][72][64 lanes]: coalesced)
-constexpr int FAC_PER_LANE = 72;
-
-// The forward step and the IFT gradients are separate kernels (separate register allocations: the
-// gradient sweeps must not cost the Newton loop its registers).  The IFT kernel rebuilds the lane
-// program from (z, u), restores the converged solution from the hand-off record and re-linearizes
-// there -- the same final linearization mehrotra! leaves behind (src/gradients/state.jl:78-84).
-#if DJ_CUT
-#define DJ_CUT_SETUP if constexpr (!QUAD) { prog.cutp = A.cuts; prog.ncut = (A.cuts && A.cutws) ? A.ncut : 0;                                              \
-        prog.cws = A.cutws ? A.cutws + (size_t)(env < A.B ? env : 0) * CUTWS : nullptr;                                                             \
-        for (int c_ = 0; c_ < NCUT; ++c_) for (int i = 0; i < 6; ++i)                                                                                \
-            prog.cue[c_][i] = (has_u && c_ < prog.ncut && env < A.B && i < A.cuts[c_].nu_t + A.cuts[c_].nu_r) ? T(A.u[(size_t)env * G.nu + A.cuts[c_].u_off + i]) : T(0); \
-        prog.cut_begin(); }
-#else
-#define DJ_CUT_SETUP
-#endif
-#if DJ_TSD && DJ_MLIM
-#define DJ_TSD_SETUP prog.tsd = A.tsd ? A.tsd + (k < G.Nb ? k : G.Nb) : nullptr; prog.tlim = prog.tsd != nullptr && prog.tsd->nlim > 0; prog.mlp = A.mlim ? A.mlim + (k < G.Nb ? k : G.Nb) : nullptr;
-#elif DJ_TSD
-#define DJ_TSD_SETUP prog.tsd = A.tsd ? A.tsd + (k < G.Nb ? k : G.Nb) : nullptr; prog.tlim = prog.tsd != nullptr && prog.tsd->nlim > 0;
-#elif DJ_MLIM
-#define DJ_TSD_SETUP prog.mlp = A.mlim ? A.mlim + (k < G.Nb ? k : G.Nb) : nullptr;
-#else
-#define DJ_TSD_SETUP
-#endif
-#ifdef DJ_PROF2
-#define DJ_P2_SETUP { prog.p2c = (unsigned long long*)wv.p2_; wv.sync(); if (lane < 24) prog.p2c[lane] = 0ull; wv.sync(); }
-#else
-#define DJ_P2_SETUP
-#endif
-#define DJ_LANE_SETUP(GRAD_LAYOUT, ENV_OK)                                                                                \
-    const Globals<T>& G = A.G;                                                                                            \
-    const int stride = QUAD ? 4 : 1;                                                                                      \
-    const int envl = stride * G.S, E = wv.width() / envl;        /* lanes per environment, environments per workgroup */  \
-    const int lane = wv.lane();                                                                                           \
-    const int slot = lane / envl, k = (lane % envl) / stride, q = lane % stride;                                          \
-    const int env = wave_index * E + slot;                                                                                \
-    const bool active = (env < A.B) && (k < G.Nb) && (ENV_OK);                                                            \
-    const int base = slot * envl;                                                                                         \
-    typedef StepLds<TIO, T, MAXC, (GRAD_LAYOUT), QUAD, Wave::kLockstep, Wave::kWaves> LY;                                   \
-    constexpr bool SHARE = QUAD && Wave::kLockstep;                                                                       \
-    char* lds = (char*)wv.lds();                                                                                          \
-    const NodeP<T>& Pg = A.nodes[k < G.Nb ? k : G.Nb];         /* idle supernode slots: the table's extra entry (node 0 without contacts) */ \
-    if (SHARE) ((NodeSlot<T>*)lds)[lane / 4].P = Pg;           /* the four lanes store identical values */                \
-    const NodeP<T>& P = SHARE ? ((NodeSlot<T>*)lds)[lane / 4].P : Pg;                                                     \
-    Lane<T, MAXC> lane_local;                                                                                             \
-    Cold<T, MAXC> cold_local;                                                                                             \
-    ContactCold<T> pool_local[QUAD ? 1 : MAXC];                                                                           \
-    Lane<T, MAXC>& lane_state = SHARE ? ((LaneSlot<T, MAXC>*)(lds + LY::lane_off))[lane / 4].L : lane_local;             \
-    Cold<T, MAXC>& cold = LY::cold_in_lds ? ((Cold<T, MAXC>*)(lds + LY::cold_off))[SHARE ? lane / 4 : lane] : cold_local; \
-    LaneProgram<T, TL, MAXC, QUAD, Wave> prog(wv, G, P, A.contacts, base, k, q, active, lane_state, cold);                \
-    if (QUAD) {                                                                                                           \
-        prog.cpool = (ContactCold<T>*)(lds + LY::pool_off); prog.pool_by_id = LY::pool_by_id;                             \
-        prog.pool_base = LY::pool_by_id ? 0 : (SHARE ? lane / 4 : lane) * MAXC;                                           \
-        prog.gb_lds = ((GRAD_LAYOUT) == 2) ? (void*)(((ConRhs<MAXC>*)(lds + LY::rhs_off)) + lane / 4) : (void*)(((QuadRhs<TIO>*)lds) + lane / 4); \
-        prog.mail = (double*)(lds + LY::mail_off); prog.chpack_init();                                                    \
-        DJ_P2_SETUP                                                                                                       \
-        prog.qred = (double*)(lds + LY::qred_off);                                                                        \
-        if (GRAD_LAYOUT) prog.sinfo = (SweepInfo*)(lds + LY::info_off);                                                   \
-        if (A.msg) prog.msg = DJ_GLOBAL_PTR(T, A.msg) + (size_t)(env < A.B ? env : 0) * (size_t)A.msg_stride;                 \
-        if (LY::ls_in_lds) prog.ls_lds = lds + LY::ls_off + (size_t)(lane / 4) * LY::ls_slot;                              \
-        prog.rows_here = LY::rows || LY::rows_lu;                                                                         \
-        if (LY::rows) { prog.stA = (double*)(lds + LY::stA_off); prog.stB = (double*)(lds + LY::stB_off); prog.rows_init(); }  \
-        if (LY::rows_lu) { prog.stA = (double*)(lds + LY::luA_off); prog.stB = (double*)(lds + LY::luB_off); prog.rows_init(); } \
-        if (SHARE) { prog.lane_slots = lds + LY::lane_off; prog.lane_slot_stride = (int)sizeof(LaneSlot<T, MAXC>); }              \
-        if (A.lu) { prog.lu = DJ_GLOBAL_PTR(T, A.lu) + (size_t)wave_index * LU_PER_LANE * wv.width() + lane; prog.lu_stride = wv.width(); }                \
-        if (A.blk) { prog.blk = DJ_GLOBAL_PTR(T, A.blk) + (size_t)wave_index * 90 * wv.width() + lane; prog.blk_stride = wv.width(); }     \
-        if (A.ypark) prog.ypark = DJ_GLOBAL_PTR(T, A.ypark) + (size_t)wave_index * (size_t)A.ypark_stride + lane;                                \
-    } else { prog.cpool = pool_local; prog.pool_by_id = false; prog.pool_base = 0; }                                      \
-    DJ_TSD_SETUP                                                                                                          \
-    T zb[13], ue[6] = {0, 0, 0, 0, 0, 0};                                                                                 \
-    for (int i = 0; i < 13; ++i) zb[i] = active ? T(A.z[(size_t)env * 13 * G.Nb + 13 * k + i]) : T(0);                   \
-    if (sizeof(TIO) < sizeof(T) && active) {   /* a narrower ABI type cannot hold a unit quaternion: the state it stands for is (x, v, q/|q|, ω) */ \
-        const T iq_ = trcp(tsqrt(zb[6] * zb[6] + zb[7] * zb[7] + zb[8] * zb[8] + zb[9] * zb[9]));                         \
-        for (int i = 6; i < 10; ++i) zb[i] *= iq_;                                                                        \
-    }                                                                                                                     \
-    const bool has_u = A.u != nullptr;                                                                                    \
-    if (active && has_u) for (int i = 0; i < 6; ++i) if (i < P.nu_t + P.nu_r) ue[i] = T(A.u[(size_t)env * G.nu + P.u_off + i]); \
-    T fe[6] = {0, 0, 0, 0, 0, 0};                                                                                         \
-    const bool has_f = A.fext != nullptr;                                                                                 \
-    if (active && has_f) for (int i = 0; i < 6; ++i) fe[i] = T(A.fext[(size_t)env * 6 * G.Nb + 6 * k + i]);             \
-    prog.begin_step(zb, has_u ? ue : nullptr, has_f ? fe : nullptr);                                                        \
-    DJ_CUT_SETUP
-
-// IFT kernel entry: one call per lane
-// MODE 0: state + control columns, pipelined sweeps; 1: contact-data columns; 2: state + control columns of the environments
-// whose solves were being refined, column by column through the refined general solve (LDS layout of the step kernel:
-// NodeP / Lane / Cold stay alive)
-// CONT (MODE 0, iteration cap): false = the environments the step kernel finished itself (all of them without a cap), true = `wave_index`
-// comes from the continuation list and the environments the continuation kernel finished are served
-template <class TIO, class T, class TL, int MAXC, bool QUAD, class Wave, int MODE = 0, bool CONT = false>
-DJ_HD void grad_entry(Wave& wv, const KernelArgs<TIO, T>& A, int wave_index) {
-    static_assert(!CONT || MODE == 0, "continuation lists exist for the plain IFT kernel only");
-    if constexpr (QUAD && MODE == 0) {
-        if (A.resume != nullptr) {                              // (uniform) a workgroup without an environment of this launch's kind leaves at once
-            const int stride_ = 4, envl_ = stride_ * A.G.S, E_ = wv.width() / envl_, lane_ = wv.lane();
-            const int env_ = wave_index * E_ + lane_ / envl_, k_ = (lane_ % envl_) / stride_;
-            const bool act_ = (env_ < A.B) && (k_ < A.G.Nb);
-            if (!wv.any(act_ && (A.resume[(size_t)env_ * CARRY_PER_ENV + CARRY_MARK] != T(0)) == CONT)) return;
-        }
-    }
-    if constexpr (QUAD && DJ_REFINE && (MODE == 0 || MODE == 2)) {
-        // refined environments belong to the MODE 2 kernel; a workgroup without work for this kernel leaves at once (uniform)
-        const int stride_ = 4, envl_ = stride_ * A.G.S, E_ = wv.width() / envl_, lane_ = wv.lane();
-        const int env_ = wave_index * E_ + lane_ / envl_, k_ = (lane_ % envl_) / stride_;
-        const bool act_ = (env_ < A.B) && (k_ < A.G.Nb);
-        const bool fl_ = act_ && A.sol[((size_t)env_ * A.G.S + (size_t)k_) * sol_record<MAXC>() + sol_flag_off<MAXC>()] != T(0);
-        if (MODE == 0 ? !wv.any(act_ && !fl_) : !wv.any(fl_)) return;
-    }
-    static_assert(MODE != 2 || Wave::kRefine || !(QUAD && DJ_REFINE), "the MODE 2 IFT kernel needs a refining Wave");
-    DJ_LANE_SETUP(MODE == 0 ? 1 : MODE == 1 ? 2 : 0,
-                  MODE == 2 ? A.sol[(size_t)env * G.S * sol_record<MAXC>() + sol_flag_off<MAXC>()] != T(0)
-                            : (MODE != 0 || !QUAD || A.resume == nullptr || (A.resume[(size_t)env * CARRY_PER_ENV + CARRY_MARK] != T(0)) == CONT))
-    bool flagged = false;
-    {   // restore the converged solution (identical on the four lanes of a quad)
-        const T* r = A.sol + ((size_t)env * G.S + (size_t)k) * sol_record<MAXC>();
-        if (active) {
-            flagged = r[sol_flag_off<MAXC>()] != T(0);
-            for (int i = 0; i < 3; ++i) { prog.L.v[i] = r[i]; prog.L.w[i] = r[3 + i]; }
-            for (int i = 0; i < 6; ++i) prog.L.lam[i] = r[6 + i];
-            prog.L.ls[0] = r[12]; prog.L.ls[1] = r[13]; prog.L.lg[0] = r[14]; prog.L.lg[1] = r[15];
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) for (int i = 0; i < 4; ++i) { prog.L.cs[c][i] = r[16 + 8 * c + i]; prog.L.cg[c][i] = r[20 + 8 * c + i]; }
-            prog.mu = r[16 + 8 * MAXC];
-#if DJ_MLIM
-            for (int m = 0; m < NLM; ++m) for (int i = 0; i < 2; ++i) { prog.L.mls[m][i] = r[sol_mlim_off<MAXC>() + 4 * m + i]; prog.L.mlg[m][i] = r[sol_mlim_off<MAXC>() + 4 * m + 2 + i]; }
-#endif
-#if DJ_CUT
-            for (int c = 0; c < NCUT; ++c) for (int i = 0; i < 6; ++i) prog.clam[c][i] = r[sol_cut_off<MAXC>() + 6 * c + i];
-#endif
-            if (QUAD) {
-                const T* r2 = r + 17 + 8 * MAXC;
-                for (int i = 0; i < 6; ++i) { prog.F.t_a[i] = r2[i]; prog.F.t_b[i] = r2[6 + i]; }
-#pragma unroll
-                for (int c = 0; c < MAXC; ++c) if (c < P.ncontact) for (int i = 0; i < 18; ++i) prog.ccold(c).G134[i] = r2[12 + 18 * c + i];
-            }
-        }
-    }
-#ifdef DJ_PROF
-    unsigned long long t_all = wv.clock();
-#endif
-    if constexpr (QUAD) { if (A.fac != nullptr) {              // the final factors of the Newton loop, as the step kernel left them (uniform)
-        const T* f = A.fac + (size_t)wave_index * FAC_PER_LANE * wv.width() + lane;
-        const int W = wv.width();
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 12; ++j) prog.F.Sq[i][j] = TL(f[(size_t)(12 * i + j) * W]);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) { prog.F.Uq[i][j] = TL(f[(size_t)(36 + 6 * i + j) * W]); prog.F.Lq[j][i] = TL(f[(size_t)(54 + 6 * i + j) * W]); }
-        }
-    } } else {
-        prog.linearize();                                     // lane mapping: rebuild the final linearization instead
-    }
-    if constexpr (MODE == 0) prog.gradients(A, env);
-    else if constexpr (MODE == 2) {
-        if constexpr (QUAD && DJ_REFINE) {
-            // the un-factored rows of the final linearization (the step kernel's copy may be older than its last iterate's):
-            // set_entries! once more into scratch rows; this also restores C134 / G134 and the limit rows of F
-            TL S2[3][12], U2[3][6], L2[6][3];
-            QuadBlocks<TL> K2(S2, U2, L2, q);
-            prog.refine = flagged;
-            prog.template evaluate<true>(K2);
-            prog.condense_limits(K2);
-            prog.store_blocks(K2);
-            prog.template gradients<true>(A, env, flagged);
-        }
-    }
-    else if constexpr (QUAD) prog.gradients_contact(A, env);
-#ifdef DJ_PROF2
-    if (active && q == 0 && A.vel && k == 8) { TIO* vo = A.vel + (size_t)env * 6 * G.Nb + 48; for (int i = 0; i < 16; ++i) vo[i] = TIO((double)prog.p2c[i]); }
-#endif
-#ifdef DJ_PROF
-    if (active && q == 0 && A.vel && k == 2) { TIO* vo = A.vel + (size_t)env * 6 * G.Nb + 12; vo[0] = TIO((double)prog.pc[0]); vo[1] = TIO((double)prog.pc[1]); vo[2] = TIO((double)prog.pc[5]); vo[3] = TIO((double)prog.pc[6]); vo[4] = TIO((double)(wv.clock() - t_all)); vo[5] = TIO((double)prog.pc[4]); vo[6] = TIO((double)prog.pc[2]); vo[7] = TIO((double)prog.pc[3]); vo[8] = TIO((double)prog.pc[7]); }
-#endif
-}
-
-// CONT = true: the continuation kernel's entry (Globals::iter_cap): `wave_index` is a workgroup of the step kernel that left
-// environments unfinished (DJ_STATUS_CONTINUE in KernelArgs::status); their iterate comes back from the hand-off record, the
-// loop scalars from KernelArgs::resume, and the Newton loop goes on.  The other environments of the workgroup stay as they are.
-template <class TIO, class T, class TL, int MAXC, bool QUAD, class Wave, bool CONT = false>
-DJ_HD void step_entry(Wave& wv, const KernelArgs<TIO, T>& A, int wave_index) {
-    constexpr bool RF = QUAD && DJ_REFINE && Wave::kRefine;      // the refining build: re-solves the environments the plain kernel deferred
-    static_assert(!(RF && CONT), "the continuation kernel is a plain build");
-    if constexpr (RF) {
-        const int envl_ = 4 * A.G.S, E_ = wv.width() / envl_, env_ = wave_index * E_ + wv.lane() / envl_;
-        if (A.flag == nullptr || !wv.any(env_ < A.B && A.flag[env_] != 0)) return;          // nothing deferred in this workgroup (uniform)
-    }
-    DJ_LANE_SETUP(0, CONT ? A.status[env] == DJ_STATUS_CONTINUE : (!RF || A.flag[env] != 0))
-#ifdef DJ_DEBUG
-    prog.dbg_on = A.dbg != nullptr; prog.trace = getenv("DJ_TRACE") != nullptr;
-    if (A.dbg && active && q == 0) prog.dbg = A.dbg + ((size_t)env * G.Nb + k) * 512;
-#endif
-    int iters = 0;
-#ifdef DJ_PROF
-    unsigned long long t_all = wv.clock();
-#endif
-    int status;
-    if constexpr (CONT) {
-        SolveCarry<T> carry;
-        carry.undercut = G.undercut; carry.rvio = carry.bvio = T(0); carry.n = 0; carry.no_progress = 0; carry.excessive = 0;
-        if (active) {                                          // the iterate the capped solve stopped at (identical on the four lanes of a quad)
-            const T* r = A.sol + ((size_t)env * G.S + (size_t)k) * sol_record<MAXC>();
-            for (int i = 0; i < 3; ++i) { prog.L.v[i] = r[i]; prog.L.w[i] = r[3 + i]; }
-            for (int i = 0; i < 6; ++i) prog.L.lam[i] = r[6 + i];
-            prog.L.ls[0] = r[12]; prog.L.ls[1] = r[13]; prog.L.lg[0] = r[14]; prog.L.lg[1] = r[15];
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) for (int i = 0; i < 4; ++i) { prog.L.cs[c][i] = r[16 + 8 * c + i]; prog.L.cg[c][i] = r[20 + 8 * c + i]; }
-            prog.mu = r[16 + 8 * MAXC];
-            const T* cr = A.resume + (size_t)env * CARRY_PER_ENV;
-            carry.undercut = cr[0]; carry.rvio = cr[1]; carry.bvio = cr[2]; carry.n = (int)cr[3]; carry.no_progress = (int)cr[4]; carry.excessive = (int)cr[5];
-        }
-        carry.n = G.iter_cap;                                  // (wave-uniform: the capped loop leaves at exactly this iteration)
-        status = prog.template mehrotra<true>(iters, /*need_factors=*/false, &carry);
-    } else {
-    // The factors of the final linearization leave this kernel only through A.fac (the refining IFT kernel reads them); the plain IFT
-    // kernels linearize once more themselves (lu_prepare / linearize in grad_entry), so a differentiable step without refinement may
-    // skip the set_entries! + factorization after the converging iteration exactly like a forward-only one.
-    status = prog.mehrotra(iters, /*need_factors=*/QUAD && A.fac != nullptr, nullptr,
-                           (!RF && G.iter_cap > 0 && A.resume != nullptr) ? DJ_GLOBAL_PTR(T, A.resume) + (size_t)(env < A.B ? env : 0) * CARRY_PER_ENV : nullptr);
-    }
-#ifdef DJ_PROF
-    prog.pc[7] = wv.clock() - t_all;
-#endif
-    if constexpr (!RF && !CONT) {                             // iteration cap: the loop scalars of the unfinished solves, and this workgroup on the continuation list
-        if (A.resume != nullptr) {
-            // (the mark is per WORKGROUP: the IFT of a listed workgroup's finished environments waits for the continuation as well, so that
-            //  no IFT launch ever works on part of a workgroup -- the per-lane staging areas KernelArgs::lu / ypark are indexed by workgroup)
-            const bool listed = wv.any(active && status == DJ_STATUS_CONTINUE);
-            if (active && q == 0 && k == 0) A.resume[(size_t)env * CARRY_PER_ENV + CARRY_MARK] = listed ? T(1) : T(0);
-            if (listed && lane == 0) A.cont_list[wv.atomic_inc(A.cont_count)] = A.wave_base + wave_index;
-        }
-    }
-    if constexpr (CONT) { if (Wave::kReplicas > 1 && wv.replica() != 0) return; }   // every replica holds the same result; the first one writes it
-    T gr_env = T(0);
-    if constexpr (QUAD && DJ_REFINE) { if (A.diag_out) { T v1[1] = {prog.growth}; prog.template env_reduce_quad_all<1>(v1); gr_env = v1[0]; } }
-    if (active && q == 0 && A.sol) {                          // hand-off to the IFT kernel, in the state precision
-        T* r = A.sol + ((size_t)env * G.S + (size_t)k) * sol_record<MAXC>();
-        for (int i = 0; i < 3; ++i) { r[i] = prog.L.v[i]; r[3 + i] = prog.L.w[i]; }
-        for (int i = 0; i < 6; ++i) r[6 + i] = prog.L.lam[i];
-        r[12] = prog.L.ls[0]; r[13] = prog.L.ls[1]; r[14] = prog.L.lg[0]; r[15] = prog.L.lg[1];
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) for (int i = 0; i < 4; ++i) { r[16 + 8 * c + i] = prog.L.cs[c][i]; r[20 + 8 * c + i] = prog.L.cg[c][i]; }
-        r[16 + 8 * MAXC] = prog.mu;
-#if DJ_MLIM
-        for (int m = 0; m < NLM; ++m) for (int i = 0; i < 2; ++i) { r[sol_mlim_off<MAXC>() + 4 * m + i] = prog.L.mls[m][i]; r[sol_mlim_off<MAXC>() + 4 * m + 2 + i] = prog.L.mlg[m][i]; }
-#endif
-#if DJ_CUT
-        for (int c = 0; c < NCUT; ++c) for (int i = 0; i < 6; ++i) r[sol_cut_off<MAXC>() + 6 * c + i] = prog.clam[c][i];
-#endif
-        if (QUAD) {
-            T* r2 = r + 17 + 8 * MAXC;
-            for (int i = 0; i < 6; ++i) { r2[i] = prog.F.t_a[i]; r2[6 + i] = prog.F.t_b[i]; }
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) if (c < P.ncontact) for (int i = 0; i < 18; ++i) r2[12 + 18 * c + i] = prog.ccold(c).G134[i];
-        }
-        r[sol_flag_off<MAXC>()] = (RF || status == DJ_STATUS_DEFERRED) ? T(1) : T(0);
-    }
-    if (!RF && A.flag && active && q == 0 && k == 0) A.flag[env] = status == DJ_STATUS_DEFERRED ? 1 : 0;
-    if (QUAD && A.fac && (!RF || active)) {
-        T* f = A.fac + (size_t)wave_index * FAC_PER_LANE * wv.width() + lane;
-        const int W = wv.width();
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 12; ++j) f[(size_t)(12 * i + j) * W] = T(prog.F.Sq[i][j]);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) { f[(size_t)(36 + 6 * i + j) * W] = T(prog.F.Uq[i][j]); f[(size_t)(54 + 6 * i + j) * W] = T(prog.F.Lq[j][i]); }
-        }
-    }
-    if (active && q == 0) {
-        T zn[13];
-        prog.next_state(zn);
-        TIO* o = A.z_next + (size_t)env * 13 * G.Nb + 13 * k;
-        for (int i = 0; i < 13; ++i) o[i] = TIO(zn[i]);
-        if (k == 0) { if (A.status) A.status[env] = status; if (A.iters) A.iters[env] = iters; if (A.mu_out) A.mu_out[env] = prog.mu; }
-        if constexpr (QUAD && DJ_REFINE) { if (k == 0 && A.diag_out) { A.diag_out[2 * env] = prog.wstiff; A.diag_out[2 * env + 1] = gr_env; } }
-        if (A.vel) { TIO* vo = A.vel + (size_t)env * 6 * G.Nb + 6 * k; for (int i = 0; i < 3; ++i) { vo[i] = TIO(prog.L.v[i]); vo[3 + i] = TIO(prog.L.w[i]); } }
-        if (A.res) { TIO* ro = A.res + (size_t)env * 6 * G.Nb + 6 * k; for (int i = 0; i < 6; ++i) ro[i] = TIO(prog.rb[i]); }
-#ifdef DJ_PROF2
-        if (A.vel && k == 4 && G.Nb >= 9) { TIO* vo = A.vel + (size_t)env * 6 * G.Nb + 24; for (int i = 0; i < 24; ++i) vo[i] = TIO((double)prog.p2c[i]); }
-#endif
-#ifdef DJ_PROF
-        if (A.vel && k == 0) { TIO* vo = A.vel + (size_t)env * 6 * G.Nb; for (int i = 0; i < 6; ++i) vo[i] = TIO((double)prog.pc[i]); }   // phases 0-5 (cycles)
-        if (A.vel && k == 1) { TIO* vo = A.vel + (size_t)env * 6 * G.Nb + 6; vo[0] = TIO((double)prog.pc[7]); vo[1] = TIO((double)iters); vo[2] = TIO((double)prog.pc[6]); }
-#endif
-        if (A.joint_imp && P.n_imp > 0) {
-            // get_solution order per joint: [tra: λ_t] [rot: s_up s_lo γ_up γ_lo λ_r]   (translational limits unsupported)
-            TIO* jo = A.joint_imp + (size_t)env * G.n_joint_imp + P.imp_off;
-            int o2 = 0;
-            if (prog.tlim) { jo[o2++] = TIO(prog.L.ls[0]); jo[o2++] = TIO(prog.L.ls[1]); jo[o2++] = TIO(prog.L.lg[0]); jo[o2++] = TIO(prog.L.lg[1]); }   // [tra: s_up s_lo γ_up γ_lo λ_t]
-#if DJ_MLIM
-            // limits on several coordinates: η = [s_up(n); s_lo(n); γ_up(n); γ_lo(n); λ] per half (split_impulses, src/joints/joint.jl)
-            if (prog.kMLim && prog.nlm() > 0) { const int nt_ = prog.mlp->nt;
-                for (int i = 0; i < 2; ++i) for (int m = 0; m < nt_; ++m) jo[o2++] = TIO(prog.L.mls[m][i]);
-                for (int i = 0; i < 2; ++i) for (int m = 0; m < nt_; ++m) jo[o2++] = TIO(prog.L.mlg[m][i]); }
-#endif
-            for (int i = 0; i < 3; ++i) if (i < P.nl_t) jo[o2++] = TIO(prog.L.lam[i]);
-            if (P.nlim_r > 0) { jo[o2++] = TIO(prog.L.ls[0]); jo[o2++] = TIO(prog.L.ls[1]); jo[o2++] = TIO(prog.L.lg[0]); jo[o2++] = TIO(prog.L.lg[1]); }
-#if DJ_MLIM
-            if (prog.kMLim && prog.nlm() > 0) { const int nt_ = prog.mlp->nt, nr_ = prog.mlp->nr;
-                for (int i = 0; i < 2; ++i) for (int m = 0; m < nr_; ++m) jo[o2++] = TIO(prog.L.mls[nt_ + m][i]);
-                for (int i = 0; i < 2; ++i) for (int m = 0; m < nr_; ++m) jo[o2++] = TIO(prog.L.mlg[nt_ + m][i]); }
-#endif
-            for (int i = 0; i < 3; ++i) if (i < P.nl_r) jo[o2++] = TIO(prog.L.lam[3 + i]);
-        }
-#if DJ_CUT
-        if constexpr (!QUAD) { if (A.joint_imp && k == 0) for (int c = 0; c < NCUT; ++c) if (c < prog.ncut) {     // the cut joints' multipliers, get_solution order [λ_t; λ_r]
-            TIO* jo = A.joint_imp + (size_t)env * G.n_joint_imp + A.cuts[c].imp_off; int o2 = 0;
-            for (int i = 0; i < 3; ++i) if (i < A.cuts[c].nl_t) jo[o2++] = TIO(prog.clam[c][i]);
-            for (int i = 0; i < 3; ++i) if (i < A.cuts[c].nl_r) jo[o2++] = TIO(prog.clam[c][3 + i]);
-        } }
-#endif
-        if (A.contact_sg) {
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) if (c < P.ncontact) {
-                TIO* co = A.contact_sg + (size_t)env * (2 * NCV) * G.Nc + (2 * NCV) * P.contact[c];       // [s; γ] per contact (8; LinearContact builds: 12)
-                for (int i = 0; i < NCV; ++i) { co[i] = TIO(prog.L.cs[c][i]); co[NCV + i] = TIO(prog.L.cg[c][i]); }
-            }
-        }
-    }
 }
 
 } // namespace dj

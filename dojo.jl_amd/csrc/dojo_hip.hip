@@ -589,7 +589,7 @@ int ensure_pipe(DojoSim* s, size_t NG) {
     while (s->grad_done[0].size() < NG)
         for (int p = 0; p < 2; ++p) { hipEvent_t dev_; HIPCHK(hipEventCreateWithFlags(&dev_, hipEventDisableTiming)); s->grad_done[p].push_back(dev_); }
     while (s->main_events.size() < NG) { hipEvent_t ev_; HIPCHK(hipEventCreateWithFlags(&ev_, hipEventDisableTiming)); s->main_events.push_back(ev_); }
-    ENSURE(s->d_sol2, (size_t)s->B * s->M.S * dj::sol_record<8, true>() * sizeof(double));
+    ENSURE(s->d_sol2, (size_t)s->B * s->M.S * dj::HANDOFF_MAX * sizeof(double));
     return DOJO_OK;
 }
 // the caller's stream waits for everything the environment groups have in flight
@@ -658,15 +658,15 @@ int refuse_unsupported(const DojoSim* s, bool want_dz, bool want_dc) {
 typedef int (*launcher_t)(const void*, int, void*, int, void*); typedef int (*claunch_t)(const void*, int, void*);
 enum { FAM_PLAIN, FAM_TSD, FAM_GEN, FAM_LIN, FAM_SS };
 struct Variant { int family, maxc, waves; launcher_t step[2]; claunch_t cgrad[2]; size_t sol_rec; };
-#define DJ_V(fam, pre, mc, nw, rec) {fam, mc, nw, {dojo_launch_##pre##double_##mc##_##nw, dojo_launch_##pre##float_##mc##_##nw}, {nullptr, nullptr}, (size_t)rec}
+#define DJ_V(fam, pre, mc, nw) {fam, mc, nw, {dojo_launch_##pre##double_##mc##_##nw, dojo_launch_##pre##float_##mc##_##nw}, {nullptr, nullptr}, (size_t)dj::HandOff<mc, fam == FAM_GEN>::size}
 #define DJ_VC(fam, pre, mc, nw) {fam, mc, nw, {dojo_launch_##pre##double_##mc##_##nw, dojo_launch_##pre##float_##mc##_##nw}, \
-                                 {dojo_launch_cgrad_##pre##double_##mc##_##nw, dojo_launch_cgrad_##pre##float_##mc##_##nw}, (size_t)dj::sol_record<mc>()}
+                                 {dojo_launch_cgrad_##pre##double_##mc##_##nw, dojo_launch_cgrad_##pre##float_##mc##_##nw}, (size_t)dj::HandOff<mc, false>::size}
 const Variant g_variants[] = {        // (rows of one family and mapping: MAXC ascending)
-    DJ_VC(FAM_PLAIN, , 1, 1), DJ_VC(FAM_PLAIN, , 4, 1), DJ_VC(FAM_PLAIN, , 8, 1), DJ_VC(FAM_PLAIN, , 1, 2), DJ_VC(FAM_PLAIN, , 4, 2), DJ_V(FAM_PLAIN, , 4, 0, dj::sol_record<4>()), DJ_V(FAM_PLAIN, , 8, 0, dj::sol_record<8>()),
-    DJ_VC(FAM_TSD, tsd_, 1, 1), DJ_VC(FAM_TSD, tsd_, 4, 1), DJ_V(FAM_TSD, tsd_, 4, 0, dj::sol_record<4>()), DJ_V(FAM_TSD, tsd_, 8, 0, dj::sol_record<8>()),
-    DJ_V(FAM_GEN, gen_, 4, 0, (dj::sol_record<4, true>())), DJ_V(FAM_GEN, gen_, 8, 0, (dj::sol_record<8, true>())),
-    DJ_V(FAM_LIN, lin_, 1, 1, dj::sol_record<1>()), DJ_V(FAM_LIN, lin_, 4, 1, dj::sol_record<4>()), DJ_V(FAM_LIN, lin_, 4, 0, dj::sol_record<4>()), DJ_V(FAM_LIN, lin_, 8, 0, dj::sol_record<8>()),
-    DJ_V(FAM_SS, ss_, 1, 1, dj::sol_record<1>())};
+    DJ_VC(FAM_PLAIN, , 1, 1), DJ_VC(FAM_PLAIN, , 4, 1), DJ_VC(FAM_PLAIN, , 8, 1), DJ_VC(FAM_PLAIN, , 1, 2), DJ_VC(FAM_PLAIN, , 4, 2), DJ_V(FAM_PLAIN, , 4, 0), DJ_V(FAM_PLAIN, , 8, 0),
+    DJ_VC(FAM_TSD, tsd_, 1, 1), DJ_VC(FAM_TSD, tsd_, 4, 1), DJ_V(FAM_TSD, tsd_, 4, 0), DJ_V(FAM_TSD, tsd_, 8, 0),
+    DJ_V(FAM_GEN, gen_, 4, 0), DJ_V(FAM_GEN, gen_, 8, 0),
+    DJ_V(FAM_LIN, lin_, 1, 1), DJ_V(FAM_LIN, lin_, 4, 1), DJ_V(FAM_LIN, lin_, 4, 0), DJ_V(FAM_LIN, lin_, 8, 0),
+    DJ_V(FAM_SS, ss_, 1, 1)};
 // the build that serves a mechanism under the mapping NW (mapping_waves): of its family and mapping, the smallest MAXC that holds its contacts per body
 // (the largest where none does); null: no such build
 const Variant* variant_of(const dj::HostModel& M, int NW) {
@@ -697,7 +697,7 @@ Geometry geometry_of(const DojoSim* s, const Span& sp, bool g) {
 
 // the handle's workspaces a launch uses, allocated on first use (all in the arithmetic type of the kernels, fp64)
 int ensure_workspaces(DojoSim* s, const StepIO& io, const Mode& m, const Geometry& ge, bool g, bool reorder) {
-    const size_t B = s->B, wT = sizeof(double), sol_bytes = B * s->M.S * dj::sol_record<8, true>() * wT;       // (the hand-off: sized for the largest record)
+    const size_t B = s->B, wT = sizeof(double), sol_bytes = B * s->M.S * dj::HANDOFF_MAX * wT;       // (the hand-off: sized for the largest record)
     if (g) {
         ENSURE(s->d_sol, sol_bytes);
         if (ge.quad) { ENSURE(s->d_fac, ge.waves_total * dj::FAC_PER_LANE * ge.lanes * wT); ENSURE(s->d_lu, ge.waves_total * dj::LU_PER_LANE * ge.lanes * wT); }

@@ -3,7 +3,7 @@
 // levels of the kinematic tree, leaves first).  Plain C++ (no HIP), shared
 // by the library and by the CPU SIMT emulator used in the tests.
 #pragma once
-#include "dojo_device.hpp"
+#include "dojo_entries.hpp"
 #include "../../include/dojo_hip.h"
 #include <vector>
 #include <string>

@@ -4,7 +4,7 @@
 //
 // One wavefront = 64/S environments x S supernodes (dojo_device.hpp); one workgroup = one wavefront.
 #include <hip/hip_runtime.h>
-#include "dojo_device.hpp"
+#include "dojo_entries.hpp"
 
 #ifndef DJ_TIO
 #define DJ_TIO float

@@ -14,7 +14,7 @@ def lib():
     if _lib is None:
         so = os.path.join(_HERE, "emu", "libcoords_emu.so")
         src = [os.path.join(_HERE, "emu", "coords_emu.cpp")] + [os.path.join(_HERE, "..", "dojo.jl_amd", "csrc", f)
-                                                                for f in ("dojo_coords.hpp", "dojo_host.hpp", "dojo_device.hpp", "dojo_math.hpp")]
+                                                                for f in ("dojo_coords.hpp", "dojo_host.hpp", "dojo_entries.hpp", "dojo_device.hpp", "dojo_math.hpp")]
         _build(so, src)
         _lib = C.CDLL(so)
         for f in ("coords_min2max", "coords_max2min", "coords_min2max_jacobian", "coords_max2min_jacobian"):

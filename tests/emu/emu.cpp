@@ -1,6 +1,6 @@
 // emu.cpp -- thread-based SIMT emulator for the lane program (TEST INFRASTRUCTURE).
 //
-// Runs the *same* device source (dojo.jl_amd/csrc/dojo_device.hpp) on the CPU: every lane of a
+// Runs the *same* device source (the entries of dojo.jl_amd/csrc/dojo_entries.hpp around the lane program of dojo_device.hpp) on the CPU: every lane of a
 // "wave" is a std::thread and wave shuffles / votes are implemented with a barrier.  This lets
 // the CPU-only test tier (-m "not gpu") check the shipped device algorithm against the oracle.
 // It is not a product path: libdojo_hip.so has no CPU fallback.

@@ -1,5 +1,5 @@
 """ctypes wrapper of the SIMT emulator (tests/emu/libemu.so): runs the shipped device source
-(dojo.jl_amd/csrc/dojo_device.hpp) on CPU threads.  Test infrastructure only."""
+(dojo.jl_amd/csrc/dojo_entries.hpp and the lane program it includes) on CPU threads.  Test infrastructure only."""
 import ctypes as C
 import os
 import subprocess
@@ -28,7 +28,7 @@ def lib_linear():
     if _lib_lin is None:
         so = os.path.join(_HERE, "emu", "libemu_lin.so")
         src = [os.path.join(_HERE, "emu", "emu.cpp")] + [os.path.join(_HERE, "..", "dojo.jl_amd", "csrc", f)
-                                                         for f in ("dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
+                                                         for f in ("dojo_entries.hpp", "dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
         _build(so, src, ("-DDJ_LINEAR=1", "-DDJ_TSD=0"))      # (the flag set of the GPU's LinearContact builds)
         _lib_lin = C.CDLL(so)
         _lib_lin.emu_step.restype = C.c_int
@@ -45,7 +45,7 @@ def lib_mlim():
     if _lib_mlim is None:
         so = os.path.join(_HERE, "emu", "libemu_mlim.so")
         src = [os.path.join(_HERE, "emu", "emu.cpp")] + [os.path.join(_HERE, "..", "dojo.jl_amd", "csrc", f)
-                                                         for f in ("dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
+                                                         for f in ("dojo_entries.hpp", "dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
         _build(so, src, ("-DDJ_MLIM=1", "-DDJ_CUT=1"))
         _lib_mlim = C.CDLL(so)
         _lib_mlim.emu_step.restype = C.c_int
@@ -61,7 +61,7 @@ def lib_ss():
     if _lib_ss is None:
         so = os.path.join(_HERE, "emu", "libemu_ss.so")
         src = [os.path.join(_HERE, "emu", "emu.cpp")] + [os.path.join(_HERE, "..", "dojo.jl_amd", "csrc", f)
-                                                         for f in ("dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
+                                                         for f in ("dojo_entries.hpp", "dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
         _build(so, src, ("-DDJ_TSD=0",))
         _lib_ss = C.CDLL(so)
         _lib_ss.emu_step.restype = C.c_int
@@ -76,7 +76,7 @@ def lib():
             return _lib
         so = os.path.join(_HERE, "emu", "libemu.so")
         src = [os.path.join(_HERE, "emu", "emu.cpp")] + [os.path.join(_HERE, "..", "dojo.jl_amd", "csrc", f)
-                                                         for f in ("dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
+                                                         for f in ("dojo_entries.hpp", "dojo_device.hpp", "dojo_host.hpp", "dojo_math.hpp")]
         _build(so, src)
         _lib = C.CDLL(so)
         _lib.emu_step.restype = C.c_int

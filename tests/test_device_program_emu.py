@@ -1,4 +1,4 @@
-"""CPU tier: the shipped device source (dojo.jl_amd/csrc/dojo_device.hpp) run under the
+"""CPU tier: the shipped device source (dojo.jl_amd/csrc/dojo_entries.hpp + dojo_device.hpp) run under the
 thread-based SIMT emulator (tests/emu) against the oracle.  Small cases only (the emulator pays
 two barriers per wave shuffle); the real parity tests are the -m gpu ones."""
 import os
