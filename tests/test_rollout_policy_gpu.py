@@ -289,6 +289,23 @@ def test_zero_policy_is_the_open_loop(name, B, dtype):
     assert same(r["Z"], Z) and same(r["S"], st)
 
 
+@pytest.mark.parametrize("per_env", [1, 0])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_null_bias_is_the_zero_bias(dtype, per_env):
+    """bias = NULL is read as 0.0 in front of the sum: every output is the bits of the run with a bias of zeros"""
+    name, B, steps = "cartpole", 3, 3
+    gm = _handle(name, dtype, B)
+    inp = dict(inputs(name, dtype, B, steps=steps))
+    if not per_env:
+        inp["W"] = inp["W"][0]
+    zeros = dict(inp); zeros["bias"] = np.zeros(inp["W"].shape[:-1], gm.np_dtype)
+    null = dict(inp); null["bias"] = None
+    a, b = rollout_policy_dev(gm, name, null, steps=steps, per_env=bool(per_env)), rollout_policy_dev(gm, name, zeros, steps=steps, per_env=bool(per_env))
+    for k in "ZOUS":
+        assert same(a[k], b[k]), k
+    assert not same(a["U"], inp["U_ff"])       # (the policy acted)
+
+
 def test_independence_of_groups_repetition_and_sharing():
     name, dtype, B = "ant", "f32", 200
     gm = _handle(name, dtype, B)
