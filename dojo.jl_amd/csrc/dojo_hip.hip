@@ -15,6 +15,7 @@
 #include "dojo_mlp.hpp"
 #include "dojo_data_adjoint.hpp"
 #include "dojo_tangent.hpp"
+#include "dojo_riccati.hpp"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -1106,6 +1107,26 @@ int launch_tangent(const DojoSim* s, int H, int T, const void* DZ, const void* D
     return DOJO_OK;
 }
 
+// dojo_riccati_dev: the Riccati backward pass (dojo_riccati.hpp), one workgroup per environment, one launch; NQ = register accumulators per lane
+template <class TIO, int NQ>
+int launch_riccati(const DojoSim* s, int H, const DojoRiccati& r, hipStream_t st) {
+    const int nu = (int)s->M.nu, n = 2 * nu;
+    const dj::riccati::Args<TIO> A{(const TIO*)r.A, (const TIO*)r.Bm, r.status, (const TIO*)r.lx, (const TIO*)r.lu, (const TIO*)r.lxx, (const TIO*)r.luu, (const TIO*)r.lux, (const TIO*)r.mu,
+                                   (TIO*)r.K, (TIO*)r.kff, r.fail, (TIO*)r.dV, (TIO*)r.Vx, (TIO*)r.Vxx, H, s->B, n, nu, r.na, r.act_off};
+    hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::lds_bytes(n, r.na), st, A);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
+}
+template <class TIO>
+int launch_riccati_any(const DojoSim* s, int H, const DojoRiccati& r, hipStream_t st) {
+    switch (dj::riccati::accumulators(2 * (int)s->M.nu, r.na)) {
+        case 3: return launch_riccati<TIO, 3>(s, H, r, st);
+        case 6: return launch_riccati<TIO, 6>(s, H, r, st);
+        case 12: return launch_riccati<TIO, 12>(s, H, r, st);
+        default: return launch_riccati<TIO, 24>(s, H, r, st);
+    }
+}
+
 int launch_policy_any(const DojoSim* s, const DojoPolicy& p, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
     return s->dtype == DOJO_DTYPE_F32 ? launch_policy<float>(s, p, z, csg, uff, obs, u, sp) : launch_policy<double>(s, p, z, csg, uff, obs, u, sp);
 }
@@ -1832,6 +1853,56 @@ int dojo_rollout_tangents(DojoHandle s, const void* z0, const void* U, int32_t H
     TRY(rollout_core(s, H, io, nullptr));
     TRY(dojo_rollout_tangent_dev(s, H, T, dDZ.p, dDU.p, dDC.p, ddz0.p, ddU.p, ddth.p, tan_space, dZs.p, (const int32_t*)dS.p, ddZ.p, nullptr));
     return st.finish(s, dZs, H);
+}
+
+// ---- batched iLQR: the Riccati backward pass in minimal coordinates (dojo_riccati.hpp), IterativeLQR's backward pass over get_minimal_gradients! ----
+// what both entries refuse, before anything is allocated or launched
+static int refuse_riccati(DojoHandle s, int32_t H, const DojoRiccati* r, const char* who) {
+    const std::string w_ = std::string(who) + ": ";
+    if (!s || !r) { g_err = w_ + "bad argument (the handle and the DojoRiccati record are required)"; return DOJO_ERR_INVALID; }
+    if (H < 1) { g_err = w_ + "H must be >= 1"; return DOJO_ERR_INVALID; }
+    if (!r->A || !r->Bm || !r->lx || !r->lu || !r->lxx || !r->luu || !r->K || !r->kff || !r->fail) {
+        g_err = w_ + "A, Bm, lx, lu, lxx, luu, K, kff and fail must not be NULL"; return DOJO_ERR_INVALID;
+    }
+    if (s->M.nu == 0) { g_err = w_ + "the mechanism has no inputs"; return DOJO_ERR_INVALID; }
+    if (r->na < 1 || r->act_off < 0 || (long long)r->act_off + r->na > (long long)s->M.nu) { g_err = w_ + "the policy must drive inputs act_off .. act_off + na - 1 inside 0 .. nu - 1, na >= 1"; return DOJO_ERR_INVALID; }
+    if (s->M.has_loop) { g_err = w_ + "the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    const int n = 2 * (int)s->M.nu, m = r->na;
+    const size_t lds = dj::riccati::lds_bytes(n, m);
+    if (lds > 65536 || !dj::riccati::accumulators(n, m) || m > dj::riccati::MAX_M) {
+        g_err = w_ + "n = " + std::to_string(n) + ", na = " + std::to_string(m) + " needs " + std::to_string(lds) + " bytes of LDS per environment; the kernel holds at most 65536, n + na <= 110 (the accumulators of [Qxx Qxu; Qux Quu] are registers) and na <= " + std::to_string(dj::riccati::MAX_M);
+        return DOJO_ERR_UNSUPPORTED;
+    }
+    return DOJO_OK;
+}
+
+int dojo_riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, void* stream) {
+    Enter enter_(s);
+    TRY(refuse_riccati(s, H, r, "dojo_riccati_dev"));
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight: the last dojo_minimal_gradients_dev may be writing the record)
+    return s->dtype == DOJO_DTYPE_F32 ? launch_riccati_any<float>(s, H, *r, st) : launch_riccati_any<double>(s, H, *r, st);
+}
+
+// host pointers: upload, one launch, download
+int dojo_riccati(DojoHandle s, int32_t H, const DojoRiccati* r) {
+    Enter enter_(s);
+    TRY(refuse_riccati(s, H, r, "dojo_riccati"));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)r->na, HB = (size_t)H * B;
+    Staging st;
+    const auto &dA = st.input(HB * n * n * w, r->A), &dB = st.input(HB * n * nu * w, r->Bm), &dS = st.input(HB * sizeof(int32_t), r->status);
+    const auto &dlx = st.input((HB + B) * n * w, r->lx), &dlu = st.input(HB * m * w, r->lu), &dlxx = st.input((HB + B) * n * n * w, r->lxx);
+    const auto &dluu = st.input(HB * m * m * w, r->luu), &dlux = st.input(HB * m * n * w, r->lux), &dmu = st.input(B * w, r->mu);
+    const auto &dK = st.output(HB * m * n * w, r->K), &dk = st.output(HB * m * w, r->kff), &dF = st.output(B * sizeof(int32_t), r->fail);
+    const auto &ddV = st.output(B * 2 * w, r->dV), &dVx = st.output(B * n * w, r->Vx), &dVxx = st.output(B * n * n * w, r->Vxx);
+    TRY(st.allocate());
+    DojoRiccati d = *r;
+    d.A = dA.p; d.Bm = dB.p; d.status = (const int32_t*)dS.p; d.lx = dlx.p; d.lu = dlu.p; d.lxx = dlxx.p; d.luu = dluu.p; d.lux = dlux.p; d.mu = dmu.p;
+    d.K = dK.p; d.kff = dk.p; d.fail = (int32_t*)dF.p; d.dV = ddV.p; d.Vx = dVx.p; d.Vxx = dVxx.p;
+    TRY(dojo_riccati_dev(s, H, &d, nullptr));
+    return st.finish(s, Staging::Buf{0, nullptr, nullptr, nullptr}, H);      // (no state: the handle's own is left alone)
 }
 
 // ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----

@@ -47,11 +47,13 @@ def lib():
                   "dojo_rollout_policy_gradients",
                   "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
                   "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients",
-                  "dojo_rollout_tangent_dev", "dojo_rollout_tangents"):
+                  "dojo_rollout_tangent_dev", "dojo_rollout_tangents", "dojo_riccati_dev", "dojo_riccati"):
             getattr(L, f).restype = C.c_int
         vp, i32 = C.c_void_p, C.c_int32
         L.dojo_rollout_tangent_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]      # h, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, stream
         L.dojo_rollout_tangents.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]                 # h, z0, U, H, T, dz0, dU, dtheta, tan_space, Z, status, dZ
+        L.dojo_riccati_dev.argtypes = [vp, i32, vp, vp]                                                       # h, H, DojoRiccati*, stream
+        L.dojo_riccati.argtypes = [vp, i32, vp]                                                               # h, H, DojoRiccati*
         L.dojo_destroy.restype = None
         _lib = L
     return _lib
@@ -71,7 +73,8 @@ EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error",
                     "dojo_rollout_policy_gradients",
                     "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
                     "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients",
-                    "dojo_rollout_tangent_dev", "dojo_rollout_tangents"]
+                    "dojo_rollout_tangent_dev", "dojo_rollout_tangents",
+                    "dojo_riccati_dev", "dojo_riccati"]
 
 
 class DojoPolicy(C.Structure):
@@ -87,6 +90,14 @@ class DojoPolicyAdjoint(C.Structure):
     _fields_ = [("DZ", C.c_void_p), ("DU", C.c_void_p), ("OBS", C.c_void_p), ("status", C.c_void_p), ("z0", C.c_void_p), ("Z", C.c_void_p), ("M", C.c_void_p),
                 ("G", C.c_void_p), ("G_u", C.c_void_p), ("G_obs", C.c_void_p), ("gW", C.c_void_p), ("gbias", C.c_void_p), ("gU", C.c_void_p), ("gz", C.c_void_p),
                 ("cot_space", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DojoRiccati(C.Structure):
+    """include/dojo_hip.h `DojoRiccati`: the record (A, Bm, status), the quadratic cost, the regularisation and the outputs of the Riccati backward pass;
+    device pointers for dojo_riccati_dev, host pointers for dojo_riccati"""
+    _fields_ = [("A", C.c_void_p), ("Bm", C.c_void_p), ("status", C.c_void_p), ("lx", C.c_void_p), ("lu", C.c_void_p), ("lxx", C.c_void_p), ("luu", C.c_void_p),
+                ("lux", C.c_void_p), ("mu", C.c_void_p), ("K", C.c_void_p), ("kff", C.c_void_p), ("fail", C.c_void_p), ("dV", C.c_void_p), ("Vx", C.c_void_p),
+                ("Vxx", C.c_void_p), ("act_off", C.c_int32), ("na", C.c_int32)]
 
 
 MLP_MAX_LAYERS = 4      # DOJO_MLP_MAX_LAYERS
@@ -432,6 +443,24 @@ class BatchedMechanism:
         dZ = np.empty((H, B, T, s.nz if ts else s.nx), self.np_dtype)
         _chk(lib().dojo_rollout_tangents(self.h, _p(z0), _p(U), H, T, _p(dz0), _p(dU), _p(dtheta), ts, _p(Z), _p(st), _p(dZ)))
         return Z, st, dZ
+
+    def riccati(self, A, Bm, lx, lu, lxx, luu, lux=None, mu=None, status=None, act_off=0, na=None, value=True):
+        """dojo_riccati (host arrays): the backward pass of iLQR in minimal coordinates over the Jacobians A [H,B,n,n], Bm [H,B,n,nu] of H steps (minimal_gradients'
+        jx, ju), n = 2 nu, for the quadratic cost lx [H+1,B,n], lu [H,B,na], lxx [H+1,B,n,n], luu [H,B,na,na], lux [H,B,na,n] (None: zeros), the regularisation
+        mu [B] (None: zeros) and the step status [H,B] (None: all solved).  -> K [H,B,na,n], kff [H,B,na], dV [B,2], fail [B] (0, or 1 + the step whose Cholesky
+        failed) and, with value, Vx [B,n], Vxx [B,n,n]."""
+        B, nu = self.batch, self.spec.nu; n = 2 * nu
+        H = int(np.shape(A)[0]); na = int(nu - act_off if na is None else na)
+        A = self._arr(A, (H, B, n, n)); Bm = self._arr(Bm, (H, B, n, nu))
+        lx = self._arr(lx, (H + 1, B, n)); lu = self._arr(lu, (H, B, na)); lxx = self._arr(lxx, (H + 1, B, n, n)); luu = self._arr(luu, (H, B, na, na))
+        lux = None if lux is None else self._arr(lux, (H, B, na, n)); mu = None if mu is None else self._arr(mu, (B,))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        K = np.empty((H, B, na, n), self.np_dtype); kff = np.empty((H, B, na), self.np_dtype); fail = np.empty(B, np.int32); dV = np.empty((B, 2), self.np_dtype)
+        Vx = np.empty((B, n), self.np_dtype) if value else None; Vxx = np.empty((B, n, n), self.np_dtype) if value else None
+        a_ = lambda x: None if x is None else x.ctypes.data
+        r = DojoRiccati(a_(A), a_(Bm), a_(status), a_(lx), a_(lu), a_(lxx), a_(luu), a_(lux), a_(mu), a_(K), a_(kff), a_(fail), a_(dV), a_(Vx), a_(Vxx), int(act_off), na)
+        _chk(lib().dojo_riccati(self.h, H, C.byref(r)))
+        return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
 
     def rollout_policy(self, z0, W, steps, bias=None, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):
         """Closed-loop rollout (dojo_rollout_policy): simulate! with the affine feedback policy u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale))

@@ -1,0 +1,169 @@
+"""Batched iLQR in minimal coordinates (torch is plumbing only: it owns the buffers and evaluates the cost and the feedback law; the steps, their Jacobians and
+the Riccati backward pass are the library's kernels).  The reference's examples/trajectory_optimization run IterativeLQR over get_minimal_gradients!; this is
+the same loop for B environments at once -- one trajectory, one regularisation and one line search per environment, one launch per stage for the whole batch.
+
+    X, A, Bm, status = linearize_rollout(gm, x0, U)                   # H calls of dojo_minimal_gradients_dev, writing into slices of A and Bm
+    K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu)           # ONE launch of dojo_riccati_dev for all H steps
+    res = solve(gm, x0, U0, QuadraticCost(Q, R, Qf, x_goal), iters=10)
+
+Everything is enqueued on torch's current stream.  The driver reads one flag per trial step length (have all environments accepted?) and nothing else.
+Not here (include/dojo_hip.h, "Batched iLQR"): the forward pass as one fused call, costs shared across the batch, control limits, second-order dynamics terms,
+constraints, kinematic loops."""
+import ctypes as C
+
+import torch
+
+from . import api
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _dtype(gm):
+    return torch.float32 if gm.dtype_code == 1 else torch.float64
+
+
+def _want(t, what, dt, shape):
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != dt or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be a %s device tensor of shape %s, got %s %s" % (what, dt, tuple(shape), t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def linearize_rollout(gm, x0, U):
+    """x0 [B,n] (n = 2 nu), U [H,B,nu] -> X [H+1,B,n] (X[0] = x0), A [H,B,n,n], Bm [H,B,n,nu], status [H,B] int32: H calls of dojo_minimal_gradients_dev, each
+    stepping from X[k] into X[k+1] and writing its Jacobians straight into A[k], Bm[k] (row-major: the layout dojo_riccati_dev reads)."""
+    B, nu = gm.batch, gm.spec.nu; n, dt = 2 * nu, _dtype(gm)
+    if U.dim() != 3:
+        raise ValueError("U must be [H, B, nu]")
+    H = int(U.shape[0])
+    U = _want(U, "U", dt, (H, B, nu)); x0 = _want(x0, "x0", dt, (B, n))
+    dev = x0.device
+    X = torch.empty((H + 1, B, n), dtype=dt, device=dev); X[0] = x0
+    A = torch.empty((H, B, n, n), dtype=dt, device=dev); Bm = torch.empty((H, B, n, nu), dtype=dt, device=dev)
+    status = torch.empty((H, B), dtype=torch.int32, device=dev); iters = torch.empty(B, dtype=torch.int32, device=dev)
+    L, st = api.lib(), _stream(dev)
+    for k in range(H):
+        api._chk(L.dojo_minimal_gradients_dev(gm.h, _ptr(X[k]), _ptr(U[k]), _ptr(X[k + 1]), _ptr(status[k]), _ptr(iters), _ptr(A[k]), _ptr(Bm[k]), st))
+    return X, A, Bm, status
+
+
+def riccati(gm, A, Bm, lx, lu, lxx, luu, lux=None, mu=None, status=None, act_off=0, na=None, value=False):
+    """dojo_riccati_dev on device tensors: A [H,B,n,n], Bm [H,B,n,nu], lx [H+1,B,n], lu [H,B,na], lxx [H+1,B,n,n], luu [H,B,na,na], lux [H,B,na,n] or None,
+    mu [B] or None, status [H,B] int32 or None -> K [H,B,na,n], kff [H,B,na], dV [B,2], fail [B] int32 (and Vx [B,n], Vxx [B,n,n] with value).  One launch."""
+    B, nu = gm.batch, gm.spec.nu; n, dt = 2 * nu, _dtype(gm)
+    H = int(A.shape[0]); na = int(nu - act_off if na is None else na)
+    A = _want(A, "A", dt, (H, B, n, n)); Bm = _want(Bm, "Bm", dt, (H, B, n, nu))
+    lx = _want(lx, "lx", dt, (H + 1, B, n)); lu = _want(lu, "lu", dt, (H, B, na)); lxx = _want(lxx, "lxx", dt, (H + 1, B, n, n))
+    luu = _want(luu, "luu", dt, (H, B, na, na)); lux = _want(lux, "lux", dt, (H, B, na, n)); mu = _want(mu, "mu", dt, (B,))
+    status = _want(status, "status", torch.int32, (H, B))
+    dev = A.device
+    K = torch.empty((H, B, na, n), dtype=dt, device=dev); kff = torch.empty((H, B, na), dtype=dt, device=dev)
+    dV = torch.empty((B, 2), dtype=dt, device=dev); fail = torch.empty(B, dtype=torch.int32, device=dev)
+    Vx = torch.empty((B, n), dtype=dt, device=dev) if value else None; Vxx = torch.empty((B, n, n), dtype=dt, device=dev) if value else None
+    a_ = lambda t: None if t is None else t.data_ptr()
+    r = api.DojoRiccati(a_(A), a_(Bm), a_(status), a_(lx), a_(lu), a_(lxx), a_(luu), a_(lux), a_(mu), a_(K), a_(kff), a_(fail), a_(dV), a_(Vx), a_(Vxx), int(act_off), na)
+    api._chk(api.lib().dojo_riccati_dev(gm.h, H, C.byref(r), _stream(dev)))
+    return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
+
+
+class QuadraticCost:
+    """J = sum_k 1/2 (x_k - g)' Q (x_k - g) + 1/2 u_k' R u_k  +  1/2 (x_H - g)' Qf (x_H - g) over the driven inputs u [na].  Q, Qf [n,n], R [na,na], x_goal [n]
+    or [B,n]: device tensors in the handle's dtype.  Any object with `value` and `quadratize` can take its place in `solve`."""
+
+    def __init__(self, Q, R, Qf, x_goal):
+        self.Q, self.R, self.Qf, self.g = Q, R, Qf, x_goal
+
+    def value(self, X, U):
+        """X [H+1,B,n], U [H,B,na] -> J [B]"""
+        d = X - self.g
+        J = 0.5 * torch.einsum("kbi,ij,kbj->b", d[:-1], self.Q, d[:-1]) + 0.5 * torch.einsum("kbi,ij,kbj->b", U, self.R, U)
+        return J + 0.5 * torch.einsum("bi,ij,bj->b", d[-1], self.Qf, d[-1])
+
+    def quadratize(self, X, U):
+        """-> lx [H+1,B,n], lu [H,B,na], lxx [H+1,B,n,n], luu [H,B,na,na], lux (None: zeros)"""
+        H, B = U.shape[:2]
+        d = X - self.g
+        lx = torch.cat([d[:-1] @ self.Q.T, (d[-1] @ self.Qf.T)[None]], 0)
+        lxx = torch.cat([self.Q.expand(H, B, -1, -1), self.Qf.expand(1, B, -1, -1)], 0).contiguous()
+        return lx.contiguous(), (U @ self.R.T).contiguous(), lxx, self.R.expand(H, B, -1, -1).contiguous(), None
+
+
+def forward_pass(gm, Xbar, Ubar, K, kff, a, act_off, na):
+    """the closed-loop rollout for step length a: u_k[act] = Ubar_k[act] + a kff_k + K_k (x_k - Xbar_k) (torch), x_{k+1} by dojo_step_minimal_dev
+    -> X [H+1,B,n], U [H,B,nu], status [H,B]"""
+    H, B = Ubar.shape[:2]
+    dev = Xbar.device
+    X = torch.empty_like(Xbar); X[0] = Xbar[0]
+    U = Ubar.clone()
+    status = torch.empty((H, B), dtype=torch.int32, device=dev); iters = torch.empty(B, dtype=torch.int32, device=dev)
+    L, st = api.lib(), _stream(dev)
+    for k in range(H):
+        U[k, :, act_off:act_off + na] += a * kff[k] + torch.einsum("bij,bj->bi", K[k], X[k] - Xbar[k])
+        api._chk(L.dojo_step_minimal_dev(gm.h, _ptr(X[k]), _ptr(U[k]), _ptr(X[k + 1]), _ptr(status[k]), _ptr(iters), st))
+    return X, U, status
+
+
+def replay(gm, x0, U):
+    """the open-loop rollout of U from x0 through dojo_step_minimal_dev -> X [H+1,B,n]"""
+    H, B = U.shape[:2]
+    X = torch.empty((H + 1, B, x0.shape[1]), dtype=x0.dtype, device=x0.device); X[0] = x0
+    status = torch.empty(B, dtype=torch.int32, device=x0.device); iters = torch.empty(B, dtype=torch.int32, device=x0.device)
+    L, st = api.lib(), _stream(x0.device)
+    for k in range(H):
+        api._chk(L.dojo_step_minimal_dev(gm.h, _ptr(X[k]), _ptr(U[k].contiguous()), _ptr(X[k + 1]), _ptr(status), _ptr(iters), st))
+    return X
+
+
+def solve(gm, x0, U0, cost, iters, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625, 0.0078125),
+          mu_init=0.0, mu_min=1e-6, mu_grow=10.0, mu_shrink=0.1):
+    """iLQR for B environments.  x0 [B,n], U0 [H,B,nu] (all inputs; the policy drives act_off .. act_off + na - 1, na = nu - act_off by default, the others keep
+    U0's values), cost: an object with value(X, U_act) -> J [B] and quadratize(X, U_act) -> (lx, lu, lxx, luu, lux).  Each of the `iters` iterations:
+      1. linearize_rollout along the current controls: X, A, Bm, status;  J_old = cost.value
+      2. cost.quadratize, riccati with the per-environment regularisation mu -> K, kff, dV, fail
+      3. for a in alphas (defaults: 1, 1/2, .. 1/128), the whole batch at once: forward_pass; environment b ACCEPTS the first a with
+             J_new <= J_old + c1 (a dV[0] + a^2 dV[1])     (c1 = 1e-4; dV[0] < 0: an Armijo condition on the model's expected change)
+         and no failed step in either rollout and fail[b] = 0 (torch.where per environment); the trials stop once every environment has accepted
+      4. mu: an environment that accepted: mu <- mu_shrink mu (0.1), set to 0 below mu_min (1e-6); one with fail != 0 or without an accepted a:
+         mu <- max(mu_grow mu, mu_min) (x 10) and its controls stay as they were.  mu starts as mu_init (0).
+    -> dict: X [H+1,B,n], U [H,B,nu] (the last accepted trajectory of every environment), J [iters+1,B] (J[i]: the cost at the start of iteration i, J[iters]:
+    at the end), a [iters,B] (the accepted step length, 0: none), mu [iters,B] (the regularisation each backward pass ran with), fail [iters,B], dV [iters,B,2]."""
+    B, nu = gm.batch, gm.spec.nu; dt = _dtype(gm)
+    na = int(nu - act_off if na is None else na)
+    dev = x0.device
+    U = U0.clone()
+    mu = torch.full((B,), float(mu_init), dtype=dt, device=dev)
+    hist = {"J": [], "a": [], "mu": [], "fail": [], "dV": []}
+    act = slice(act_off, act_off + na)
+    if int(iters) < 1:
+        raise ValueError("iters must be >= 1")
+    for _ in range(int(iters)):
+        X, A, Bm, status = linearize_rollout(gm, x0, U)
+        J = cost.value(X, U[:, :, act])
+        lx, lu, lxx, luu, lux = cost.quadratize(X, U[:, :, act])
+        K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na)
+        solved = (status == 0).all(0) & (fail == 0)
+        accepted = torch.zeros(B, dtype=torch.bool, device=dev)
+        a_acc = torch.zeros(B, dtype=dt, device=dev)
+        U_new = U.clone()
+        for a in alphas:
+            Xa, Ua, sa = forward_pass(gm, X, U, K, kff, float(a), act_off, na)
+            Ja = cost.value(Xa, Ua[:, :, act])
+            now = ~accepted & solved & (sa == 0).all(0) & (Ja <= J + c1 * (a * dV[:, 0] + a * a * dV[:, 1]))
+            U_new = torch.where(now[None, :, None], Ua, U_new); a_acc = torch.where(now, torch.full_like(a_acc, a), a_acc)
+            accepted |= now
+            if bool((accepted | ~solved).all()):
+                break
+        hist["J"].append(J); hist["a"].append(a_acc); hist["mu"].append(mu.clone()); hist["fail"].append(fail); hist["dV"].append(dV)
+        shrunk = mu * mu_shrink
+        mu = torch.where(accepted, torch.where(shrunk < mu_min, torch.zeros_like(mu), shrunk), torch.clamp(mu * mu_grow, min=mu_min))
+        U = U_new
+    X = replay(gm, x0, U)
+    hist["J"].append(cost.value(X, U[:, :, act]))
+    return {"X": X, "U": U, **{k: torch.stack(v) for k, v in hist.items()}}

@@ -261,6 +261,33 @@ function rollout_policy(bm::BatchedMechanism{T}, z0::Matrix{T}, W::Array{T}, H::
     return Z, OBS, U, status
 end
 
+"mirror of `DojoRiccati` (include/dojo_hip.h): fifteen pointers, two Int32"
+struct DojoRiccati
+    A::Ptr{Cvoid}; Bm::Ptr{Cvoid}; status::Ptr{Cvoid}; lx::Ptr{Cvoid}; lu::Ptr{Cvoid}; lxx::Ptr{Cvoid}; luu::Ptr{Cvoid}; lux::Ptr{Cvoid}; mu::Ptr{Cvoid}
+    K::Ptr{Cvoid}; kff::Ptr{Cvoid}; fail::Ptr{Cvoid}; dV::Ptr{Cvoid}; Vx::Ptr{Cvoid}; Vxx::Ptr{Cvoid}
+    act_off::Int32; na::Int32
+end
+
+"""
+the backward pass of iLQR in minimal coordinates (IterativeLQR's backward pass over get_minimal_gradients!, examples/trajectory_optimization) for the whole
+batch on the device: dojo_riccati.  n = 2nu; the ABI is row-major, so every matrix is passed TRANSPOSED: A[n, n, B, H] holds jx' and Bm[nu, n, B, H] holds ju' of
+every step, lx[n, B, H + 1], lu[na, B, H], lxx[n, n, B, H + 1], luu[na, na, B, H], lux[n, na, B, H] (or `nothing`), mu[B] (or `nothing`), status[B, H] (or `nothing`).
+The policy drives the inputs act_off + 1 : act_off + na.
+-> K[n, na, B, H] (K_k'), kff[na, B, H], dV[2, B], fail[B] (0, or 1 + the zero-based step whose Cholesky failed), Vx[n, B], Vxx[n, n, B].
+"""
+function riccati(bm::BatchedMechanism{T}, A::Array{T,4}, Bm::Array{T,4}, lx::Array{T,3}, lu::Array{T,3}, lxx::Array{T,4}, luu::Array{T,4};
+                 lux::Union{Nothing,Array{T,4}}=nothing, mu::Union{Nothing,Vector{T}}=nothing, status::Union{Nothing,Matrix{Int32}}=nothing, act_off::Integer=0) where T
+    H = size(A, 4); n = 2 * bm.nu; na = size(lu, 1)
+    K = Array{T}(undef, n, na, bm.batch, H); kff = Array{T}(undef, na, bm.batch, H); fail = Vector{Int32}(undef, bm.batch)
+    dV = Matrix{T}(undef, 2, bm.batch); Vx = Matrix{T}(undef, n, bm.batch); Vxx = Array{T}(undef, n, n, bm.batch)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve A Bm status lx lu lxx luu lux mu K kff fail dV Vx Vxx begin
+        r = Ref(DojoRiccati(p(A), p(Bm), p(status), p(lx), p(lu), p(lxx), p(luu), p(lux), p(mu), p(K), p(kff), p(fail), p(dV), p(Vx), p(Vxx), Int32(act_off), Int32(na)))
+        check(@ccall $(fn(:dojo_riccati))(bm.handle::Ptr{Cvoid}, Int32(H)::Int32, r::Ptr{DojoRiccati})::Cint)
+    end
+    return K, kff, dV, fail, Vx, Vxx
+end
+
 """
 reverse mode through a closed-loop rollout (no counterpart in Dojo.jl): the rollout of `rollout_policy` (without contact observations) and the
 gradient of a trajectory loss w.r.t. the policy, the feed-forward term and the initial state; the recorded Jacobians stay on the device.

@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""Trajectory optimisation with iLQR on the device: swing-up of B cartpoles from different start angles in ONE batch.
+
+The reference's examples/trajectory_optimization run IterativeLQR over get_minimal_gradients! for one mechanism.  Here every environment has its own
+trajectory, its own regularisation and its own line search, and every stage is one call for the whole batch:
+
+    linearize_rollout   H calls of dojo_minimal_gradients_dev (the step and its Jacobians in minimal coordinates, on the GPU)
+    riccati             ONE launch of dojo_riccati_dev: the backward pass of all H steps of all environments (csrc/dojo_riccati.hpp)
+    forward_pass        H calls of dojo_step_minimal_dev per trial step length, the feedback law evaluated in torch between them
+
+The cart's input is the only driven one (act_off = 0, na = 1); the minimal state is [cart position, cart velocity, pole angle, pole angular velocity], the pole is
+upright at angle 0 and hangs at pi.
+
+    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations]          # needs a GPU: libdojo_hip has no CPU fallback
+"""
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "dojo.jl_amd", "host"))
+import dojo_amd as d                                   # noqa: E402
+from dojo_amd import api, ilqr                         # noqa: E402
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    B = int(argv[0]) if len(argv) > 0 else 64
+    H = int(argv[1]) if len(argv) > 1 else 60
+    iters = int(argv[2]) if len(argv) > 2 else 40
+    torch.cuda.init()                                  # (torch brings the GPU up first: INTEGRATION.md "Using the library next to PyTorch")
+    spec = d.get_cartpole(timestep=0.05)
+    gm = api.BatchedMechanism(spec, B, dtype="f64", opts=d.SolverOptions(rtol=1e-8, btol=1e-8))
+    dev, dt = torch.device("cuda"), torch.float64
+    # the starts: hanging, and a spread of angles around it
+    x0 = torch.zeros((B, 4), dtype=dt, device=dev)
+    x0[:, 2] = torch.linspace(np.pi, 0.5 * np.pi, B, dtype=dt, device=dev)
+    U0 = torch.zeros((H, B, spec.nu), dtype=dt, device=dev)
+    cost = ilqr.QuadraticCost(Q=torch.diag(torch.tensor([1.0, 0.1, 1.0, 0.1], dtype=dt, device=dev)) * spec.timestep,
+                              R=torch.eye(1, dtype=dt, device=dev) * 0.01 * spec.timestep,
+                              Qf=torch.diag(torch.tensor([100.0, 10.0, 100.0, 10.0], dtype=dt, device=dev)),
+                              x_goal=torch.zeros(4, dtype=dt, device=dev))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = ilqr.solve(gm, x0, U0, cost, iters, act_off=0, na=1)
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    J = res["J"].cpu().numpy()
+    for i in range(J.shape[0]):
+        print("iteration %2d: cost min %.4e  median %.4e  max %.4e" % (i, J[i].min(), np.median(J[i]), J[i].max()) +
+              ("" if i == J.shape[0] - 1 else "   accepted %d / %d, mu max %.1e" % (int((res["a"][i] > 0).sum()), B, float(res["mu"][i].max()))))
+    xH = res["X"][-1].cpu().numpy()
+    print("final |pole angle|: min %.3f  median %.3f  max %.3f rad (start: %.3f .. %.3f)" % (np.abs(xH[:, 2]).min(), np.median(np.abs(xH[:, 2])), np.abs(xH[:, 2]).max(), 0.5 * np.pi, np.pi))
+    print("%d environments x %d steps x %d iterations in %.2f s" % (B, H, iters, el))
+    assert (J[-1] <= J[0]).all()
+    gm.close()
+    return res
+
+
+if __name__ == "__main__":
+    main()

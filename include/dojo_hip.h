@@ -667,6 +667,51 @@ int  dojo_rollout_mlp_gradients(DojoHandle h, const void* z0, const DojoMlpPolic
                                 const void* G_u, const void* G_obs, void* Z, void* OBS, void* U_out, int32_t* status,
                                 void* gtheta, void* gU, void* gz);
 
+/* Batched iLQR: the Riccati backward pass in minimal coordinates (csrc/dojo_riccati.hpp).  The reference's examples/trajectory_optimization run
+ * IterativeLQR over get_minimal_gradients! (src/gradients/state.jl:183-217); this is IterativeLQR's backward pass for B environments at once, over the
+ * Jacobians H calls of dojo_minimal_gradients_dev leave on the device (jx -> A + k B n n, ju -> Bm + k B n nu: they fill the record in place).
+ * n = 2 nu; the policy drives the inputs act_off .. act_off + na - 1 as in DojoPolicy, m = na.  Per environment b, A_k = A[k][b] [n x n] row-major,
+ * B_k = the columns act_off .. act_off + na - 1 of Bm[k][b] [n x nu] row-major:
+ *     Vx <- lx_H;  Vxx <- lxx_H;  dV <- (0, 0);  fail <- 0
+ *     for k = H-1 .. 0:
+ *         if status && status[k][b] != 0:  A_k, B_k are NOT read (they may be NaN) and count as zero   (nothing flows through a failed step)
+ *         Qx  = lx_k + A^T Vx            Qu  = lu_k + B^T Vx
+ *         Qxx = lxx_k + A^T Vxx A        Qux = lux_k + B^T Vxx A  (lux NULL = 0)       Quu = luu_k + B^T Vxx B
+ *         Qreg = Quu + mu[b] I           (mu NULL = 0)
+ *         Cholesky Qreg = L L^T; a pivot that is not > 0 or not finite:  fail <- k + 1, stop this environment
+ *         kff_k = -Qreg^-1 Qu            K_k = -Qreg^-1 Qux
+ *         dV[0] += kff^T Qu              dV[1] += 1/2 kff^T Quu kff      (Quu, not Qreg: the expected change for step length a is  a dV[0] + a^2 dV[1])
+ *         Vx  = Qx  + K^T Quu kff + K^T Qu  + Qux^T kff
+ *         Vxx = Qxx + K^T Quu K   + K^T Qux + Qux^T K;   Vxx <- (Vxx + Vxx^T) / 2
+ * Outputs: K [H][B][na][n], kff [H][B][na], fail [B] (int32), and -- each may be NULL -- dV [B][2], Vx [B][n], Vxx [B][n][n] (the value function at k = 0).
+ * lxx_k and luu_k are symmetric matrices: the kernel uses their symmetric parts.  On failure at step k: K, kff of the steps <= k are written as zeros, the steps
+ * above k keep what was computed, dV, Vx, Vxx of that environment are written as zeros.  Every element of every given output is written in every case; a NaN in
+ * one environment's Jacobians ends as that environment's `fail` and nowhere else.
+ * Inputs are in the handle dtype and converted on load; every product and sum is fp64, the state of the recursion stays fp64 between the steps, outputs are
+ * rounded once.  No atomics; the summation order is fixed by (n, na) alone: results are bit-identical from run to run and do not depend on B or on the
+ * environment's place in the batch.
+ * dojo_riccati_dev: device pointers, ONE launch on `stream`, no synchronization.  dojo_riccati: host pointers, staged like the other host entries.  The
+ * struct is host memory, read during the call.
+ * DOJO_ERR_INVALID (text on the handle, nothing launched): H < 1; a NULL required member (A, Bm, lx, lu, lxx, luu, K, kff, fail); nu = 0; na < 1,
+ * act_off < 0 or act_off + na > nu.  DOJO_ERR_UNSUPPORTED: a mechanism with a kinematic loop (as dojo_minimal_gradients_dev); a shape the kernel's plan
+ * cannot hold -- more than 64 KB of LDS (8 (n (n + 1) / 2 + max(32 (n + na), na n + 2 na^2) + 2 n + 4 na + 8) bytes: Ant (28, 8) 13 KB, Atlas (72, 30) 55 KB),
+ * n + na > 110 (the accumulators of the lower triangle of [Qxx Qxu; Qux Quu] live in registers), na > 64 -- with the byte count in the text.
+ * Not part of it: the forward pass as one fused call (it needs time-varying gains in the controller kernel: a follow-up; dojo_amd/ilqr.py builds it from
+ * dojo_step_minimal_dev), costs shared across the batch or given as diagonals, control limits, second-order dynamics terms (DDP), constraints (augmented
+ * Lagrangian), kinematic loops. */
+typedef struct DojoRiccati {
+    const void* A;      /* [H][B][n][n]   row-major, jx of dojo_minimal_gradients_dev per step */
+    const void* Bm;     /* [H][B][n][nu]  row-major, ju ...; columns act_off .. act_off+na-1 are read */
+    const int32_t* status; /* [H][B] or NULL */
+    const void *lx, *lu, *lxx, *luu, *lux; /* [H+1][B][n], [H][B][na], [H+1][B][n][n], [H][B][na][na], [H][B][na][n] or NULL */
+    const void* mu;     /* [B] or NULL */
+    void *K, *kff; int32_t* fail;          /* required */
+    void *dV, *Vx, *Vxx;                   /* each may be NULL */
+    int32_t act_off, na;
+} DojoRiccati;
+int  dojo_riccati_dev(DojoHandle h, int32_t H, const DojoRiccati* r, void* stream);
+int  dojo_riccati(DojoHandle h, int32_t H, const DojoRiccati* r);
+
 /* get_state(environment) of DojoEnvironments (environments.jl:100-102; quadruped_sampling.jl:67-72): the minimal state
  * of the mechanism, and with contact_forces != 0 the normal impulse of every contact of the last step clamped to
  * [-1, 1] behind it (get_state(::AntARS), ant_ars.jl:72-80).  obs [B, 2*nu (+ Nc)].
