@@ -116,7 +116,7 @@ template <class S> DJ_HD PoseVel<S> origin_body() {
 }
 
 // a body state seeded with its 12 tangent directions [x, v, phi, omega] starting at direction d0 of N: q (x) (1, phi).  What the Jacobian kernels of
-// dojo_hip.hip and observation_jacobian_kernel (dojo_policy_adjoint.hpp) differentiate the maps below at.
+// dojo_coord_kernels.hpp and observation_jacobian_kernel (dojo_policy_adjoint.hpp) differentiate the maps below at.
 template <int N> DJ_HD PoseVel<Dual<N>> seed_body(const PoseVel<double>& p, int d0) {
     typedef Dual<N> D;
     PoseVel<D> s;

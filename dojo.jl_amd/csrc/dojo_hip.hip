@@ -1,4 +1,6 @@
-// dojo_hip.hip -- libdojo_hip.so: host side of the C ABI of include/dojo_hip.h (kernels: dojo_kernels.hip).
+// dojo_hip.hip -- libdojo_hip.so: host side of the C ABI of include/dojo_hip.h.  Host code only: the step and IFT kernels are dojo_kernels.hip's,
+// every other kernel family has a header of its own (dojo_coord_kernels.hpp, dojo_adjoint.hpp, dojo_policy.hpp, ...) and a launch_*<TIO> here;
+// the one kernel in this file is the scheduler's dispatch_order_kernel.
 //
 // One wavefront = 64/S environments x S supernodes (dojo_device.hpp).  One workgroup = one
 // wavefront (64 threads), so a batch of B environments launches ceil(B*S/64) workgroups --
@@ -8,7 +10,7 @@
 // fails with DOJO_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include "dojo_host.hpp"
-#include "dojo_coords.hpp"
+#include "dojo_coord_kernels.hpp"
 #include "dojo_adjoint.hpp"
 #include "dojo_policy.hpp"
 #include "dojo_policy_adjoint.hpp"
@@ -67,13 +69,6 @@ DJ_CDECL(dojo_launch_cgrad_tsd_float_1_1) DJ_CDECL(dojo_launch_cgrad_tsd_float_4
 #undef DJ_DECL
 }
 
-// temporary device buffer of a host-pointer entry point: freed on every return path
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-};
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return DOJO_ERR_DEVICE; } } while (0)
 #define TRY(x) do { int rc_ = (x); if (rc_ != DOJO_OK) return rc_; } while (0)      // (a failing call of the library's own has set the error text)
 
@@ -188,207 +183,17 @@ struct DojoSim {
 namespace {
 void handle_set_error(::DojoSim* s, const std::string& m) { std::lock_guard<std::mutex> g(s->err_m); s->err = m; }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Minimal <-> maximal coordinates: HBM-bound helper kernels around the step; every DojoEnvironments
-// step! goes through them (src/simulation/step.jl:42-60).  The per-joint maps live in dojo_coords.hpp, written for any
-// scalar: double gives the values, forward-mode dual numbers give the chain-rule Jacobians of get_minimal_gradients!
-// (src/gradients/state.jl:9-56, 136-217).  x per joint (mechanism.joints order): [dx(nu_t); dtheta(nu_r); dv(nu_t); domega(nu_r)]
-// ---------------------------------------------------------------------------------------------------------------
-namespace ckern {
-using namespace dj;
-using namespace dj::coords;
-// (load_body, origin_body: dojo_coords.hpp -- the policy kernel of dojo_policy.hpp reads bodies the same way)
-// get_next_state (src/mechanism/get.jl:126-134) of a body whose velocities are its solution: x + dt v, q (x) xi(w)
-template <class S> __device__ __forceinline__ void advance_body(PoseVel<S>& p, double dt) {
-    for (int i = 0; i < 3; ++i) p.x[i] = p.x[i] + p.v[i] * dt;
-    S qn[4]; next_qS(qn, p.q, p.w, dt); for (int i = 0; i < 4; ++i) p.q[i] = qn[i];
+// The ABI has two scalar types.  This is the one place that picks a template argument from the handle's: f is called with a float or a double,
+// `by_dtype(s, [&](auto t) { return launch_x<decltype(t)>(s, ...); })`.
+template <class F> int by_dtype(const DojoSim* s, F&& f) { return s->dtype == DOJO_DTYPE_F32 ? f(float()) : f(double()); }
+
+// What every entry that works in minimal coordinates refuses, under its own name: a mechanism with a kinematic loop
+int refuse_minimal(const DojoSim* s, const char* who, const char* note = " (the reference sets them with exclude_ids)") {
+    if (!s->M.has_loop) return DOJO_OK;
+    g_err = std::string(who) + ": the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal" + note + ": not supported";
+    return DOJO_ERR_UNSUPPORTED;
 }
 
-// one thread per environment: bodies in root -> leaves order (the parent's maximal state must exist first)
-template <class TIO>
-__global__ void min2max_kernel(const NodeP<double>* nodes, const int* order, int Nb, int nu, double dt, int B, const TIO* x, TIO* z) {
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= B) return;
-    const TIO* xe = x + (size_t)env * 2 * nu; TIO* ze = z + (size_t)env * 13 * Nb;
-    for (int oi = 0; oi < Nb; ++oi) {
-        const int k = order[oi];
-        const NodeP<double>& P = nodes[k];
-        const int nt = P.nu_t, nr = P.nu_r, n = nt + nr;
-        const TIO* xm = xe + 2 * P.u_off;
-        double dx[3] = {0, 0, 0}, dth[3] = {0, 0, 0}, dv[3] = {0, 0, 0}, dw[3] = {0, 0, 0};
-        for (int i = 0; i < 3; ++i) { if (i < nt) { dx[i] = (double)xm[i]; dv[i] = (double)xm[n + i]; } if (i < nr) { dth[i] = (double)xm[nt + i]; dw[i] = (double)xm[n + nt + i]; } }
-        const PoseVel<double> a = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
-        PoseVel<double> b;
-        joint_min2max(b, P, dt, a, dx, dth, dv, dw);
-        for (int i = 0; i < 3; ++i) { ze[13 * k + i] = (TIO)b.x[i]; ze[13 * k + 3 + i] = (TIO)b.v[i]; ze[13 * k + 10 + i] = (TIO)b.w[i]; }
-        for (int i = 0; i < 4; ++i) ze[13 * k + 6 + i] = (TIO)b.q[i];
-    }
-}
-// one thread per (environment, joint): the joints are independent
-template <class TIO>
-__global__ void max2min_kernel(const NodeP<double>* nodes, int Nb, int nu, double dt, int B, const TIO* z, TIO* x, int ldx) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int env = tid / Nb, k = tid % Nb;
-    if (env >= B) return;
-    const NodeP<double>& P = nodes[k];
-    const TIO* ze = z + (size_t)env * 13 * Nb; TIO* xm = x + (size_t)env * ldx + 2 * P.u_off;
-    const int nt = P.nu_t, nr = P.nu_r, n = nt + nr;
-    const PoseVel<double> b = load_body<double>(ze, k), a = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
-    double ct[3], cr[3], vt[3], vr[3];
-    joint_max2min(ct, cr, vt, vr, P, dt, a, b);
-    for (int i = 0; i < 3; ++i) { if (i < nt) { xm[i] = (TIO)ct[i]; xm[n + i] = (TIO)vt[i]; } if (i < nr) { xm[nt + i] = (TIO)cr[i]; xm[n + nt + i] = (TIO)vr[i]; } }
-}
-
-// the contact part of get_state(::AntARS) (DojoEnvironments/src/environments/ant_ars.jl:72-80): the normal impulse of
-// every contact, clamped to [-1, 1], behind the minimal state.  csg = [s(4); gamma(4)] per contact of the last step.
-template <class TIO>
-__global__ void contact_obs_kernel(int Nc, int B, const TIO* csg, TIO* obs, int ldx, int off) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int env = tid / Nc, c = tid % Nc;
-    if (env >= B) return;
-    const double g = (double)csg[(size_t)env * 8 * Nc + 8 * c + 4];
-    obs[(size_t)env * ldx + off + c] = (TIO)(g < -1.0 ? -1.0 : g > 1.0 ? 1.0 : g);
-}
-
-// save_to_storage! (src/simulation/storage.jl:50-67): one thread per (environment, body); inputs are the state the step
-// was solved at and what the step kernel left behind (solution velocities, cone variables, body residual rows)
-template <class TIO>
-__global__ void storage_kernel(const NodeP<double>* nodes, const ContactP<double>* contacts, int Nb, int Nc, int model, int cper, double dt, int env0, int nenv,
-                               const TIO* z, const TIO* vel, const TIO* csg, const TIO* res, const TIO* fext, TIO* storage) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int e = tid / Nb, k = tid % Nb;
-    if (e >= nenv) return;
-    const size_t env = (size_t)env0 + e;
-    double zb[13], v[3], w[3], rb[6], row[25], fe[6];
-    if (fext) for (int i = 0; i < 6; ++i) fe[i] = (double)fext[env * 6 * Nb + 6 * k + i];
-    for (int i = 0; i < 13; ++i) zb[i] = (double)z[env * 13 * Nb + 13 * k + i];
-    for (int i = 0; i < 3; ++i) { v[i] = (double)vel[env * 6 * Nb + 6 * k + i]; w[i] = (double)vel[env * 6 * Nb + 6 * k + 3 + i]; }
-    for (int i = 0; i < 6; ++i) rb[i] = (double)res[env * 6 * Nb + 6 * k + i];
-    auto other = [=](int b, double* zo, double* vo, double* wo) {            // (body-body contacts: the contact partner's state and solution)
-        for (int i = 0; i < 13; ++i) zo[i] = (double)z[env * 13 * Nb + 13 * b + i];
-        for (int i = 0; i < 3; ++i) { vo[i] = (double)vel[env * 6 * Nb + 6 * b + i]; wo[i] = (double)vel[env * 6 * Nb + 6 * b + 3 + i]; }
-    };
-    dj::storage_row(row, nodes[k], contacts, dt, zb, v, w, csg + env * (size_t)cper * Nc, rb, fext ? fe : (const double*)nullptr, nodes, other, model, cper, k, Nc);
-    TIO* o = storage + (env * Nb + k) * 25;
-    for (int i = 0; i < 25; ++i) o[i] = (TIO)row[i];
-}
-
-// ---- Jacobians by forward-mode differentiation of the same maps ----
-typedef Dual<24> D24;
-// minimal_to_maximal_jacobian (src/gradients/state.jl:136-181): one thread per environment, root -> leaves;
-// Jm[env][12 Nb rows][2 nu columns] row-major.  z must already hold minimal_to_maximal(x).
-template <class TIO>
-__global__ void min2max_jac_kernel(const NodeP<double>* nodes, const int* order, int Nb, int nu, double dt, int B, const TIO* x, const TIO* z, double* Jm) {
-    const int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= B) return;
-    const int nm = 2 * nu;
-    const TIO* xe = x + (size_t)env * nm; const TIO* ze = z + (size_t)env * 13 * Nb;
-    double* J = Jm + (size_t)env * 12 * Nb * nm;
-    for (int oi = 0; oi < Nb; ++oi) {
-        const int k = order[oi];
-        const NodeP<double>& P = nodes[k];
-        const int nt = P.nu_t, nr = P.nu_r, n = nt + nr;
-        const TIO* xm = xe + 2 * P.u_off;
-        // directions 0..11: the parent's reduced state; 12..12+2n-1: the joint's own minimal coordinates in layout order
-        D24 dx[3], dth[3], dv[3], dw[3];
-        for (int i = 0; i < 3; ++i) {
-            dx[i] = i < nt ? D24::seed((double)xm[i], 12 + i) : D24(0.0);             dv[i] = i < nt ? D24::seed((double)xm[n + i], 12 + n + i) : D24(0.0);
-            dth[i] = i < nr ? D24::seed((double)xm[nt + i], 12 + nt + i) : D24(0.0);    dw[i] = i < nr ? D24::seed((double)xm[n + nt + i], 12 + n + nt + i) : D24(0.0);
-        }
-        const PoseVel<double> a0 = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
-        PoseVel<D24> a = seed_body<24>(a0, 0), b;
-        joint_min2max(b, P, dt, a, dx, dth, dv, dw);
-        // rows of the child: x, v, phi = V(q_b^-1 (x) dq_b), omega
-        double Pm[12][24];
-        for (int d = 0; d < 24; ++d) {
-            for (int i = 0; i < 3; ++i) { Pm[i][d] = b.x[i].d[d]; Pm[3 + i][d] = b.v[i].d[d]; Pm[9 + i][d] = b.w[i].d[d]; }
-            const double q0 = b.q[0].v, q1 = b.q[1].v, q2 = b.q[2].v, q3 = b.q[3].v, e0 = b.q[0].d[d], e1 = b.q[1].d[d], e2 = b.q[2].d[d], e3 = b.q[3].d[d];
-            Pm[6][d] = q0 * e1 - q1 * e0 - q2 * e3 + q3 * e2;                 // vector part of conj(q) (x) dq
-            Pm[7][d] = q0 * e2 + q1 * e3 - q2 * e0 - q3 * e1;
-            Pm[8][d] = q0 * e3 - q1 * e2 + q2 * e1 - q3 * e0;
-        }
-        for (int r = 0; r < 12; ++r) {
-            double* Jr = J + (size_t)(12 * k + r) * nm;
-            for (int c = 0; c < nm; ++c) {
-                double acc = 0.0;
-                if (P.parent >= 0) { const double* Jp = J + (size_t)(12 * P.parent) * nm + c; for (int m = 0; m < 12; ++m) acc += Pm[r][m] * Jp[(size_t)m * nm]; }
-                const int lc = c - 2 * P.u_off;
-                if (lc >= 0 && lc < 2 * n) acc += Pm[r][12 + lc];
-                Jr[c] = acc;
-            }
-        }
-    }
-}
-// maximal_to_minimal_jacobian (src/gradients/state.jl:9-56) at z (advanced by one integrator step when `advance`):
-// one thread per (environment, joint); Jb[env][joint k][2n rows in layout order][24]: d/d(parent reduced state), d/d(child)
-template <class TIO>
-__global__ void max2min_jac_kernel(const NodeP<double>* nodes, int Nb, double dt, int B, const TIO* z, int advance, double* Jb) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-    const int env = tid / Nb, k = tid % Nb;
-    if (env >= B) return;
-    const NodeP<double>& P = nodes[k];
-    const TIO* ze = z + (size_t)env * 13 * Nb;
-    const int nt = P.nu_t, nr = P.nu_r, n = nt + nr;
-    PoseVel<double> b0 = load_body<double>(ze, k), a0 = P.parent >= 0 ? load_body<double>(ze, P.parent) : origin_body<double>();
-    if (advance) { advance_body(b0, dt); if (P.parent >= 0) advance_body(a0, dt); }
-    PoseVel<D24> a = seed_body<24>(a0, 0), b = seed_body<24>(b0, 12);
-    D24 ct[3], cr[3], vt[3], vr[3];
-    joint_max2min(ct, cr, vt, vr, P, dt, a, b);
-    double* o = Jb + ((size_t)env * Nb + k) * 12 * 24;
-    for (int i = 0; i < 3; ++i) for (int d = 0; d < 24; ++d) {
-        if (i < nt) { o[(size_t)i * 24 + d] = ct[i].d[d]; o[(size_t)(n + i) * 24 + d] = vt[i].d[d]; }
-        if (i < nr) { o[(size_t)(nt + i) * 24 + d] = cr[i].d[d]; o[(size_t)(n + nt + i) * 24 + d] = vr[i].d[d]; }
-    }
-}
-// T = dz * Jm  (12Nb x 2nu per environment); dz is column-major per environment: dz(r, c) = dz[c * nx + r]
-template <class TIO>
-__global__ void chain_mid_kernel(int nx, int nm, int B, const TIO* dz, const double* Jm, double* T) {
-    const int env = blockIdx.x;
-    const TIO* D = dz + (size_t)env * nx * nx; const double* J = Jm + (size_t)env * nx * nm; double* Te = T + (size_t)env * nx * nm;
-    for (int e = threadIdx.x; e < nx * nm; e += blockDim.x) {
-        const int r = e % nx, j = e / nx;                                       // consecutive threads -> consecutive rows (coalesced dz reads)
-        double acc = 0.0;
-        for (int c = 0; c < nx; ++c) acc += (double)D[(size_t)c * nx + r] * J[(size_t)c * nm + j];
-        Te[(size_t)r * nm + j] = acc;
-    }
-}
-// jx = M2m * T, ju = M2m * du with the block-sparse M2m (each joint's rows touch its parent's and its child's 12 columns);
-// outputs row-major per environment: jx[env][2nu][2nu], ju[env][2nu][nu]; du(r, c) = du[c * nx + r]
-template <class TIO>
-__global__ void chain_out_kernel(const NodeP<double>* nodes, int Nb, int nu, int B, const double* Jb, const double* T, const TIO* du, TIO* jx, TIO* ju) {
-    const int env = blockIdx.x, nx = 12 * Nb, nm = 2 * nu;
-    const double* Te = T + (size_t)env * nx * nm; const TIO* Du = du ? du + (size_t)env * nx * nu : nullptr;
-    for (int e = threadIdx.x; e < nm * (nm + nu); e += blockDim.x) {
-        const int i = e / (nm + nu), j = e % (nm + nu);
-        // joint owning minimal row i
-        int k = 0, lr = 0;
-        for (int b = 0; b < Nb; ++b) { const int o = 2 * nodes[b].u_off, nn = 2 * (nodes[b].nu_t + nodes[b].nu_r); if (i >= o && i < o + nn) { k = b; lr = i - o; } }
-        const double* Jr = Jb + (((size_t)env * Nb + k) * 12 + lr) * 24;
-        const int par = nodes[k].parent;
-        double acc = 0.0;
-        for (int m = 0; m < 12; ++m) {
-            if (j < nm) { if (par >= 0) acc += Jr[m] * Te[(size_t)(12 * par + m) * nm + j]; acc += Jr[12 + m] * Te[(size_t)(12 * k + m) * nm + j]; }
-            else if (Du) { const int c = j - nm; if (par >= 0) acc += Jr[m] * (double)Du[(size_t)c * nx + 12 * par + m]; acc += Jr[12 + m] * (double)Du[(size_t)c * nx + 12 * k + m]; }
-        }
-        if (j < nm) jx[((size_t)env * nm + i) * nm + j] = (TIO)acc; else if (ju) ju[((size_t)env * nm + i) * nu + (j - nm)] = (TIO)acc;
-    }
-}
-// get_next_state(mechanism) (src/mechanism/get.jl:126-134) of bodies whose stored velocities are their solution: one thread per (env, body)
-template <class TIO>
-__global__ void next_state_kernel(int Nb, double dt, int B, const TIO* z, TIO* zo) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= B * Nb) return;
-    PoseVel<double> p = load_body<double>(z + (size_t)(tid / Nb) * 13 * Nb, tid % Nb);
-    advance_body(p, dt);
-    TIO* o = zo + (size_t)tid * 13;
-    for (int i = 0; i < 3; ++i) { o[i] = (TIO)p.x[i]; o[3 + i] = (TIO)p.v[i]; o[10 + i] = (TIO)p.w[i]; }
-    for (int i = 0; i < 4; ++i) o[6 + i] = (TIO)p.q[i];
-}
-// dojo_step_impulses: external force + body impulses / dt
-template <class TIO> __global__ void fold_impulses_kernel(long long n, const TIO* fext, const TIO* jf, double inv_dt, TIO* out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (TIO)((fext ? (double)fext[i] : 0.0) + (double)jf[i] * inv_dt);
-}
 // dojo_set_dispatch_order: the permutation the NEXT step kernel of these workgroups hands its hardware workgroups out by -- a counting sort of
 // the launch's workgroups by the Newton iterations their environments took in this step, longest first (a solve that was long stays long for
 // a while: the same contacts are closing).  One workgroup; the order inside a bucket is whatever the atomics give (results do not depend on it:
@@ -405,7 +210,6 @@ __global__ void __launch_bounds__(1024) dispatch_order_kernel(const int* iters, 
     __syncthreads();
     for (int wg = t; wg < nwg; wg += 1024) order[atomicAdd(&cnt[bucket(wg)], 1)] = wg;
 }
-} // namespace ckern
 
 // what an allocation takes from the device: whole 4096-byte granules, at least 8 bytes
 size_t granules(size_t bytes) { return (std::max<size_t>(bytes, 8) + 4095) / 4096 * 4096; }
@@ -781,20 +585,53 @@ int launch_dispatch_order(DojoSim* s, const int* iters, const Span& sp, const Ge
         const size_t a_ = it_->first, b_ = a_ + ((size_t)it_->second + ge.E - 1) / ge.E;
         if (a_ < ge.wave0 + ge.grid && ge.wave0 < b_) it_ = s->dispatch_have.erase(it_); else ++it_;
     }
-    hipLaunchKernelGGL(ckern::dispatch_order_kernel, dim3(1), dim3(1024), 0, sp.stream, iters, sp.nenv, ge.E, (int)ge.grid, s->d_dispatch + ge.wave0);
+    hipLaunchKernelGGL(dispatch_order_kernel, dim3(1), dim3(1024), 0, sp.stream, iters, sp.nenv, ge.E, (int)ge.grid, s->d_dispatch + ge.wave0);
     HIPCHK(hipGetLastError());
     s->dispatch_have[ge.wave0] = sp.nenv;
     return DOJO_OK;
 }
-// record: the Storage rows of the environments of a launch
-template <class TIO>
-int launch_storage(const DojoSim* s, const StepIO& io, const Span& sp) {
-    const size_t Nb = s->M.Nb; const long long n = (long long)sp.nenv * Nb; const int T_ = 128;
-    hipLaunchKernelGGL((ckern::storage_kernel<TIO>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, sp.stream, (const dj::NodeP<double>*)s->d_nodes,
-                       (const dj::ContactP<double>*)s->d_contacts, (int)Nb, s->M.Nc, s->M.contact_model, (int)csg_per(s), s->M.dt, (int)sp.env0, sp.nenv,
-                       (const TIO*)io.z, (const TIO*)s->d_vel, (const TIO*)s->d_csg, (const TIO*)s->d_res, (const TIO*)s->fext, (TIO*)io.storage);
+// The kernels of dojo_coord_kernels.hpp, one launcher each: the grid, the casts and the launch check are here, once for both ABI types.
+// One thread per item, T_ threads per workgroup:
+template <class K, class... Args>
+int launch_items(K kernel, long long items, int T_, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((items + T_ - 1) / T_)), dim3(T_), 0, st, args...);
     HIPCHK(hipGetLastError());
     return DOJO_OK;
+}
+const dj::NodeP<double>* node_table(const DojoSim* s) { return (const dj::NodeP<double>*)s->d_nodes; }
+// record: the Storage rows of the environments of a launch, one thread per (environment, body)
+template <class TIO>
+int launch_storage(const DojoSim* s, const StepIO& io, const Span& sp) {
+    return launch_items(dj::ckern::storage_kernel<TIO>, (long long)sp.nenv * s->M.Nb, 128, sp.stream, node_table(s), (const dj::ContactP<double>*)s->d_contacts, s->M.Nb, s->M.Nc,
+                        s->M.contact_model, (int)csg_per(s), s->M.dt, (int)sp.env0, sp.nenv, (const TIO*)io.z, (const TIO*)s->d_vel, (const TIO*)s->d_csg, (const TIO*)s->d_res,
+                        (const TIO*)s->fext, (TIO*)io.storage);
+}
+// ... the others over the whole batch, device arrays in:
+template <class TIO> int launch_min2max(const DojoSim* s, const void* x, void* z, hipStream_t st) {      // one thread per environment
+    return launch_items(dj::ckern::min2max_kernel<TIO>, s->B, 64, st, node_table(s), (const int*)s->d_order, s->M.Nb, (int)s->M.nu, s->M.dt, s->B, (const TIO*)x, (TIO*)z);
+}
+template <class TIO> int launch_max2min(const DojoSim* s, const void* z, void* x, int ldx, hipStream_t st) {      // per (environment, joint); ldx: scalars per row of x
+    return launch_items(dj::ckern::max2min_kernel<TIO>, (long long)s->B * s->M.Nb, 256, st, node_table(s), s->M.Nb, (int)s->M.nu, s->M.dt, s->B, (const TIO*)z, (TIO*)x, ldx);
+}
+template <class TIO> int launch_contact_obs(const DojoSim* s, void* obs, int ldx, hipStream_t st) {      // per (environment, contact), behind the 2 nu minimal coordinates of a row
+    return launch_items(dj::ckern::contact_obs_kernel<TIO>, (long long)s->B * s->M.Nc, 256, st, s->M.Nc, s->B, (const TIO*)s->d_csg, (TIO*)obs, ldx, 2 * (int)s->M.nu);
+}
+template <class TIO> int launch_next_state(const DojoSim* s, const void* z, void* z_out, hipStream_t st) {      // per (environment, body)
+    return launch_items(dj::ckern::next_state_kernel<TIO>, (long long)s->B * s->M.Nb, 256, st, s->M.Nb, s->M.dt, s->B, (const TIO*)z, (TIO*)z_out);
+}
+template <class TIO> int launch_fold_impulses(const DojoSim* s, const void* jf, void* out, hipStream_t st) {      // per scalar of [B][6Nb]: the handle's external force + jf / dt
+    const long long n = (long long)s->B * 6 * s->M.Nb;
+    return launch_items(dj::ckern::fold_impulses_kernel<TIO>, n, 256, st, n, (const TIO*)s->fext, (const TIO*)jf, 1.0 / s->M.dt, (TIO*)out);
+}
+// the chain of get_minimal_gradients! over the handle's d_dz, d_du: the min -> max Jacobian at (x, z) into d_jm, the max -> min blocks at d_zn (advanced by a step with
+// `advance`) into d_jb, d_jt = dz d_jm, and jx, ju = blocks * (d_jt, du).  The two Jacobian kernels per environment / per (environment, joint), the products one workgroup per environment.
+template <class TIO> int launch_minimal_chain(const DojoSim* s, const void* x, const void* z, int advance, void* jx, void* ju, hipStream_t st) {
+    const int B = s->B, Nb = s->M.Nb, nu = (int)s->M.nu, T_ = 256;
+    double *jm = (double*)s->d_jm, *jt = (double*)s->d_jt, *jb = (double*)s->d_jb;
+    TRY(launch_items(dj::ckern::min2max_jac_kernel<TIO>, B, 64, st, node_table(s), (const int*)s->d_order, Nb, nu, s->M.dt, B, (const TIO*)x, (const TIO*)z, jm));
+    TRY(launch_items(dj::ckern::max2min_jac_kernel<TIO>, (long long)B * Nb, T_, st, node_table(s), Nb, s->M.dt, B, (const TIO*)s->d_zn, advance, jb));
+    TRY(launch_items(dj::ckern::chain_mid_kernel<TIO>, (long long)B * T_, T_, st, 12 * Nb, 2 * nu, B, (const TIO*)s->d_dz, (const double*)jm, jt));
+    return launch_items(dj::ckern::chain_out_kernel<TIO>, (long long)B * T_, T_, st, node_table(s), Nb, nu, B, (const double*)jb, (const double*)jt, (const TIO*)s->d_du, (TIO*)jx, (TIO*)ju);
 }
 
 // Launches the step (and IFT) kernels for the environments of `sp`; all pointers of `io` are the batch-level buffers.
@@ -836,7 +673,7 @@ int launch(DojoSim* s, const StepIO& io, const Span& sp, const Mode& m) {
 }
 
 int launch_any(DojoSim* s, const StepIO& io, const Span& sp, const Mode& m) {
-    return s->dtype == DOJO_DTYPE_F32 ? launch<float, double, double>(s, io, sp, m) : launch<double, double, double>(s, io, sp, m);
+    return by_dtype(s, [&](auto t) { return launch<decltype(t), double, double>(s, io, sp, m); });
 }
 Mode step_mode(const DojoSim* s, size_t NG, bool cap_lists = false, bool chained = false) { return Mode{PH_ALL, nullptr, cap_lists, chained, NG, s->sol_cur}; }
 Span whole_batch(const DojoSim* s, hipStream_t st) { return Span{0, s->B, st}; }
@@ -990,14 +827,11 @@ int launch_policy(const DojoSim* s, const DojoPolicy& p, const void* z, const vo
 }
 // dojo_observation_jacobian_dev: M [n][B][2nu][24] of the states (z_first; z_rest[0 .. n-2]), one launch over all (state, environment, joint) triples
 int launch_observation_jacobian(const DojoSim* s, const void* z_first, const void* z_rest, long long n, double* M, hipStream_t st) {
-    constexpr int T_ = dj::padjoint::JAC_THREADS;
-    const long long total = n * s->B * s->M.Nb;
-    const dim3 grid((unsigned)((total + T_ - 1) / T_));
-    const dj::NodeP<double>* nodes = (const dj::NodeP<double>*)s->d_nodes;
-    if (s->dtype == DOJO_DTYPE_F32) hipLaunchKernelGGL((dj::padjoint::observation_jacobian_kernel<float>), grid, dim3(T_), 0, st, nodes, s->M.Nb, (int)s->M.nu, s->M.dt, s->B, n, (const float*)z_first, (const float*)z_rest, M);
-    else hipLaunchKernelGGL((dj::padjoint::observation_jacobian_kernel<double>), grid, dim3(T_), 0, st, nodes, s->M.Nb, (int)s->M.nu, s->M.dt, s->B, n, (const double*)z_first, (const double*)z_rest, M);
-    HIPCHK(hipGetLastError());
-    return DOJO_OK;
+    return by_dtype(s, [&](auto t) {
+        using TIO = decltype(t);
+        return launch_items(dj::padjoint::observation_jacobian_kernel<TIO>, n * s->B * s->M.Nb, dj::padjoint::JAC_THREADS, st, node_table(s), s->M.Nb, (int)s->M.nu, s->M.dt, s->B, n,
+                            (const TIO*)z_first, (const TIO*)z_rest, M);
+    });
 }
 // what the two closed-loop sweeps are given alike (padjoint::Common), from the ABI records of either entry: a is a DojoPolicyAdjoint or a DojoMlpAdjoint, p its policy
 template <class TIO, class Rec, class Pol>
@@ -1063,10 +897,15 @@ struct Staging {
         }
         return DOJO_OK;
     }
-    // behind the device work of the call: the downloads, and the last state Z[H-1] into the handle's d_zn (dojo_get_state) as a rollout without Z leaves it there
-    int finish(DojoSim* s, const Buf& Z, int H) {
+    // behind the device work of the call: the downloads ...
+    int finish() {
         HIPCHK(hipDeviceSynchronize());
         for (const Buf& b : bufs) if (b.dst) HIPCHK(hipMemcpy(b.dst, b.p, b.bytes, hipMemcpyDeviceToHost));
+        return DOJO_OK;
+    }
+    // ... and, of a rollout, the last state Z[H-1] into the handle's d_zn (dojo_get_state) as a rollout without Z leaves it there
+    int finish(DojoSim* s, const Buf& Z, int H) {
+        TRY(finish());
         const size_t zb = (size_t)s->B * 13 * s->M.Nb * s->w;
         if (Z.p) HIPCHK(hipMemcpy(s->d_zn, (char*)Z.p + (size_t)(H - 1) * zb, zb, hipMemcpyDeviceToDevice));
         return DOJO_OK;
@@ -1079,6 +918,40 @@ private:
         return bufs.back();
     }
 };
+
+// The host-pointer step entries keep their arrays in buffers of the handle instead: those are state (dojo_gradients and dojo_contact_gradients read d_z, d_u and
+// d_dz later) and a step must not pay for allocations.  In front of the step: the state (n scalars per environment) into d_state and, for an entry with controls
+// (d_u given), the controls into the handle's d_u -- *d_u: where they are, null where the call has none.
+int upload_step(DojoSim* s, void* d_state, const void* state, size_t n, const void* u = nullptr, const void** d_u = nullptr) {
+    const size_t B = s->B, w = s->w, nu = s->M.nu;
+    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
+    HIPCHK(hipMemcpy(d_state, state, B * n * w, hipMemcpyHostToDevice));
+    if (!d_u) return DOJO_OK;
+    ENSURE(s->d_u, B * (nu + 1) * w);
+    *d_u = (u && nu) ? s->d_u : nullptr;
+    if (*d_u) HIPCHK(hipMemcpy(s->d_u, u, B * nu * w, hipMemcpyHostToDevice));
+    return DOJO_OK;
+}
+// Behind it: the next state (n scalars per environment, from d_next) and the handle's d_status / d_iters into the arrays that are wanted
+int download_step(DojoSim* s, void* next, const void* d_next, size_t n, int32_t* status, int32_t* iters) {
+    const size_t B = s->B;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(next, d_next, B * n * s->w, hipMemcpyDeviceToHost));
+    if (status) HIPCHK(hipMemcpy(status, s->d_status, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (iters) HIPCHK(hipMemcpy(iters, s->d_iters, B * sizeof(int), hipMemcpyDeviceToHost));
+    return DOJO_OK;
+}
+// The device keeps Jacobians column-major per environment (Julia-native), the host ABI is row-major: dst [B][rows][cols] on the host <- src [B][cols][rows] on the device
+int download_transposed(const DojoSim* s, void* dst, const void* src, size_t rows, size_t cols) {
+    const size_t B = s->B, w = s->w;
+    std::vector<char> tmp(B * rows * cols * w);
+    HIPCHK(hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; ++b)
+        for (size_t c = 0; c < cols; ++c)
+            for (size_t r = 0; r < rows; ++r)
+                std::memcpy((char*)dst + ((b * rows + r) * cols + c) * w, tmp.data() + ((b * cols + c) * rows + r) * w, w);
+    return DOJO_OK;
+}
 
 // dojo_rollout_data_adjoint_dev: the contact-data sweep (dojo_data_adjoint.hpp; one workgroup per environment, one launch) and, for the gradient shared by the
 // batch, the reduction over the environments (one workgroup per entry)
@@ -1128,7 +1001,7 @@ int launch_riccati_any(const DojoSim* s, int H, const DojoRiccati& r, hipStream_
 }
 
 int launch_policy_any(const DojoSim* s, const DojoPolicy& p, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
-    return s->dtype == DOJO_DTYPE_F32 ? launch_policy<float>(s, p, z, csg, uff, obs, u, sp) : launch_policy<double>(s, p, z, csg, uff, obs, u, sp);
+    return by_dtype(s, [&](auto t) { return launch_policy<decltype(t)>(s, p, z, csg, uff, obs, u, sp); });
 }
 
 // dojo_rollout_mlp_dev: the same controller with a tanh network in place of the mat-vec (dojo_mlp.hpp); act: [B][nh] of this step or null
@@ -1156,7 +1029,7 @@ struct Controller {
 int launch_controller(const DojoSim* s, const Controller& c, int k, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
     if (c.affine) return launch_policy_any(s, *c.affine, z, csg, uff, obs, u, sp);
     double* const act = (c.ACT && u) ? c.ACT + (size_t)k * s->B * c.shape.nh : nullptr;
-    return s->dtype == DOJO_DTYPE_F32 ? launch_mlp<float>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp) : launch_mlp<double>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp);
+    return by_dtype(s, [&](auto t) { return launch_mlp<decltype(t)>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp); });
 }
 
 // dojo_rollout_mlp_adjoint_dev: the sweep (one workgroup per environment, one launch) and, for a shared policy, the reduction over the batch
@@ -1319,7 +1192,7 @@ int dojo_allgather_dev(DojoHandle s, const void* send, void* recv, int64_t count
     if (!s || !send || !recv || count < 0) { g_err = "dojo_allgather_dev: bad argument"; return DOJO_ERR_INVALID; }
     if (!s->comm) { g_err = "dojo_allgather_dev: no communicator (dojo_comm_init)"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    int rcj = join_groups(s, (hipStream_t)stream); if (rcj != DOJO_OK) return rcj;
+    TRY(join_groups(s, (hipStream_t)stream));
     const int dt = as_int32 ? 2 /*ncclInt32*/ : (s->dtype == DOJO_DTYPE_F32 ? 7 /*ncclFloat32*/ : 8 /*ncclFloat64*/);
     int rc = rccl::all_gather(send, recv, (size_t)count, dt, s->comm, (hipStream_t)stream);
     if (rc != 0) { g_err = std::string("ncclAllGather: ") + rccl::why(rc); return DOJO_ERR_DEVICE; }
@@ -1405,20 +1278,12 @@ int dojo_step(DojoHandle s, const void* z, const void* u, void* z_next, int32_t*
     if (!s || !z || !z_next) { g_err = "dojo_step: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nx = 12 * s->M.Nb, nu = s->M.nu;
-    int rc;
+    const void* d_u = nullptr;
     ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
-    ENSURE(s->d_u, B * (nu + 1) * w);
-    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
     if (with_gradient) { ENSURE(s->d_dz, B * nx * nx * w); ENSURE(s->d_du, B * nx * (nu + 1) * w); }
-    HIPCHK(hipMemcpy(s->d_z, z, B * nz * w, hipMemcpyHostToDevice));
-    if (u && nu) HIPCHK(hipMemcpy(s->d_u, u, B * nu * w, hipMemcpyHostToDevice));
-    rc = dojo_step_dev(s, s->d_z, (u && nu) ? s->d_u : nullptr, s->d_zn, s->d_status, s->d_iters,
-                       with_gradient ? s->d_dz : nullptr, with_gradient ? s->d_du : nullptr, nullptr);
-    if (rc != DOJO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(z_next, s->d_zn, B * nz * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, s->d_status, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(hipMemcpy(iters, s->d_iters, B * sizeof(int), hipMemcpyDeviceToHost));
+    TRY(upload_step(s, s->d_z, z, nz, u, &d_u));
+    TRY(dojo_step_dev(s, s->d_z, d_u, s->d_zn, s->d_status, s->d_iters, with_gradient ? s->d_dz : nullptr, with_gradient ? s->d_du : nullptr, nullptr));
+    TRY(download_step(s, z_next, s->d_zn, nz, status, iters));
     s->have_grad = with_gradient != 0; s->have_u = (u && nu);
     return DOJO_OK;
 }
@@ -1433,27 +1298,19 @@ int dojo_step_impulses(DojoHandle s, const void* z, const void* jf, void* z_next
     if (!s || !z || !jf || !z_next) { g_err = "dojo_step_impulses: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nz = 13 * s->M.Nb, nf = 6 * s->M.Nb;
-    int rc;
     ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
     ENSURE(s->d_jf, 2 * B * nf * w);               // [raw impulses | folded forces]
-    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(s->d_z, z, B * nz * w, hipMemcpyHostToDevice));
+    TRY(upload_step(s, s->d_z, z, nz));
     HIPCHK(hipMemcpy(s->d_jf, jf, B * nf * w, hipMemcpyHostToDevice));
     void* folded = (char*)s->d_jf + B * nf * w;
-    const long long n = (long long)(B * nf); const int T_ = 256;
-    if (s->dtype == DOJO_DTYPE_F32) hipLaunchKernelGGL((ckern::fold_impulses_kernel<float>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, nullptr, n, (const float*)s->fext, (const float*)s->d_jf, 1.0 / s->M.dt, (float*)folded);
-    else hipLaunchKernelGGL((ckern::fold_impulses_kernel<double>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, nullptr, n, (const double*)s->fext, (const double*)s->d_jf, 1.0 / s->M.dt, (double*)folded);
-    HIPCHK(hipGetLastError());
+    TRY(by_dtype(s, [&](auto t) { return launch_fold_impulses<decltype(t)>(s, s->d_jf, folded, nullptr); }));
     const void* user_fext = s->fext;
     s->fext = folded;
-    rc = dojo_step_dev(s, s->d_z, nullptr, s->d_zn, s->d_status, s->d_iters, nullptr, nullptr, nullptr);
+    const int rc = dojo_step_dev(s, s->d_z, nullptr, s->d_zn, s->d_status, s->d_iters, nullptr, nullptr, nullptr);
     s->fext = user_fext;
-    if (rc != DOJO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(z_next, s->d_zn, B * nz * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, s->d_status, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(hipMemcpy(iters, s->d_iters, B * sizeof(int), hipMemcpyDeviceToHost));
+    TRY(rc);
+    TRY(download_step(s, z_next, s->d_zn, nz, status, iters));
     s->have_grad = false; s->have_u = false;
     return DOJO_OK;
 }
@@ -1511,20 +1368,9 @@ int dojo_gradients(DojoHandle s, void* dz, void* du) {
     Enter enter_(s);
     if (!s || !s->have_grad) { g_err = "dojo_gradients: the last dojo_step was not run with with_gradient=1"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    size_t B = s->B, w = s->w, nx = 12 * s->M.Nb, nu = s->M.nu;
-    // device layout is column-major per environment (Julia-native); the host ABI is row-major [B,nx,nx] / [B,nx,nu]
-    std::vector<char> tmp(B * nx * std::max(nx, nu) * w);
-    auto transpose_out = [&](void* dst, const void* src, size_t ncols) -> int {
-        HIPCHK(hipMemcpy(tmp.data(), src, B * nx * ncols * w, hipMemcpyDeviceToHost));
-        for (size_t b = 0; b < B; ++b)
-            for (size_t c = 0; c < ncols; ++c)
-                for (size_t r = 0; r < nx; ++r)
-                    std::memcpy((char*)dst + ((b * nx + r) * ncols + c) * w, tmp.data() + ((b * ncols + c) * nx + r) * w, w);
-        return DOJO_OK;
-    };
-    int rc;
-    if (dz && (rc = transpose_out(dz, s->d_dz, nx))) return rc;
-    if (du && nu && (rc = transpose_out(du, s->d_du, nu))) return rc;
+    const size_t nx = 12 * s->M.Nb, nu = s->M.nu;      // host layout: [B, nx, nx] / [B, nx, nu] row-major
+    if (dz) TRY(download_transposed(s, dz, s->d_dz, nx, nx));
+    if (du && nu) TRY(download_transposed(s, du, s->d_du, nx, nu));
     return DOJO_OK;
 }
 
@@ -1659,7 +1505,7 @@ static int refuse_policy(DojoHandle s, const void* z0, const DojoPolicy* p, int3
     if (s->M.nu == 0) { g_err = w_ + "the mechanism has no inputs"; return DOJO_ERR_INVALID; }
     if (p->na < 1 || p->act_off < 0 || (long long)p->act_off + p->na > (long long)s->M.nu) { g_err = w_ + "the policy must drive inputs act_off .. act_off + na - 1 inside 0 .. nu - 1, na >= 1"; return DOJO_ERR_INVALID; }
     if (p->contact_init && !s->have_solution) { g_err = w_ + "contact_init = 1 needs a step on this handle"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = w_ + "the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, who));
     if (p->contact_forces && s->M.contact_model == 2) { g_err = w_ + "contact forces are not available for LinearContact mechanisms"; return DOJO_ERR_UNSUPPORTED; }
     if (dj::policy::lds_bytes(2 * s->M.nu + s->M.Nc) > 65536) { g_err = w_ + "supports at most 2048 observations per environment (they are kept in LDS)"; return DOJO_ERR_UNSUPPORTED; }
     return DOJO_OK;
@@ -1705,8 +1551,7 @@ int dojo_rollout_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const void
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the Jacobians)
     if (!gU && !gz) return DOJO_OK;
-    return s->dtype == DOJO_DTYPE_F32 ? launch_adjoint<float>(s, H, DZ, DU, G, cot_space, Z, status, gU, gz, st)
-                                      : launch_adjoint<double>(s, H, DZ, DU, G, cot_space, Z, status, gU, gz, st);
+    return by_dtype(s, [&](auto t) { return launch_adjoint<decltype(t)>(s, H, DZ, DU, G, cot_space, Z, status, gU, gz, st); });
 }
 
 // host pointers: upload, record on the device, reverse sweep, download -- the Jacobians never cross PCIe
@@ -1763,8 +1608,7 @@ int dojo_rollout_data_adjoint_dev(DojoHandle s, int32_t H, const void* DZ, const
     if (!gtheta_env && !gtheta && !gz) return DOJO_OK;
     if (gtheta) TRY(ensure_dacc(s));
     double* acc = gtheta ? s->d_dacc : nullptr;
-    return s->dtype == DOJO_DTYPE_F32 ? launch_data_adjoint<float>(s, H, DZ, DC, G, cot_space, Z, status, gtheta_env, acc, gtheta, gz, st)
-                                      : launch_data_adjoint<double>(s, H, DZ, DC, G, cot_space, Z, status, gtheta_env, acc, gtheta, gz, st);
+    return by_dtype(s, [&](auto t) { return launch_data_adjoint<decltype(t)>(s, H, DZ, DC, G, cot_space, Z, status, gtheta_env, acc, gtheta, gz, st); });
 }
 
 // host pointers: upload, record on the device (with the contact-data columns), the contact-data sweep -- and the open-loop sweep over the same record when gU is
@@ -1820,8 +1664,7 @@ int dojo_rollout_tangent_dev(DojoHandle s, int32_t H, int32_t T, const void* DZ,
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: they may be writing the Jacobians)
-    return s->dtype == DOJO_DTYPE_F32 ? launch_tangent<float>(s, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, st)
-                                      : launch_tangent<double>(s, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, st);
+    return by_dtype(s, [&](auto t) { return launch_tangent<decltype(t)>(s, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, st); });
 }
 
 // host pointers: upload, record on the device (DU only for dU, DC only for dtheta), forward sweep, download -- the Jacobians never cross PCIe
@@ -1866,7 +1709,7 @@ static int refuse_riccati(DojoHandle s, int32_t H, const DojoRiccati* r, const c
     }
     if (s->M.nu == 0) { g_err = w_ + "the mechanism has no inputs"; return DOJO_ERR_INVALID; }
     if (r->na < 1 || r->act_off < 0 || (long long)r->act_off + r->na > (long long)s->M.nu) { g_err = w_ + "the policy must drive inputs act_off .. act_off + na - 1 inside 0 .. nu - 1, na >= 1"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = w_ + "the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, who));
     const int n = 2 * (int)s->M.nu, m = r->na;
     const size_t lds = dj::riccati::lds_bytes(n, m);
     if (lds > 65536 || !dj::riccati::accumulators(n, m) || m > dj::riccati::MAX_M) {
@@ -1882,7 +1725,7 @@ int dojo_riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, void* stream
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: the last dojo_minimal_gradients_dev may be writing the record)
-    return s->dtype == DOJO_DTYPE_F32 ? launch_riccati_any<float>(s, H, *r, st) : launch_riccati_any<double>(s, H, *r, st);
+    return by_dtype(s, [&](auto t) { return launch_riccati_any<decltype(t)>(s, H, *r, st); });
 }
 
 // host pointers: upload, one launch, download
@@ -1902,7 +1745,7 @@ int dojo_riccati(DojoHandle s, int32_t H, const DojoRiccati* r) {
     d.A = dA.p; d.Bm = dB.p; d.status = (const int32_t*)dS.p; d.lx = dlx.p; d.lu = dlu.p; d.lxx = dlxx.p; d.luu = dluu.p; d.lux = dlux.p; d.mu = dmu.p;
     d.K = dK.p; d.kff = dk.p; d.fail = (int32_t*)dF.p; d.dV = ddV.p; d.Vx = dVx.p; d.Vxx = dVxx.p;
     TRY(dojo_riccati_dev(s, H, &d, nullptr));
-    return st.finish(s, Staging::Buf{0, nullptr, nullptr, nullptr}, H);      // (no state: the handle's own is left alone)
+    return st.finish();      // (no state: the handle's own is left alone)
 }
 
 // ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----
@@ -1910,7 +1753,7 @@ int dojo_observation_jacobian_dev(DojoHandle s, const void* z, int32_t n, double
     Enter enter_(s);
     if (!s || !z || !M || n < 1) { g_err = "dojo_observation_jacobian_dev: bad argument (handle, z and M are required, n >= 1)"; return DOJO_ERR_INVALID; }
     if (s->M.nu == 0) { g_err = "dojo_observation_jacobian_dev: the mechanism has no inputs"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = "dojo_observation_jacobian_dev: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal: not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, "dojo_observation_jacobian_dev", ""));
     HIPCHK(hipSetDevice(s->device));
     return launch_observation_jacobian(s, z, (const char*)z + (size_t)s->B * 13 * s->M.Nb * s->w, n, M, (hipStream_t)stream);
 }
@@ -1919,16 +1762,14 @@ int dojo_observation_jacobian(DojoHandle s, const void* z, double* M) {
     Enter enter_(s);
     if (!s || !z || !M) { g_err = "dojo_observation_jacobian: bad argument (handle, z and M are required)"; return DOJO_ERR_INVALID; }
     if (s->M.nu == 0) { g_err = "dojo_observation_jacobian: the mechanism has no inputs"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = "dojo_observation_jacobian: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal: not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, "dojo_observation_jacobian", ""));
     HIPCHK(hipSetDevice(s->device));
     const size_t zb = (size_t)s->B * 13 * s->M.Nb * s->w, mb = (size_t)s->B * 2 * s->M.nu * 24 * sizeof(double);
-    DevBuf dz, dM;
-    HIPCHK(dz.alloc(zb)); HIPCHK(dM.alloc(mb));
-    HIPCHK(hipMemcpy(dz.p, z, zb, hipMemcpyHostToDevice));
+    Staging st;
+    const auto &dz = st.input(zb, z), &dM = st.output(mb, M);
+    TRY(st.allocate());
     TRY(launch_observation_jacobian(s, dz.p, nullptr, 1, (double*)dM.p, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(M, dM.p, mb, hipMemcpyDeviceToHost));
-    return DOJO_OK;
+    return st.finish();
 }
 
 int dojo_rollout_policy_record_dev(DojoHandle s, const void* z0, const DojoPolicy* policy, int32_t H, void* Z, void* OBS, void* U_out, int32_t* status,
@@ -1982,7 +1823,7 @@ int dojo_rollout_policy_adjoint_dev(DojoHandle s, const DojoPolicy* policy, int3
     if (!M) TRY(observation_jacobians(s, H, a.z0, a.Z, a.G_obs != nullptr, st, &M));
     double* acc = nullptr;
     if (!p.per_env) { TRY(ensure_pacc(s, (size_t)p.na)); acc = s->d_pacc; }
-    return s->dtype == DOJO_DTYPE_F32 ? launch_policy_adjoint<float>(s, p, H, a, M, acc, st) : launch_policy_adjoint<double>(s, p, H, a, M, acc, st);
+    return by_dtype(s, [&](auto t) { return launch_policy_adjoint<decltype(t)>(s, p, H, a, M, acc, st); });
 }
 
 // host pointers (the members of *policy too): upload, record on the device, sweep, download -- neither the Jacobians nor M cross PCIe
@@ -2121,7 +1962,7 @@ int dojo_rollout_mlp_adjoint_dev(DojoHandle s, const DojoMlpPolicy* policy, int3
     const double* M = a.M;
     if (!M) TRY(observation_jacobians(s, H, a.z0, a.Z, a.G_obs != nullptr, st, &M));
     TRY(ensure_macc(s, (size_t)sh.P));
-    return s->dtype == DOJO_DTYPE_F32 ? launch_mlp_adjoint<float>(s, p, sh, H, a, M, s->d_macc, st) : launch_mlp_adjoint<double>(s, p, sh, H, a, M, s->d_macc, st);
+    return by_dtype(s, [&](auto t) { return launch_mlp_adjoint<decltype(t)>(s, p, sh, H, a, M, s->d_macc, st); });
 }
 
 // host pointers (the members of *policy too): upload, record on the device, sweep, download -- the Jacobians, M and ACT do not cross PCIe
@@ -2215,19 +2056,14 @@ int dojo_contact_gradients(DojoHandle s, void* dc) {
     if (!s || !dc) { g_err = "dojo_contact_gradients: bad argument"; return DOJO_ERR_INVALID; }
     if (!s->have_grad || !s->d_z) { g_err = "dojo_contact_gradients: call dojo_step(..., with_gradient = 1) first"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    size_t B = s->B, w = s->w, nx = 12 * s->M.Nb, ncc = 5 * (size_t)s->M.Nc;
+    const size_t nx = 12 * s->M.Nb, ncc = 5 * (size_t)s->M.Nc;
     if (ncc == 0) return DOJO_OK;
-    DevBuf d_dc;
-    HIPCHK(d_dc.alloc(B * nx * ncc * w));
-    int rc = dojo_contact_gradients_dev(s, s->d_z, s->have_u ? s->d_u : nullptr, d_dc.p, nullptr);
-    if (rc != DOJO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    // device layout: [B][5Nc columns][12Nb rows] -> host layout [B, 12Nb, 5Nc] row-major
-    std::vector<char> tmp(B * nx * ncc * w);
-    HIPCHK(hipMemcpy(tmp.data(), d_dc.p, tmp.size(), hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < B; ++b) for (size_t c = 0; c < ncc; ++c) for (size_t r = 0; r < nx; ++r)
-        std::memcpy((char*)dc + ((b * nx + r) * ncc + c) * w, tmp.data() + ((b * ncc + c) * nx + r) * w, w);
-    return DOJO_OK;
+    Staging st;
+    const auto& d_dc = st.kept((size_t)s->B * nx * ncc * s->w);
+    TRY(st.allocate());
+    TRY(dojo_contact_gradients_dev(s, s->d_z, s->have_u ? s->d_u : nullptr, d_dc.p, nullptr));
+    TRY(st.finish());
+    return download_transposed(s, dc, d_dc.p, nx, ncc);      // device layout [B][5Nc columns][12Nb rows] -> host layout [B, 12Nb, 5Nc]
 }
 
 // set_data!(mechanism.contacts, theta) (examples/system_identification/utilities.jl:52) on a live handle: theta [Nc][5] =
@@ -2275,26 +2111,18 @@ int dojo_get_contact_data(DojoHandle s, double* theta) {
 int dojo_minimal_to_maximal_dev(DojoHandle s, const void* x, void* z, void* stream) {
     Enter enter_(s);
     if (!s || !x || !z) { g_err = "dojo_minimal_to_maximal_dev: bad argument"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = "dojo_minimal_to_maximal_dev: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, "dojo_minimal_to_maximal_dev"));
     HIPCHK(hipSetDevice(s->device));
-    { int rcj = join_groups(s, (hipStream_t)stream); if (rcj != DOJO_OK) return rcj; }   // (asynchronous steps still in flight may write / read these buffers)
-    const int B = s->B, T_ = 64;
-    if (s->dtype == DOJO_DTYPE_F32) hipLaunchKernelGGL((ckern::min2max_kernel<float>), dim3((B + T_ - 1) / T_), dim3(T_), 0, (hipStream_t)stream, (const dj::NodeP<double>*)s->d_nodes, s->d_order, s->M.Nb, s->M.nu, s->M.dt, B, (const float*)x, (float*)z);
-    else hipLaunchKernelGGL((ckern::min2max_kernel<double>), dim3((B + T_ - 1) / T_), dim3(T_), 0, (hipStream_t)stream, (const dj::NodeP<double>*)s->d_nodes, s->d_order, s->M.Nb, s->M.nu, s->M.dt, B, (const double*)x, (double*)z);
-    HIPCHK(hipGetLastError());
-    return DOJO_OK;
+    TRY(join_groups(s, (hipStream_t)stream));      // (asynchronous steps still in flight may write / read these buffers)
+    return by_dtype(s, [&](auto t) { return launch_min2max<decltype(t)>(s, x, z, (hipStream_t)stream); });
 }
 int dojo_maximal_to_minimal_dev(DojoHandle s, const void* z, void* x, void* stream) {
     Enter enter_(s);
     if (!s || !x || !z) { g_err = "dojo_maximal_to_minimal_dev: bad argument"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = "dojo_maximal_to_minimal_dev: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, "dojo_maximal_to_minimal_dev"));
     HIPCHK(hipSetDevice(s->device));
-    { int rcj = join_groups(s, (hipStream_t)stream); if (rcj != DOJO_OK) return rcj; }   // (asynchronous steps still in flight may write / read these buffers)
-    const long long n = (long long)s->B * s->M.Nb; const int T_ = 256;
-    if (s->dtype == DOJO_DTYPE_F32) hipLaunchKernelGGL((ckern::max2min_kernel<float>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, (const dj::NodeP<double>*)s->d_nodes, s->M.Nb, s->M.nu, s->M.dt, s->B, (const float*)z, (float*)x, 2 * s->M.nu);
-    else hipLaunchKernelGGL((ckern::max2min_kernel<double>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, (const dj::NodeP<double>*)s->d_nodes, s->M.Nb, s->M.nu, s->M.dt, s->B, (const double*)z, (double*)x, 2 * s->M.nu);
-    HIPCHK(hipGetLastError());
-    return DOJO_OK;
+    TRY(join_groups(s, (hipStream_t)stream));      // (asynchronous steps still in flight may write / read these buffers)
+    return by_dtype(s, [&](auto t) { return launch_max2min<decltype(t)>(s, z, x, 2 * (int)s->M.nu, (hipStream_t)stream); });
 }
 // get_state(environment) of DojoEnvironments: the minimal state of z (environments.jl:100-102, quadruped_sampling.jl:67-72)
 // and, with contact_forces != 0, the clamped normal impulses of the last step behind it (ant_ars.jl:72-80).
@@ -2302,54 +2130,46 @@ int dojo_maximal_to_minimal_dev(DojoHandle s, const void* z, void* x, void* stre
 int dojo_observe_dev(DojoHandle s, const void* z, void* obs, int32_t contact_forces, void* stream) {
     Enter enter_(s);
     if (!s || !obs) { g_err = "dojo_observe_dev: bad argument"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = "dojo_observe_dev: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, "dojo_observe_dev"));
     if (!z) z = s->d_zn;                   // the state the last host-buffer / minimal-coordinate step left on the handle
     if (!z) { g_err = "dojo_observe_dev: z is NULL and the handle holds no state yet"; return DOJO_ERR_INVALID; }
     if (contact_forces && !s->have_solution) { g_err = "dojo_observe_dev: contact forces need a step on this handle"; return DOJO_ERR_INVALID; }
     if (contact_forces && s->M.contact_model == 2) { g_err = "dojo_observe: contact forces are not available for LinearContact mechanisms"; return DOJO_ERR_UNSUPPORTED; }
     HIPCHK(hipSetDevice(s->device));
-    { int rcj = join_groups(s, (hipStream_t)stream); if (rcj != DOJO_OK) return rcj; }
-    const int Nc = contact_forces ? s->M.Nc : 0, ld = 2 * s->M.nu + Nc;
-    const long long n = (long long)s->B * s->M.Nb, nc = (long long)s->B * Nc; const int T_ = 256;
-    if (s->dtype == DOJO_DTYPE_F32) {
-        hipLaunchKernelGGL((ckern::max2min_kernel<float>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, (const dj::NodeP<double>*)s->d_nodes, s->M.Nb, s->M.nu, s->M.dt, s->B, (const float*)z, (float*)obs, ld);
-        if (Nc) hipLaunchKernelGGL((ckern::contact_obs_kernel<float>), dim3((unsigned)((nc + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, Nc, s->B, (const float*)s->d_csg, (float*)obs, ld, 2 * s->M.nu);
-    } else {
-        hipLaunchKernelGGL((ckern::max2min_kernel<double>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, (const dj::NodeP<double>*)s->d_nodes, s->M.Nb, s->M.nu, s->M.dt, s->B, (const double*)z, (double*)obs, ld);
-        if (Nc) hipLaunchKernelGGL((ckern::contact_obs_kernel<double>), dim3((unsigned)((nc + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, Nc, s->B, (const double*)s->d_csg, (double*)obs, ld, 2 * s->M.nu);
-    }
-    HIPCHK(hipGetLastError());
-    return DOJO_OK;
+    TRY(join_groups(s, (hipStream_t)stream));
+    const int Nc = contact_forces ? s->M.Nc : 0, ld = 2 * (int)s->M.nu + Nc;
+    return by_dtype(s, [&](auto t) {
+        using TIO = decltype(t);
+        TRY(launch_max2min<TIO>(s, z, obs, ld, (hipStream_t)stream));
+        return Nc ? launch_contact_obs<TIO>(s, obs, ld, (hipStream_t)stream) : DOJO_OK;
+    });
 }
 int dojo_observe(DojoHandle s, void* obs, int32_t contact_forces) {
     Enter enter_(s);
     if (!s || !obs || !s->d_zn || !s->have_solution) { g_err = "dojo_observe: no step has been taken on this handle"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     const size_t ld = 2 * s->M.nu + (contact_forces ? s->M.Nc : 0), bytes = (size_t)s->B * ld * s->w;
-    DevBuf d;
-    HIPCHK(d.alloc(bytes));
+    Staging st;
+    const auto& d = st.output(bytes, obs);
+    TRY(st.allocate());
     HIPCHK(hipDeviceSynchronize());                          // (not the cached stream of the last step: the caller may have destroyed it)
-    int rc = dojo_observe_dev(s, s->d_zn, d.p, contact_forces, nullptr);
-    if (rc != DOJO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(obs, d.p, bytes, hipMemcpyDeviceToHost));
-    return DOJO_OK;
+    TRY(dojo_observe_dev(s, s->d_zn, d.p, contact_forces, nullptr));
+    return st.finish();
 }
 // step_minimal_coordinates!  src/simulation/step.jl:42-60: x -> z -> step! -> z' -> x'
 int dojo_step_minimal_dev(DojoHandle s, const void* x, const void* u, void* x_next, int32_t* status, int32_t* iters, void* stream) {
     Enter enter_(s);
     if (!s || !x || !x_next) { g_err = "dojo_step_minimal_dev: bad argument"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = "dojo_step_minimal_dev: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, "dojo_step_minimal_dev"));
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w, nz = 13 * s->M.Nb;
-    int rc;
     ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
     // (asynchronous handle: environment groups of the previous call may still read d_z / write d_zn, and the kernels that follow
     //  the step on `stream` read what its groups write -- both sides of the step are joined into the caller's stream here)
-    if ((rc = join_groups(s, (hipStream_t)stream))) return rc;
-    if ((rc = dojo_minimal_to_maximal_dev(s, x, s->d_z, stream))) return rc;
-    if ((rc = dojo_step_dev(s, s->d_z, u, s->d_zn, status, iters, nullptr, nullptr, stream))) return rc;
-    if ((rc = join_groups(s, (hipStream_t)stream))) return rc;
+    TRY(join_groups(s, (hipStream_t)stream));
+    TRY(dojo_minimal_to_maximal_dev(s, x, s->d_z, stream));
+    TRY(dojo_step_dev(s, s->d_z, u, s->d_zn, status, iters, nullptr, nullptr, stream));
+    TRY(join_groups(s, (hipStream_t)stream));
     s->have_grad = false;
     return dojo_maximal_to_minimal_dev(s, s->d_zn, x_next, stream);
 }
@@ -2363,77 +2183,50 @@ int dojo_minimal_gradients_dev(DojoHandle s, const void* x, const void* u, void*
                                void* jx, void* ju, void* stream) {
     Enter enter_(s);
     if (!s || !x || !x_next || !jx) { g_err = "dojo_minimal_gradients_dev: bad argument"; return DOJO_ERR_INVALID; }
-    if (s->M.has_loop) { g_err = "dojo_minimal_gradients_dev: the minimal coordinates of a mechanism with a kinematic loop are not those of a tree traversal (the reference sets them with exclude_ids): not supported"; return DOJO_ERR_UNSUPPORTED; }
+    TRY(refuse_minimal(s, "dojo_minimal_gradients_dev"));
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, Nb = s->M.Nb, nz = 13 * Nb, nx = 12 * Nb, nu = s->M.nu, nm = 2 * nu;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
     ENSURE(s->d_z, B * nz * w); ENSURE(s->d_zn, B * nz * w);
     ENSURE(s->d_dz, B * nx * nx * w); ENSURE(s->d_du, B * nx * (nu + 1) * w);
     ENSURE(s->d_jm, B * nx * (nm + 1) * sizeof(double)); ENSURE(s->d_jt, B * nx * (nm + 1) * sizeof(double));
     ENSURE(s->d_jb, B * Nb * 12 * 24 * sizeof(double));
-    if ((rc = join_groups(s, st))) return rc;              // (asynchronous handle: see dojo_step_minimal_dev)
-    if ((rc = dojo_minimal_to_maximal_dev(s, x, s->d_z, stream))) return rc;
-    if ((rc = dojo_step_dev(s, s->d_z, u, s->d_zn, status, iters, s->d_dz, s->d_du, stream))) return rc;
-    if ((rc = join_groups(s, st))) return rc;
+    TRY(join_groups(s, st));              // (asynchronous handle: see dojo_step_minimal_dev)
+    TRY(dojo_minimal_to_maximal_dev(s, x, s->d_z, stream));
+    TRY(dojo_step_dev(s, s->d_z, u, s->d_zn, status, iters, s->d_dz, s->d_du, stream));
+    TRY(join_groups(s, st));
     s->have_grad = false;          // the hand-off belongs to (d_z, the CALLER's u): the host variant below re-arms the flag with its own copy of u
-    if ((rc = dojo_maximal_to_minimal_dev(s, s->d_zn, x_next, stream))) return rc;
+    TRY(dojo_maximal_to_minimal_dev(s, s->d_zn, x_next, stream));
     const bool literal = s->grad_mode == DOJO_GRAD_REFERENCE;
     const void* xj = literal ? (const void*)x_next : x;                // where the min -> max Jacobian is evaluated ...
     const void* zj = literal ? (const void*)s->d_zn : (const void*)s->d_z;   // ... and the maximal state that belongs to it
-    const int T1 = 64, T2 = 256;
-    const dj::NodeP<double>* nodes = (const dj::NodeP<double>*)s->d_nodes;
-    if (s->dtype == DOJO_DTYPE_F32) {
-        hipLaunchKernelGGL((ckern::min2max_jac_kernel<float>), dim3((B + T1 - 1) / T1), dim3(T1), 0, st, nodes, s->d_order, (int)Nb, (int)nu, s->M.dt, (int)B, (const float*)xj, (const float*)zj, (double*)s->d_jm);
-        hipLaunchKernelGGL((ckern::max2min_jac_kernel<float>), dim3((unsigned)((B * Nb + T2 - 1) / T2)), dim3(T2), 0, st, nodes, (int)Nb, s->M.dt, (int)B, (const float*)s->d_zn, literal ? 1 : 0, (double*)s->d_jb);
-        hipLaunchKernelGGL((ckern::chain_mid_kernel<float>), dim3((unsigned)B), dim3(T2), 0, st, (int)nx, (int)nm, (int)B, (const float*)s->d_dz, (const double*)s->d_jm, (double*)s->d_jt);
-        hipLaunchKernelGGL((ckern::chain_out_kernel<float>), dim3((unsigned)B), dim3(T2), 0, st, nodes, (int)Nb, (int)nu, (int)B, (const double*)s->d_jb, (const double*)s->d_jt, (const float*)s->d_du, (float*)jx, (float*)ju);
-    } else {
-        hipLaunchKernelGGL((ckern::min2max_jac_kernel<double>), dim3((B + T1 - 1) / T1), dim3(T1), 0, st, nodes, s->d_order, (int)Nb, (int)nu, s->M.dt, (int)B, (const double*)xj, (const double*)zj, (double*)s->d_jm);
-        hipLaunchKernelGGL((ckern::max2min_jac_kernel<double>), dim3((unsigned)((B * Nb + T2 - 1) / T2)), dim3(T2), 0, st, nodes, (int)Nb, s->M.dt, (int)B, (const double*)s->d_zn, literal ? 1 : 0, (double*)s->d_jb);
-        hipLaunchKernelGGL((ckern::chain_mid_kernel<double>), dim3((unsigned)B), dim3(T2), 0, st, (int)nx, (int)nm, (int)B, (const double*)s->d_dz, (const double*)s->d_jm, (double*)s->d_jt);
-        hipLaunchKernelGGL((ckern::chain_out_kernel<double>), dim3((unsigned)B), dim3(T2), 0, st, nodes, (int)Nb, (int)nu, (int)B, (const double*)s->d_jb, (const double*)s->d_jt, (const double*)s->d_du, (double*)jx, (double*)ju);
-    }
-    HIPCHK(hipGetLastError());
-    return DOJO_OK;
+    return by_dtype(s, [&](auto t) { return launch_minimal_chain<decltype(t)>(s, xj, zj, literal ? 1 : 0, jx, ju, st); });
 }
 int dojo_minimal_gradients(DojoHandle s, const void* x, const void* u, void* x_next, int32_t* status, int32_t* iters, void* jx, void* ju) {
     Enter enter_(s);
     if (!s || !x || !x_next || !jx) { g_err = "dojo_minimal_gradients: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    size_t B = s->B, w = s->w, nu = s->M.nu, nm = 2 * nu;
-    int rc;
+    const size_t B = s->B, w = s->w, nu = s->M.nu, nm = 2 * nu;
+    const void* d_u = nullptr;
     ENSURE(s->d_x, B * (nm + 1) * w); ENSURE(s->d_xn, B * (nm + 1) * w);
-    ENSURE(s->d_u, B * (nu + 1) * w);
-    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
-    DevBuf bjx, bju;
-    HIPCHK(bjx.alloc(B * nm * nm * w)); HIPCHK(bju.alloc(B * nm * (nu + 1) * w));
-    void *d_jx = bjx.p, *d_ju = bju.p;
-    HIPCHK(hipMemcpy(s->d_x, x, B * nm * w, hipMemcpyHostToDevice));
-    if (u && nu) HIPCHK(hipMemcpy(s->d_u, u, B * nu * w, hipMemcpyHostToDevice));
-    rc = dojo_minimal_gradients_dev(s, s->d_x, (u && nu) ? s->d_u : nullptr, s->d_xn, s->d_status, s->d_iters, d_jx, d_ju, nullptr);
-    if (rc == DOJO_OK) { s->have_grad = true; s->have_u = (u && nu); }   // d_z, d_u, d_dz, d_du and the hand-off all belong to this step
-    if (rc == DOJO_OK) {
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(x_next, s->d_xn, B * nm * w, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(jx, d_jx, B * nm * nm * w, hipMemcpyDeviceToHost));
-        if (ju && nu) HIPCHK(hipMemcpy(ju, d_ju, B * nm * nu * w, hipMemcpyDeviceToHost));
-        if (status) HIPCHK(hipMemcpy(status, s->d_status, B * sizeof(int), hipMemcpyDeviceToHost));
-        if (iters) HIPCHK(hipMemcpy(iters, s->d_iters, B * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    return rc;
+    Staging st;
+    const auto &d_jx = st.output(B * nm * nm * w, jx), &d_ju = st.kept(B * nm * nu * w, nu ? ju : nullptr);
+    TRY(st.allocate());
+    TRY(upload_step(s, s->d_x, x, nm, u, &d_u));
+    TRY(dojo_minimal_gradients_dev(s, s->d_x, d_u, s->d_xn, s->d_status, s->d_iters, d_jx.p, d_ju.p, nullptr));
+    s->have_grad = true; s->have_u = (u && nu);   // d_z, d_u, d_dz, d_du and the hand-off all belong to this step
+    TRY(download_step(s, x_next, s->d_xn, nm, status, iters));
+    return st.finish();
 }
 
 static int coords_host(DojoHandle s, const void* in, void* out, size_t n_in, size_t n_out, bool to_max) {
     HIPCHK(hipSetDevice(s->device));
     size_t B = s->B, w = s->w;
-    int rc;
     ENSURE(s->d_x, B * (2 * s->M.nu + 1) * w);
     ENSURE(s->d_cz, B * 13 * s->M.Nb * w);       // not d_z: that is the state dojo_contact_gradients re-linearizes at
     void* din = to_max ? s->d_x : s->d_cz; void* dout = to_max ? s->d_cz : s->d_x;
     HIPCHK(hipMemcpy(din, in, B * n_in * w, hipMemcpyHostToDevice));
-    rc = to_max ? dojo_minimal_to_maximal_dev(s, din, dout, nullptr) : dojo_maximal_to_minimal_dev(s, din, dout, nullptr);
-    if (rc != DOJO_OK) return rc;
+    TRY(to_max ? dojo_minimal_to_maximal_dev(s, din, dout, nullptr) : dojo_maximal_to_minimal_dev(s, din, dout, nullptr));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, dout, B * n_out * w, hipMemcpyDeviceToHost));
     return DOJO_OK;
@@ -2455,47 +2248,32 @@ int dojo_next_state_dev(DojoHandle s, const void* z, void* z_out, void* stream) 
     Enter enter_(s);
     if (!s || !z || !z_out) { g_err = "dojo_next_state_dev: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    { int rcj = join_groups(s, (hipStream_t)stream); if (rcj != DOJO_OK) return rcj; }   // (asynchronous steps still in flight may write / read these buffers)
-    const long long n = (long long)s->B * s->M.Nb; const int T_ = 256;
-    if (s->dtype == DOJO_DTYPE_F32) hipLaunchKernelGGL((ckern::next_state_kernel<float>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, s->M.Nb, s->M.dt, s->B, (const float*)z, (float*)z_out);
-    else hipLaunchKernelGGL((ckern::next_state_kernel<double>), dim3((unsigned)((n + T_ - 1) / T_)), dim3(T_), 0, (hipStream_t)stream, s->M.Nb, s->M.dt, s->B, (const double*)z, (double*)z_out);
-    HIPCHK(hipGetLastError());
-    return DOJO_OK;
+    TRY(join_groups(s, (hipStream_t)stream));      // (asynchronous steps still in flight may write / read these buffers)
+    return by_dtype(s, [&](auto t) { return launch_next_state<decltype(t)>(s, z, z_out, (hipStream_t)stream); });
 }
 int dojo_next_state(DojoHandle s, const void* z, void* z_out) {
     Enter enter_(s);
     if (!s || !z || !z_out) { g_err = "dojo_next_state: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     const size_t bytes = (size_t)s->B * 13 * s->M.Nb * s->w;
-    DevBuf a, b;
-    HIPCHK(a.alloc(bytes)); HIPCHK(b.alloc(bytes));
-    HIPCHK(hipMemcpy(a.p, z, bytes, hipMemcpyHostToDevice));
-    int rc = dojo_next_state_dev(s, a.p, b.p, nullptr);
-    if (rc != DOJO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(z_out, b.p, bytes, hipMemcpyDeviceToHost));
-    return DOJO_OK;
+    Staging st;
+    const auto &a = st.input(bytes, z), &b = st.output(bytes, z_out);
+    TRY(st.allocate());
+    TRY(dojo_next_state_dev(s, a.p, b.p, nullptr));
+    return st.finish();
 }
 
 int dojo_step_minimal(DojoHandle s, const void* x, const void* u, void* x_next, int32_t* status, int32_t* iters) {
     Enter enter_(s);
     if (!s || !x || !x_next) { g_err = "dojo_step_minimal: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    size_t B = s->B, w = s->w, nm = 2 * s->M.nu, nu = s->M.nu;
-    int rc;
+    const size_t B = s->B, w = s->w, nm = 2 * s->M.nu;
+    const void* d_u = nullptr;
     ENSURE(s->d_x, B * (nm + 1) * w); ENSURE(s->d_xn, B * (nm + 1) * w);
-    ENSURE(s->d_u, B * (nu + 1) * w);
-    ENSURE(s->d_status, B * sizeof(int)); ENSURE(s->d_iters, B * sizeof(int));
-    HIPCHK(hipMemcpy(s->d_x, x, B * nm * w, hipMemcpyHostToDevice));
-    if (u && nu) HIPCHK(hipMemcpy(s->d_u, u, B * nu * w, hipMemcpyHostToDevice));
-    rc = dojo_step_minimal_dev(s, s->d_x, (u && nu) ? s->d_u : nullptr, s->d_xn, s->d_status, s->d_iters, nullptr);
-    if (rc != DOJO_OK) return rc;
+    TRY(upload_step(s, s->d_x, x, nm, u, &d_u));
+    TRY(dojo_step_minimal_dev(s, s->d_x, d_u, s->d_xn, s->d_status, s->d_iters, nullptr));
     s->have_grad = false;                                   // d_z / d_u now hold this (forward-only) step's inputs
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(x_next, s->d_xn, B * nm * w, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, s->d_status, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(hipMemcpy(iters, s->d_iters, B * sizeof(int), hipMemcpyDeviceToHost));
-    return DOJO_OK;
+    return download_step(s, x_next, s->d_xn, nm, status, iters);
 }
 
 int dojo_last_kernel_ms(DojoHandle s, double* ms) {
@@ -2523,7 +2301,7 @@ int dojo_kernel_time_totals(DojoHandle s, double* step_ms, double* ift_ms, int64
     Enter enter_(s);
     if (!s) { g_err = "dojo_kernel_time_totals: bad argument"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
-    for (auto& e : s->ring) { int rc = drain_slot(s, e); if (rc != DOJO_OK) return rc; }
+    for (auto& e : s->ring) TRY(drain_slot(s, e));
     if (step_ms) *step_ms = s->acc_step_ms;
     if (ift_ms) *ift_ms = s->acc_ift_ms;
     if (launches) *launches = (int64_t)s->acc_n;

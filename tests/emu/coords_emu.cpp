@@ -1,6 +1,6 @@
 // coords_emu.cpp -- the per-joint coordinate templates of dojo.jl_amd/csrc/dojo_coords.hpp on the host (TEST INFRASTRUCTURE).
 //
-// The coordinate kernels of dojo_hip.hip are thin wrappers around coords::joint_min2max / coords::joint_max2min, instantiated for double (the maps)
+// The coordinate kernels of dojo_coord_kernels.hpp are thin wrappers around coords::joint_min2max / coords::joint_max2min, instantiated for double (the maps)
 // and Dual<24> (their Jacobians).  This file instantiates the same templates with g++ for ONE environment, so the CPU tier can pin the series
 // branches and the dual arithmetic against the oracle (tests/test_coords_emu.py); what is left to the GPU tier is the kernels' indexing and launches.
 // The loops below restate min2max_kernel, max2min_kernel, min2max_jac_kernel and max2min_jac_kernel for fp64 buffers.  Not a product path.

@@ -1,4 +1,4 @@
-"""The coordinate kernels of dojo.jl_amd/csrc/dojo_hip.hip (min2max_kernel, max2min_kernel, min2max_jac_kernel, max2min_jac_kernel, chain_mid_kernel,
+"""The coordinate kernels of dojo.jl_amd/csrc/dojo_coord_kernels.hpp (min2max_kernel, max2min_kernel, min2max_jac_kernel, max2min_jac_kernel, chain_mid_kernel,
 chain_out_kernel, next_state_kernel) and observation_jacobian_kernel on the device, against the C++ oracle: every joint prototype, rotations at 0, on either
 side of the series switches of dojo_coords.hpp and beyond pi (tests/fd_coords.py: edge_inputs), fp64 and fp32 handles, batches that end inside a block
 and environments that straddle one.  Every environment of a batch has an input row of its own and every environment is compared unless a test says
