@@ -28,53 +28,63 @@ class DojoError(RuntimeError):
     pass
 
 
+# include/dojo_hip.h, one line per entry point: the C return type and the parameters -- p: DojoHandle, any pointer (struct pointers, int32_t out[3] and
+# the stream included), i: int32_t, l: int64_t, d: double.  With argtypes a plain Python int is a full 64-bit address; without, ctypes would cut it to a C int.
+_KINDS = {"p": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
+_SIGNATURES = {
+    "dojo_device_count": (C.c_int, ""), "dojo_last_error": (C.c_char_p, ""), "dojo_handle_error": (C.c_char_p, "p"), "dojo_create": (C.c_int, "piiip"), "dojo_destroy": (None, "p"),
+    "dojo_get_dims": (C.c_int, "pp"), "dojo_set_options": (C.c_int, "pp"), "dojo_set_gradient_mode": (C.c_int, "pi"), "dojo_set_refinement": (C.c_int, "pd"),
+    "dojo_step": (C.c_int, "ppppppi"), "dojo_step_impulses": (C.c_int, "pppppp"), "dojo_next_state": (C.c_int, "ppp"), "dojo_next_state_dev": (C.c_int, "pppp"),
+    "dojo_get_solution": (C.c_int, "pppp"), "dojo_get_mu": (C.c_int, "pp"), "dojo_get_diagnostics": (C.c_int, "pp"), "dojo_get_kernel_build": (C.c_int, "pp"),
+    "dojo_gradients": (C.c_int, "ppp"), "dojo_rollout": (C.c_int, "pppipp"), "dojo_get_state": (C.c_int, "pp"), "dojo_step_dev": (C.c_int, "ppppppppp"),
+    "dojo_set_async": (C.c_int, "pi"), "dojo_set_groups": (C.c_int, "pi"), "dojo_set_iteration_cap": (C.c_int, "pi"), "dojo_set_dispatch_order": (C.c_int, "pi"),
+    "dojo_join": (C.c_int, "pp"), "dojo_comm_unique_id": (C.c_int, "p"), "dojo_comm_init": (C.c_int, "piip"), "dojo_allgather_dev": (C.c_int, "ppplip"),
+    "dojo_comm_info": (C.c_int, "ppp"), "dojo_rollout_dev": (C.c_int, "pppippp"), "dojo_set_external_force": (C.c_int, "pp"), "dojo_set_external_force_dev": (C.c_int, "pp"),
+    "dojo_simulate": (C.c_int, "pppippp"), "dojo_simulate_dev": (C.c_int, "pppipppp"), "dojo_rollout_record_dev": (C.c_int, "pppippppp"),
+    "dojo_rollout_adjoint_dev": (C.c_int, "pipppippppp"), "dojo_rollout_gradients": (C.c_int, "pppipipppp"), "dojo_set_contact_data": (C.c_int, "pp"),
+    "dojo_get_contact_data": (C.c_int, "pp"), "dojo_rollout_data_record_dev": (C.c_int, "pppipppppp"), "dojo_rollout_data_adjoint_dev": (C.c_int, "pipppipppppp"),
+    "dojo_rollout_data_gradients": (C.c_int, "pppipipppppp"), "dojo_rollout_tangent_dev": (C.c_int, "piippppppipppp"), "dojo_rollout_tangents": (C.c_int, "pppiipppippp"),
+    "dojo_rollout_policy_dev": (C.c_int, "pppippppp"), "dojo_rollout_policy": (C.c_int, "pppipppp"), "dojo_observation_jacobian_dev": (C.c_int, "ppipp"),
+    "dojo_observation_jacobian": (C.c_int, "ppp"), "dojo_rollout_policy_record_dev": (C.c_int, "pppippppppp"), "dojo_rollout_policy_adjoint_dev": (C.c_int, "ppipp"),
+    "dojo_rollout_policy_gradients": (C.c_int, "pppipipppppppppp"), "dojo_rollout_mlp_dev": (C.c_int, "pppipppppp"), "dojo_rollout_mlp": (C.c_int, "pppipppp"),
+    "dojo_rollout_mlp_record_dev": (C.c_int, "pppipppppppp"), "dojo_rollout_mlp_adjoint_dev": (C.c_int, "ppipp"), "dojo_rollout_mlp_gradients": (C.c_int, "pppipippppppppp"),
+    "dojo_riccati_dev": (C.c_int, "pipp"), "dojo_riccati": (C.c_int, "pip"), "dojo_observe": (C.c_int, "ppi"), "dojo_observe_dev": (C.c_int, "pppip"),
+    "dojo_contact_gradients": (C.c_int, "pp"), "dojo_contact_gradients_dev": (C.c_int, "ppppp"), "dojo_minimal_to_maximal": (C.c_int, "ppp"),
+    "dojo_maximal_to_minimal": (C.c_int, "ppp"), "dojo_step_minimal": (C.c_int, "pppppp"), "dojo_minimal_to_maximal_dev": (C.c_int, "pppp"),
+    "dojo_maximal_to_minimal_dev": (C.c_int, "pppp"), "dojo_step_minimal_dev": (C.c_int, "ppppppp"), "dojo_minimal_gradients": (C.c_int, "pppppppp"),
+    "dojo_minimal_gradients_dev": (C.c_int, "ppppppppp"), "dojo_last_kernel_ms": (C.c_int, "pp"), "dojo_last_kernel_times": (C.c_int, "ppp"),
+    "dojo_kernel_time_totals": (C.c_int, "ppppi"),
+}
+EXPORTED_SYMBOLS = list(_SIGNATURES)
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
             raise DojoError("libdojo_hip.so not built (run __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(_LIB_PATH)
-        L.dojo_last_error.restype = C.c_char_p
-        L.dojo_handle_error.restype = C.c_char_p; L.dojo_handle_error.argtypes = [C.c_void_p]
-        for f in ("dojo_device_count", "dojo_create", "dojo_get_dims", "dojo_set_options", "dojo_set_gradient_mode", "dojo_set_refinement", "dojo_set_async", "dojo_set_groups", "dojo_set_iteration_cap", "dojo_set_dispatch_order", "dojo_join", "dojo_comm_unique_id", "dojo_comm_init", "dojo_allgather_dev", "dojo_comm_info", "dojo_step", "dojo_step_impulses", "dojo_get_mu", "dojo_get_diagnostics", "dojo_get_kernel_build", "dojo_next_state", "dojo_next_state_dev",
-                  "dojo_get_solution", "dojo_gradients", "dojo_rollout", "dojo_get_state", "dojo_step_dev", "dojo_rollout_dev",
-                  "dojo_last_kernel_ms", "dojo_last_kernel_times", "dojo_kernel_time_totals",
-                  "dojo_minimal_to_maximal", "dojo_maximal_to_minimal", "dojo_step_minimal",
-                  "dojo_minimal_to_maximal_dev", "dojo_maximal_to_minimal_dev", "dojo_step_minimal_dev",
-                  "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
-                  "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients", "dojo_rollout_policy_dev", "dojo_rollout_policy",
-                  "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
-                  "dojo_rollout_policy_gradients",
-                  "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
-                  "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients",
-                  "dojo_rollout_tangent_dev", "dojo_rollout_tangents", "dojo_riccati_dev", "dojo_riccati"):
-            getattr(L, f).restype = C.c_int
-        vp, i32 = C.c_void_p, C.c_int32
-        L.dojo_rollout_tangent_dev.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]      # h, H, T, DZ, DU, DC, dz0, dU, dtheta, tan_space, Z, status, dZ, stream
-        L.dojo_rollout_tangents.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]                 # h, z0, U, H, T, dz0, dU, dtheta, tan_space, Z, status, dZ
-        L.dojo_riccati_dev.argtypes = [vp, i32, vp, vp]                                                       # h, H, DojoRiccati*, stream
-        L.dojo_riccati.argtypes = [vp, i32, vp]                                                               # h, H, DojoRiccati*
-        L.dojo_destroy.restype = None
+        for name, (restype, args) in _SIGNATURES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, [_KINDS[k] for k in args]
         _lib = L
     return _lib
 
 
-EXPORTED_SYMBOLS = ["dojo_device_count", "dojo_last_error", "dojo_handle_error", "dojo_step_impulses", "dojo_get_mu", "dojo_get_diagnostics", "dojo_get_kernel_build", "dojo_next_state", "dojo_next_state_dev", "dojo_create", "dojo_destroy", "dojo_get_dims", "dojo_set_options",
-                    "dojo_set_gradient_mode", "dojo_set_refinement", "dojo_set_async", "dojo_set_groups", "dojo_set_iteration_cap", "dojo_set_dispatch_order", "dojo_join", "dojo_comm_unique_id", "dojo_comm_init", "dojo_allgather_dev", "dojo_comm_info", "dojo_step", "dojo_get_solution", "dojo_gradients", "dojo_rollout", "dojo_get_state",
-                    "dojo_step_dev", "dojo_rollout_dev", "dojo_last_kernel_ms", "dojo_last_kernel_times", "dojo_kernel_time_totals",
-                    "dojo_minimal_to_maximal", "dojo_maximal_to_minimal", "dojo_step_minimal",
-                    "dojo_minimal_to_maximal_dev", "dojo_maximal_to_minimal_dev", "dojo_step_minimal_dev",
-                    "dojo_contact_gradients", "dojo_contact_gradients_dev", "dojo_minimal_gradients", "dojo_minimal_gradients_dev",
-                    "dojo_simulate", "dojo_simulate_dev", "dojo_observe", "dojo_observe_dev",
-                    "dojo_set_external_force", "dojo_set_external_force_dev",
-                    "dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients",
-                    "dojo_rollout_policy_dev", "dojo_rollout_policy",
-                    "dojo_observation_jacobian_dev", "dojo_observation_jacobian", "dojo_rollout_policy_record_dev", "dojo_rollout_policy_adjoint_dev",
-                    "dojo_rollout_policy_gradients",
-                    "dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients",
-                    "dojo_set_contact_data", "dojo_get_contact_data", "dojo_rollout_data_record_dev", "dojo_rollout_data_adjoint_dev", "dojo_rollout_data_gradients",
-                    "dojo_rollout_tangent_dev", "dojo_rollout_tangents",
-                    "dojo_riccati_dev", "dojo_riccati"]
+def addr(x):
+    """the address to hand to the library: of a NumPy array, of anything with data_ptr() (a torch tensor); None and a plain int pass through"""
+    if x is None or isinstance(x, int):
+        return x
+    return x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr()
+
+
+_p = addr      # the earlier name, kept for callers outside this package that still spell it
+
+
+def torch_stream(device=None):
+    """the handle of torch's current stream on `device`, for the stream argument of the `_dev` entries"""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 class DojoPolicy(C.Structure):
@@ -179,10 +189,6 @@ def _chk(rc):
         raise DojoError("libdojo_hip error %d: %s" % (rc, lib().dojo_last_error().decode()))
 
 
-def _p(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
-
-
 class BatchedMechanism:
     """B independent copies of one Dojo `Mechanism` resident on one GPU."""
 
@@ -239,7 +245,7 @@ class BatchedMechanism:
         _chk(lib().dojo_set_dispatch_order(self.h, int(mode)))
 
     def join(self, stream=None):
-        _chk(lib().dojo_join(self.h, C.c_void_p(stream or 0)))
+        _chk(lib().dojo_join(self.h, stream or 0))
 
     # ---- multi-GPU: RCCL communicator of the handle (one process per GPU) ----
     @staticmethod
@@ -249,14 +255,14 @@ class BatchedMechanism:
         return bytes(buf)
 
     def comm_init(self, rank, world, unique_id):
-        _chk(lib().dojo_comm_init(self.h, int(rank), int(world), C.c_char_p(unique_id)))
+        _chk(lib().dojo_comm_init(self.h, int(rank), int(world), unique_id))
 
     def allgather_dev(self, send_ptr, recv_ptr, count, as_int32=False, stream=None):
-        _chk(lib().dojo_allgather_dev(self.h, C.c_void_p(send_ptr), C.c_void_p(recv_ptr), C.c_int64(int(count)), int(bool(as_int32)), C.c_void_p(stream or 0)))
+        _chk(lib().dojo_allgather_dev(self.h, send_ptr, recv_ptr, int(count), int(bool(as_int32)), stream or 0))
 
     def set_refinement(self, stiffness):
         """Refine the linear solves of environments whose cones reach max gamma/s > stiffness (inf: never, 0: always)."""
-        _chk(lib().dojo_set_refinement(self.h, C.c_double(float(stiffness))))
+        _chk(lib().dojo_set_refinement(self.h, float(stiffness)))
 
     def _arr(self, a, shape):
         a = np.ascontiguousarray(a, dtype=self.np_dtype)
@@ -264,12 +270,68 @@ class BatchedMechanism:
             raise ValueError("expected shape %s, got %s" % (shape, a.shape))
         return a
 
+    def _controls(self, U, steps):
+        """-> (U, H) of an open-loop rollout: the horizon is U's, or `steps` without controls"""
+        if U is not None and self.spec.nu:
+            U = np.ascontiguousarray(U, dtype=self.np_dtype); H = U.shape[0]
+            assert U.shape == (H, self.batch, self.spec.nu)
+            return U, H
+        return None, int(steps)
+
+    @staticmethod
+    def _space(name, value):
+        """cot_space / tan_space -> 0 (tangent coordinates) or 1 (state coordinates)"""
+        if value not in ("tangent", "state", 0, 1):
+            raise ValueError("%s must be 'tangent' or 'state'" % name)
+        return 1 if value in ("state", 1) else 0
+
+    def _cotangents(self, who, G, steps, cot_space):
+        """-> (G, H, cs): the cotangents in the handle dtype, the horizon they hold and the code of cot_space"""
+        B, s = self.batch, self.spec
+        cs = self._space("cot_space", cot_space)
+        if G is None:
+            raise ValueError("%s needs the cotangents G of the loss w.r.t. the state after every step" % who)
+        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
+        if G.shape != (H, B, s.nz if cs else s.nx):
+            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
+        if steps is not None and int(steps) != H:
+            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
+        return G, H, cs
+
+    def _policy_terms(self, mean, scale, U_ff, H, nobs):
+        """the optional arguments both policies share, checked in this order: mean, scale [nobs], U_ff [H,B,nu]"""
+        return (None if mean is None else self._arr(mean, (nobs,)), None if scale is None else self._arr(scale, (nobs,)),
+                None if U_ff is None else self._arr(U_ff, (H, self.batch, self.spec.nu)))
+
+    def _affine_policy(self, W, bias, mean, scale, U_ff, H, nobs, act_off, contact_forces=False, contact_init=0):
+        """-> (DojoPolicy, the arrays it points to: W, bias, mean, scale, U_ff in the handle dtype)"""
+        W = np.ascontiguousarray(W, dtype=self.np_dtype)
+        if W.ndim not in (2, 3):
+            raise ValueError("W must be [na, nobs] or [B, na, nobs]")
+        per_env, na = W.ndim == 3, W.shape[-2]
+        W = self._arr(W, (self.batch, na, nobs) if per_env else (na, nobs))
+        bias = None if bias is None else self._arr(bias, (self.batch, na) if per_env else (na,))
+        arrays = (W, bias) + self._policy_terms(mean, scale, U_ff, H, nobs)
+        return DojoPolicy(*map(addr, arrays), int(per_env), int(act_off), int(na), int(bool(contact_forces)), int(contact_init), 0), arrays
+
+    def _mlp_policy(self, theta, widths, mean, scale, U_ff, H, nobs, act_off, contact_forces=False, contact_init=0):
+        """-> (DojoMlpPolicy, the arrays it points to: theta, mean, scale, U_ff in the handle dtype)"""
+        theta, w, per_env = self._mlp_args(theta, widths)
+        arrays = (theta,) + self._policy_terms(mean, scale, U_ff, H, nobs)
+        return mlp_policy_struct(*map(addr, arrays), per_env, act_off, w, bool(contact_forces), contact_init), arrays
+
+    def _closed_loop_outputs(self, H, nobs):
+        """-> Z [H,B,13Nb], OBS [H+1,B,nobs], U [H,B,nu], status [H,B]"""
+        B, s, H = self.batch, self.spec, max(H, 0)
+        return (np.empty((H, B, s.nz), self.np_dtype), np.empty((H + 1, B, nobs), self.np_dtype), np.empty((H, B, s.nu), self.np_dtype),
+                np.empty((H, B), np.int32))
+
     def step(self, z, u=None, with_gradient=False):
         B, s = self.batch, self.spec
         z = self._arr(z, (B, s.nz))
         u = None if (u is None or s.nu == 0) else self._arr(u, (B, s.nu))
         zn = np.empty_like(z); st = np.empty(B, np.int32); it = np.empty(B, np.int32)
-        _chk(lib().dojo_step(self.h, _p(z), _p(u), _p(zn), _p(st), _p(it), int(with_gradient)))
+        _chk(lib().dojo_step(self.h, addr(z), addr(u), addr(zn), addr(st), addr(it), int(with_gradient)))
         return zn, st, it
 
     def step_impulses(self, z, jf):
@@ -279,33 +341,33 @@ class BatchedMechanism:
         z = self._arr(z, (B, s.nz))
         jf = self._arr(np.asarray(jf).reshape(B, 6 * s.Nb), (B, 6 * s.Nb))
         zn = np.empty_like(z); st = np.empty(B, np.int32); it = np.empty(B, np.int32)
-        _chk(lib().dojo_step_impulses(self.h, _p(z), _p(jf), _p(zn), _p(st), _p(it)))
+        _chk(lib().dojo_step_impulses(self.h, addr(z), addr(jf), addr(zn), addr(st), addr(it)))
         return zn, st, it
 
     def next_state(self, z):
         """get_next_state of a state whose velocities are its solution: maps dojo_step's return (the internal state after
         update_state!) to the vector the reference's step! literally returns."""
         z = self._arr(z, (self.batch, self.spec.nz)); zo = np.empty_like(z)
-        _chk(lib().dojo_next_state(self.h, _p(z), _p(zo)))
+        _chk(lib().dojo_next_state(self.h, addr(z), addr(zo)))
         return zo
 
     def diagnostics(self, read=True):
         """[B, 2]: max gamma/s of the cones and the largest Gauss-Jordan multiplier at the last step's final linearization
         (the first call switches the recording on)"""
         dg = np.zeros((self.batch, 2)) if read else None
-        _chk(lib().dojo_get_diagnostics(self.h, _p(dg)))
+        _chk(lib().dojo_get_diagnostics(self.h, addr(dg)))
         return dg
 
     def get_mu(self):
         mu = np.empty(self.batch, np.float64)
-        _chk(lib().dojo_get_mu(self.h, _p(mu)))
+        _chk(lib().dojo_get_mu(self.h, addr(mu)))
         return mu
 
     def kernel_build(self):
         """dojo_get_kernel_build: (family, MAXC, waves) of the kernel build that steps this handle -- family one of KERNEL_FAMILIES,
         waves 1 / 2 = the quad mapping's wavefronts per workgroup, 0 = the lane mapping"""
         out = np.zeros(3, np.int32)
-        _chk(lib().dojo_get_kernel_build(self.h, _p(out)))
+        _chk(lib().dojo_get_kernel_build(self.h, addr(out)))
         return KERNEL_FAMILIES[int(out[0])], int(out[1]), int(out[2])
 
     def last_error(self):
@@ -316,27 +378,23 @@ class BatchedMechanism:
         vel = np.empty((B, 6 * s.Nb), self.np_dtype)
         ji = np.empty((B, max(s.n_joint_impulses, 1)), self.np_dtype)
         cs = np.empty((B, max(self.csg_per * len(s.contacts), 1)), self.np_dtype)
-        _chk(lib().dojo_get_solution(self.h, _p(vel), _p(ji), _p(cs)))
+        _chk(lib().dojo_get_solution(self.h, addr(vel), addr(ji), addr(cs)))
         return vel, ji[:, :s.n_joint_impulses], cs[:, :self.csg_per * len(s.contacts)]
 
     def gradients(self):
         B, s = self.batch, self.spec
         dz = np.empty((B, s.nx, s.nx), self.np_dtype)
         du = np.empty((B, s.nx, max(s.nu, 1)), self.np_dtype)
-        _chk(lib().dojo_gradients(self.h, _p(dz), _p(du)))
+        _chk(lib().dojo_gradients(self.h, addr(dz), addr(du)))
         return dz, du[:, :, :s.nu]
 
     def rollout(self, z0, U=None, steps=None, record=True):
         B, s = self.batch, self.spec
         z0 = self._arr(z0, (B, s.nz))
-        if U is not None and s.nu:
-            U = np.ascontiguousarray(U, dtype=self.np_dtype); H = U.shape[0]
-            assert U.shape == (H, B, s.nu)
-        else:
-            U = None; H = int(steps)
+        U, H = self._controls(U, steps)
         Z = np.empty((H, B, s.nz), self.np_dtype) if record else None
         st = np.empty((H, B), np.int32)
-        _chk(lib().dojo_rollout(self.h, _p(z0), _p(U), H, _p(Z), _p(st)))
+        _chk(lib().dojo_rollout(self.h, addr(z0), addr(U), H, addr(Z), addr(st)))
         return Z, st
 
     def rollout_gradients(self, z0, U=None, G=None, steps=None, cot_space="tangent"):
@@ -347,23 +405,11 @@ class BatchedMechanism:
         through a failed step.  GRAD_CONSISTENT (set_gradient_mode) is the mode whose chain is the derivative of the rollout."""
         B, s = self.batch, self.spec
         z0 = self._arr(z0, (B, s.nz))
-        if cot_space not in ("tangent", "state", 0, 1):
-            raise ValueError("cot_space must be 'tangent' or 'state'")
-        cs = 1 if cot_space in ("state", 1) else 0
-        if G is None:
-            raise ValueError("rollout_gradients needs the cotangents G of the loss w.r.t. the state after every step")
-        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
-        if G.shape != (H, B, s.nz if cs else s.nx):
-            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
-        if steps is not None and int(steps) != H:
-            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
-        if U is not None and s.nu:
-            U = self._arr(U, (H, B, s.nu))
-        else:
-            U = None
+        G, H, cs = self._cotangents("rollout_gradients", G, steps, cot_space)
+        U = self._arr(U, (H, B, s.nu)) if (U is not None and s.nu) else None
         Z = np.empty((H, B, s.nz), self.np_dtype); st = np.empty((H, B), np.int32)
         gU = np.zeros((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
-        _chk(lib().dojo_rollout_gradients(self.h, _p(z0), _p(U), H, _p(G), cs, _p(Z), _p(st), _p(gU) if s.nu else None, _p(gz)))
+        _chk(lib().dojo_rollout_gradients(self.h, addr(z0), addr(U), H, addr(G), cs, addr(Z), addr(st), addr(gU) if s.nu else None, addr(gz)))
         return Z, st, gU, gz
 
     def set_contact_data(self, theta):
@@ -372,12 +418,12 @@ class BatchedMechanism:
         differentiable step first."""
         Nc = len(self.spec.contacts)
         th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(Nc, 5))
-        _chk(lib().dojo_set_contact_data(self.h, _p(th) if Nc else None))
+        _chk(lib().dojo_set_contact_data(self.h, addr(th) if Nc else None))
 
     def contact_data(self):
         """the handle's contact data [Nc, 5] (dojo_get_contact_data)"""
         th = np.zeros((len(self.spec.contacts), 5), np.float64)
-        _chk(lib().dojo_get_contact_data(self.h, _p(th) if len(th) else None))
+        _chk(lib().dojo_get_contact_data(self.h, addr(th) if len(th) else None))
         return th
 
     def rollout_data_gradients(self, z0, U=None, G=None, steps=None, cot_space="tangent", per_env=False):
@@ -388,22 +434,13 @@ class BatchedMechanism:
         B, s = self.batch, self.spec
         Nc = len(s.contacts)
         z0 = self._arr(z0, (B, s.nz))
-        if cot_space not in ("tangent", "state", 0, 1):
-            raise ValueError("cot_space must be 'tangent' or 'state'")
-        cs = 1 if cot_space in ("state", 1) else 0
-        if G is None:
-            raise ValueError("rollout_data_gradients needs the cotangents G of the loss w.r.t. the state after every step")
-        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
-        if G.shape != (H, B, s.nz if cs else s.nx):
-            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
-        if steps is not None and int(steps) != H:
-            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
+        G, H, cs = self._cotangents("rollout_data_gradients", G, steps, cot_space)
         U = self._arr(U, (H, B, s.nu)) if (U is not None and s.nu) else None
         Z = np.empty((H, B, s.nz), self.np_dtype); st = np.empty((H, B), np.int32)
         gth = np.zeros((Nc, 5), self.np_dtype); gte = np.zeros((B, Nc, 5), self.np_dtype) if per_env else None
         gU = np.zeros((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
-        _chk(lib().dojo_rollout_data_gradients(self.h, _p(z0), _p(U), H, _p(G), cs, _p(Z), _p(st), _p(gth) if Nc else None,
-                                               _p(gte) if (per_env and Nc) else None, _p(gU) if s.nu else None, _p(gz)))
+        _chk(lib().dojo_rollout_data_gradients(self.h, addr(z0), addr(U), H, addr(G), cs, addr(Z), addr(st), addr(gth) if Nc else None,
+                                               addr(gte) if (per_env and Nc) else None, addr(gU) if s.nu else None, addr(gz)))
         return Z, st, gth, gte, gU, gz
 
     def rollout_tangents(self, z0, U=None, dz0=None, dU=None, dtheta=None, steps=None, tan_space="tangent"):
@@ -415,9 +452,7 @@ class BatchedMechanism:
         B, s = self.batch, self.spec
         nth = 5 * len(s.contacts)
         z0 = self._arr(z0, (B, s.nz))
-        if tan_space not in ("tangent", "state", 0, 1):
-            raise ValueError("tan_space must be 'tangent' or 'state'")
-        ts = 1 if tan_space in ("state", 1) else 0
+        ts = self._space("tan_space", tan_space)
         dz0 = None if dz0 is None else np.ascontiguousarray(dz0, dtype=self.np_dtype)
         dU = None if (dU is None or not s.nu) else np.ascontiguousarray(dU, dtype=self.np_dtype)
         dtheta = None if (dtheta is None or not nth) else np.ascontiguousarray(dtheta, dtype=self.np_dtype)
@@ -441,7 +476,7 @@ class BatchedMechanism:
                 raise ValueError("expected %s of shape %s, got %s" % (name, shape, a.shape))
         Z = np.empty((H, B, s.nz), self.np_dtype); st = np.empty((H, B), np.int32)
         dZ = np.empty((H, B, T, s.nz if ts else s.nx), self.np_dtype)
-        _chk(lib().dojo_rollout_tangents(self.h, _p(z0), _p(U), H, T, _p(dz0), _p(dU), _p(dtheta), ts, _p(Z), _p(st), _p(dZ)))
+        _chk(lib().dojo_rollout_tangents(self.h, addr(z0), addr(U), H, T, addr(dz0), addr(dU), addr(dtheta), ts, addr(Z), addr(st), addr(dZ)))
         return Z, st, dZ
 
     def riccati(self, A, Bm, lx, lu, lxx, luu, lux=None, mu=None, status=None, act_off=0, na=None, value=True):
@@ -457,8 +492,7 @@ class BatchedMechanism:
         status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
         K = np.empty((H, B, na, n), self.np_dtype); kff = np.empty((H, B, na), self.np_dtype); fail = np.empty(B, np.int32); dV = np.empty((B, 2), self.np_dtype)
         Vx = np.empty((B, n), self.np_dtype) if value else None; Vxx = np.empty((B, n, n), self.np_dtype) if value else None
-        a_ = lambda x: None if x is None else x.ctypes.data
-        r = DojoRiccati(a_(A), a_(Bm), a_(status), a_(lx), a_(lu), a_(lxx), a_(luu), a_(lux), a_(mu), a_(K), a_(kff), a_(fail), a_(dV), a_(Vx), a_(Vxx), int(act_off), na)
+        r = DojoRiccati(*map(addr, (A, Bm, status, lx, lu, lxx, luu, lux, mu, K, kff, fail, dV, Vx, Vxx)), int(act_off), na)
         _chk(lib().dojo_riccati(self.h, H, C.byref(r)))
         return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
 
@@ -471,22 +505,10 @@ class BatchedMechanism:
         B, s = self.batch, self.spec
         H = int(steps)
         z0 = self._arr(z0, (B, s.nz))
-        W = np.ascontiguousarray(W, dtype=self.np_dtype)
-        if W.ndim not in (2, 3):
-            raise ValueError("W must be [na, nobs] or [B, na, nobs]")
-        per_env = W.ndim == 3
-        na = W.shape[-2]
         nobs = 2 * s.nu + (len(s.contacts) if contact_forces else 0)
-        W = self._arr(W, (B, na, nobs) if per_env else (na, nobs))
-        bias = None if bias is None else self._arr(bias, (B, na) if per_env else (na,))
-        mean = None if mean is None else self._arr(mean, (nobs,))
-        scale = None if scale is None else self._arr(scale, (nobs,))
-        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
-        ptr = lambda a: None if a is None else a.ctypes.data
-        pol = DojoPolicy(ptr(W), ptr(bias), ptr(mean), ptr(scale), ptr(U_ff), int(per_env), int(act_off), int(na), int(bool(contact_forces)), int(contact_init), 0)
-        Z = np.empty((max(H, 0), B, s.nz), self.np_dtype); OBS = np.empty((max(H, 0) + 1, B, nobs), self.np_dtype)
-        U = np.empty((max(H, 0), B, s.nu), self.np_dtype); st = np.empty((max(H, 0), B), np.int32)
-        _chk(lib().dojo_rollout_policy(self.h, _p(z0), C.byref(pol), H, _p(Z), _p(OBS), _p(U), _p(st)))
+        pol, keep = self._affine_policy(W, bias, mean, scale, U_ff, H, nobs, act_off, contact_forces, contact_init)
+        Z, OBS, U, st = self._closed_loop_outputs(H, nobs)
+        _chk(lib().dojo_rollout_policy(self.h, addr(z0), C.byref(pol), H, addr(Z), addr(OBS), addr(U), addr(st)))
         return Z, OBS, U, st
 
     def observation_jacobian(self, z):
@@ -496,7 +518,7 @@ class BatchedMechanism:
         B, s = self.batch, self.spec
         z = self._arr(z, (B, s.nz))
         M = np.empty((B, 2 * s.nu, 24), np.float64)
-        _chk(lib().dojo_observation_jacobian(self.h, _p(z), _p(M)))
+        _chk(lib().dojo_observation_jacobian(self.h, addr(z), addr(M)))
         return M
 
     def rollout_policy_gradients(self, z0, W, G, steps=None, bias=None, mean=None, scale=None, U_ff=None, act_off=0, G_u=None, G_obs=None, cot_space="tangent"):
@@ -507,36 +529,16 @@ class BatchedMechanism:
         the shapes of W, bias ([B,na,nobs] / [B,na] for one policy per environment; [na,nobs] / [na], summed over the batch, for a shared one)."""
         B, s = self.batch, self.spec
         z0 = self._arr(z0, (B, s.nz))
-        if cot_space not in ("tangent", "state", 0, 1):
-            raise ValueError("cot_space must be 'tangent' or 'state'")
-        cs = 1 if cot_space in ("state", 1) else 0
-        if G is None:
-            raise ValueError("rollout_policy_gradients needs the cotangents G of the loss w.r.t. the state after every step")
-        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
-        if G.shape != (H, B, s.nz if cs else s.nx):
-            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
-        if steps is not None and int(steps) != H:
-            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
-        W = np.ascontiguousarray(W, dtype=self.np_dtype)
-        if W.ndim not in (2, 3):
-            raise ValueError("W must be [na, nobs] or [B, na, nobs]")
-        per_env = W.ndim == 3
-        na, nobs = W.shape[-2], 2 * s.nu
-        W = self._arr(W, (B, na, nobs) if per_env else (na, nobs))
-        bias = None if bias is None else self._arr(bias, (B, na) if per_env else (na,))
-        mean = None if mean is None else self._arr(mean, (nobs,))
-        scale = None if scale is None else self._arr(scale, (nobs,))
-        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
+        G, H, cs = self._cotangents("rollout_policy_gradients", G, steps, cot_space)
+        nobs = 2 * s.nu
+        pol, keep = self._affine_policy(W, bias, mean, scale, U_ff, H, nobs, act_off)
         G_u = None if G_u is None else self._arr(G_u, (H, B, s.nu))
         G_obs = None if G_obs is None else self._arr(G_obs, (H + 1, B, nobs))
-        ptr = lambda a: None if a is None else a.ctypes.data
-        pol = DojoPolicy(ptr(W), ptr(bias), ptr(mean), ptr(scale), ptr(U_ff), int(per_env), int(act_off), int(na), 0, 0, 0)
-        Z = np.empty((H, B, s.nz), self.np_dtype); OBS = np.empty((H + 1, B, nobs), self.np_dtype)
-        U = np.empty((H, B, s.nu), self.np_dtype); st = np.empty((H, B), np.int32)
-        gW = np.empty_like(W); gb = np.empty((B, na) if per_env else (na,), self.np_dtype)
+        Z, OBS, U, st = self._closed_loop_outputs(H, nobs)
+        gW = np.empty_like(keep[0]); gb = np.empty((B, pol.na) if pol.per_env else (pol.na,), self.np_dtype)
         gU = np.empty((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
-        _chk(lib().dojo_rollout_policy_gradients(self.h, _p(z0), C.byref(pol), H, _p(G), cs, _p(G_u), _p(G_obs), _p(Z), _p(OBS), _p(U), _p(st),
-                                                 _p(gW), _p(gb), _p(gU), _p(gz)))
+        _chk(lib().dojo_rollout_policy_gradients(self.h, addr(z0), C.byref(pol), H, addr(G), cs, addr(G_u), addr(G_obs), addr(Z), addr(OBS), addr(U), addr(st),
+                                                 addr(gW), addr(gb), addr(gU), addr(gz)))
         return Z, OBS, U, st, gW, gb, gU, gz
 
     def _mlp_args(self, theta, widths):
@@ -558,15 +560,9 @@ class BatchedMechanism:
         H = int(steps)
         z0 = self._arr(z0, (B, s.nz))
         nobs = 2 * s.nu + (len(s.contacts) if contact_forces else 0)
-        theta, w, per_env = self._mlp_args(theta, widths)
-        mean = None if mean is None else self._arr(mean, (nobs,))
-        scale = None if scale is None else self._arr(scale, (nobs,))
-        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
-        ptr = lambda a: None if a is None else a.ctypes.data
-        pol = mlp_policy_struct(ptr(theta), ptr(mean), ptr(scale), ptr(U_ff), per_env, act_off, w, bool(contact_forces), contact_init)
-        Z = np.empty((max(H, 0), B, s.nz), self.np_dtype); OBS = np.empty((max(H, 0) + 1, B, nobs), self.np_dtype)
-        U = np.empty((max(H, 0), B, s.nu), self.np_dtype); st = np.empty((max(H, 0), B), np.int32)
-        _chk(lib().dojo_rollout_mlp(self.h, _p(z0), C.byref(pol), H, _p(Z), _p(OBS), _p(U), _p(st)))
+        pol, keep = self._mlp_policy(theta, widths, mean, scale, U_ff, H, nobs, act_off, contact_forces, contact_init)
+        Z, OBS, U, st = self._closed_loop_outputs(H, nobs)
+        _chk(lib().dojo_rollout_mlp(self.h, addr(z0), C.byref(pol), H, addr(Z), addr(OBS), addr(U), addr(st)))
         return Z, OBS, U, st
 
     def rollout_mlp_gradients(self, z0, theta, widths, G, steps=None, mean=None, scale=None, U_ff=None, act_off=0, G_u=None, G_obs=None, cot_space="tangent"):
@@ -576,30 +572,15 @@ class BatchedMechanism:
         has the shape of theta ([B, P]; or [P], summed over the batch, for a shared policy)."""
         B, s = self.batch, self.spec
         z0 = self._arr(z0, (B, s.nz))
-        if cot_space not in ("tangent", "state", 0, 1):
-            raise ValueError("cot_space must be 'tangent' or 'state'")
-        cs = 1 if cot_space in ("state", 1) else 0
-        if G is None:
-            raise ValueError("rollout_mlp_gradients needs the cotangents G of the loss w.r.t. the state after every step")
-        G = np.ascontiguousarray(G, dtype=self.np_dtype); H = G.shape[0]
-        if G.shape != (H, B, s.nz if cs else s.nx):
-            raise ValueError("expected G of shape %s, got %s" % ((H, B, s.nz if cs else s.nx), G.shape))
-        if steps is not None and int(steps) != H:
-            raise ValueError("steps = %d but G holds %d steps" % (int(steps), H))
+        G, H, cs = self._cotangents("rollout_mlp_gradients", G, steps, cot_space)
         nobs = 2 * s.nu
-        theta, w, per_env = self._mlp_args(theta, widths)
-        mean = None if mean is None else self._arr(mean, (nobs,))
-        scale = None if scale is None else self._arr(scale, (nobs,))
-        U_ff = None if U_ff is None else self._arr(U_ff, (H, B, s.nu))
+        pol, keep = self._mlp_policy(theta, widths, mean, scale, U_ff, H, nobs, act_off)
         G_u = None if G_u is None else self._arr(G_u, (H, B, s.nu))
         G_obs = None if G_obs is None else self._arr(G_obs, (H + 1, B, nobs))
-        ptr = lambda a: None if a is None else a.ctypes.data
-        pol = mlp_policy_struct(ptr(theta), ptr(mean), ptr(scale), ptr(U_ff), per_env, act_off, w)
-        Z = np.empty((H, B, s.nz), self.np_dtype); OBS = np.empty((H + 1, B, nobs), self.np_dtype)
-        U = np.empty((H, B, s.nu), self.np_dtype); st = np.empty((H, B), np.int32)
-        gth = np.empty_like(theta); gU = np.empty((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
-        _chk(lib().dojo_rollout_mlp_gradients(self.h, _p(z0), C.byref(pol), H, _p(G), cs, _p(G_u), _p(G_obs), _p(Z), _p(OBS), _p(U), _p(st),
-                                              _p(gth), _p(gU), _p(gz)))
+        Z, OBS, U, st = self._closed_loop_outputs(H, nobs)
+        gth = np.empty_like(keep[0]); gU = np.empty((H, B, s.nu), self.np_dtype); gz = np.empty((B, s.nx), self.np_dtype)
+        _chk(lib().dojo_rollout_mlp_gradients(self.h, addr(z0), C.byref(pol), H, addr(G), cs, addr(G_u), addr(G_obs), addr(Z), addr(OBS), addr(U), addr(st),
+                                              addr(gth), addr(gU), addr(gz)))
         return Z, OBS, U, st, gth, gU, gz
 
     def set_external_force(self, fext):
@@ -608,7 +589,7 @@ class BatchedMechanism:
         if fext is None:
             _chk(lib().dojo_set_external_force(self.h, None)); return
         f = self._arr(np.asarray(fext).reshape(self.batch, 6 * self.spec.Nb), (self.batch, 6 * self.spec.Nb))
-        _chk(lib().dojo_set_external_force(self.h, _p(f)))
+        _chk(lib().dojo_set_external_force(self.h, addr(f)))
 
     def simulate(self, z0, U=None, steps=None):
         """simulate!(mechanism, 1:H, storage, control!; record=true) with pre-sampled controls (simulate.jl:16-37).
@@ -616,15 +597,11 @@ class BatchedMechanism:
         x2(3) q2(4) v15(3) w15(3) px(3) pq(3) vl(3) wl(3) of the solved step (storage.jl:50-67), see STORAGE_FIELDS."""
         B, s = self.batch, self.spec
         z0 = self._arr(z0, (B, s.nz))
-        if U is not None and s.nu:
-            U = np.ascontiguousarray(U, dtype=self.np_dtype); H = U.shape[0]
-            assert U.shape == (H, B, s.nu)
-        else:
-            U = None; H = int(steps)
+        U, H = self._controls(U, steps)
         Z = np.empty((H, B, s.nz), self.np_dtype)
         S = np.empty((H, B, s.Nb, 25), self.np_dtype)
         st = np.empty((H, B), np.int32)
-        _chk(lib().dojo_simulate(self.h, _p(z0), _p(U), H, _p(Z), _p(S), _p(st)))
+        _chk(lib().dojo_simulate(self.h, addr(z0), addr(U), H, addr(Z), addr(S), addr(st)))
         return Z, S, st
 
     def observe(self, contact_forces=False):
@@ -632,7 +609,7 @@ class BatchedMechanism:
         get_state(::AntARS), ant_ars.jl:72-80) by the clamped normal impulses of the last step [B, 2nu + Nc]."""
         B, s = self.batch, self.spec
         obs = np.empty((B, 2 * s.nu + (len(s.contacts) if contact_forces else 0)), self.np_dtype)
-        _chk(lib().dojo_observe(self.h, _p(obs), int(bool(contact_forces))))
+        _chk(lib().dojo_observe(self.h, addr(obs), int(bool(contact_forces))))
         return obs
 
     def contact_gradients(self):
@@ -640,7 +617,7 @@ class BatchedMechanism:
         [B, 12Nb, 5Nc], contact data = [friction_coefficient, contact_radius, contact_origin(3)] per contact."""
         B, s = self.batch, self.spec
         dc = np.zeros((B, s.nx, 5 * len(s.contacts)), self.np_dtype)
-        _chk(lib().dojo_contact_gradients(self.h, _p(dc)))
+        _chk(lib().dojo_contact_gradients(self.h, addr(dc)))
         return dc
 
     # ---- minimal <-> maximal coordinates (src/mechanism/state.jl:9-66, src/simulation/step.jl:42-60) ----
@@ -648,14 +625,14 @@ class BatchedMechanism:
         B, s = self.batch, self.spec
         x = self._arr(x, (B, 2 * s.nu))
         z = np.empty((B, s.nz), self.np_dtype)
-        _chk(lib().dojo_minimal_to_maximal(self.h, _p(x), _p(z)))
+        _chk(lib().dojo_minimal_to_maximal(self.h, addr(x), addr(z)))
         return z
 
     def maximal_to_minimal(self, z):
         B, s = self.batch, self.spec
         z = self._arr(z, (B, s.nz))
         x = np.empty((B, 2 * s.nu), self.np_dtype)
-        _chk(lib().dojo_maximal_to_minimal(self.h, _p(z), _p(x)))
+        _chk(lib().dojo_maximal_to_minimal(self.h, addr(z), addr(x)))
         return x
 
     def step_minimal(self, x, u=None):
@@ -665,7 +642,7 @@ class BatchedMechanism:
         u = self._arr(u, (B, s.nu)) if (u is not None and s.nu) else None
         xn = np.empty((B, 2 * s.nu), self.np_dtype)
         st = np.empty(B, np.int32); it = np.empty(B, np.int32)
-        _chk(lib().dojo_step_minimal(self.h, _p(x), _p(u), _p(xn), _p(st), _p(it)))
+        _chk(lib().dojo_step_minimal(self.h, addr(x), addr(u), addr(xn), addr(st), addr(it)))
         return xn, st, it
 
     def minimal_gradients(self, x, u=None):
@@ -676,7 +653,7 @@ class BatchedMechanism:
         u = self._arr(u, (B, s.nu)) if (u is not None and s.nu) else None
         xn = np.empty((B, nm), self.np_dtype); st = np.empty(B, np.int32); it = np.empty(B, np.int32)
         jx = np.empty((B, nm, nm), self.np_dtype); ju = np.empty((B, nm, max(s.nu, 1)), self.np_dtype)
-        _chk(lib().dojo_minimal_gradients(self.h, _p(x), _p(u), _p(xn), _p(st), _p(it), _p(jx), _p(ju)))
+        _chk(lib().dojo_minimal_gradients(self.h, addr(x), addr(u), addr(xn), addr(st), addr(it), addr(jx), addr(ju)))
         return xn, st, it, jx, ju.reshape(-1)[:B * nm * s.nu].reshape(B, nm, s.nu)
 
     def last_kernel_ms(self):

@@ -24,14 +24,6 @@ import torch
 from . import api
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def lift_tangent(gz, z0):
     """[B,nx] tangent cotangent -> [B,13Nb] state cotangent at z0: g_x, g_v, g_omega are copied and g_q = q0 (x) (0, g_phi), the transpose's
     right inverse on the tangent space of the unit sphere at q0 (a 4-byte z0 stands for q0 / |q0|, as in the kernels)."""
@@ -41,10 +33,6 @@ def lift_tangent(gz, z0):
     s, v, p = q[..., :1], q[..., 1:], g[..., 6:9]
     gq = torch.cat([-(v * p).sum(-1, keepdim=True), s * p + torch.linalg.cross(v, p)], -1)
     return torch.cat([g[..., 0:6], gq, g[..., 9:12]], -1).reshape(B, -1).to(z0.dtype)
-
-
-def _addr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _dtype(mech):
@@ -98,7 +86,7 @@ class _Rollout(torch.autograd.Function):
         H, Uc = _controls(mech, U, steps)
         dev = z0.device
         Z, status, DZ, DU = _record(mech, H, dev)
-        api._chk(api.lib().dojo_rollout_record_dev(mech.h, _ptr(z0c), _ptr(Uc), H, _ptr(Z), _ptr(status), _ptr(DZ), _ptr(DU), _stream(dev)))
+        api._chk(api.lib().dojo_rollout_record_dev(mech.h, api.addr(z0c), api.addr(Uc), H, api.addr(Z), api.addr(status), api.addr(DZ), api.addr(DU), api.torch_stream(dev)))
         ctx.mech, ctx.H, ctx.has_u = mech, H, U is not None
         ctx.save_for_backward(z0c, Z, status, DZ, *([DU] if DU is not None else []))
         ctx.mark_non_differentiable(status)
@@ -114,7 +102,7 @@ class _Rollout(torch.autograd.Function):
         want_u = ctx.has_u and s.nu > 0 and ctx.needs_input_grad[2]
         gU = torch.empty((H, B, s.nu), dtype=Z.dtype, device=Z.device) if want_u else None
         gz = torch.empty((B, s.nx), dtype=Z.dtype, device=Z.device) if ctx.needs_input_grad[1] else None
-        api._chk(api.lib().dojo_rollout_adjoint_dev(mech.h, H, _ptr(DZ), _ptr(DU), _ptr(gZ), 1, _ptr(Z), _ptr(status), _ptr(gU), _ptr(gz), _stream(Z.device)))
+        api._chk(api.lib().dojo_rollout_adjoint_dev(mech.h, H, api.addr(DZ), api.addr(DU), api.addr(gZ), 1, api.addr(Z), api.addr(status), api.addr(gU), api.addr(gz), api.torch_stream(Z.device)))
         return None, (lift_tangent(gz, z0) if gz is not None else None), gU, None
 
 
@@ -144,7 +132,7 @@ class _DataRollout(torch.autograd.Function):
         dev = z0.device
         Z, status, DZ, DU = _record(mech, H, dev)
         DC = torch.empty((H, B, 5 * Nc, s.nx), dtype=dt, device=dev) if Nc else None
-        api._chk(api.lib().dojo_rollout_data_record_dev(mech.h, _ptr(z0c), _ptr(Uc), H, _ptr(Z), _ptr(status), _ptr(DZ), _ptr(DU), _ptr(DC), _stream(dev)))
+        api._chk(api.lib().dojo_rollout_data_record_dev(mech.h, api.addr(z0c), api.addr(Uc), H, api.addr(Z), api.addr(status), api.addr(DZ), api.addr(DU), api.addr(DC), api.torch_stream(dev)))
         ctx.mech, ctx.H, ctx.has_u, ctx.theta_device, ctx.layout = mech, H, U is not None, theta.device, (DU is not None, DC is not None)
         ctx.save_for_backward(z0c, Z, status, DZ, *[t for t in (DU, DC) if t is not None])
         ctx.mark_non_differentiable(status)
@@ -166,9 +154,9 @@ class _DataRollout(torch.autograd.Function):
         gz = torch.empty((B, s.nx), dtype=Z.dtype, device=Z.device) if need[1] else None
         gth = torch.empty((Nc, 5), dtype=Z.dtype, device=Z.device) if (need[3] and Nc) else None
         if gth is not None or gz is not None:
-            api._chk(api.lib().dojo_rollout_data_adjoint_dev(mech.h, H, _ptr(DZ), _ptr(DC), _ptr(gZ), 1, _ptr(Z), _ptr(status), None, _ptr(gth), _ptr(gz), _stream(Z.device)))
+            api._chk(api.lib().dojo_rollout_data_adjoint_dev(mech.h, H, api.addr(DZ), api.addr(DC), api.addr(gZ), 1, api.addr(Z), api.addr(status), None, api.addr(gth), api.addr(gz), api.torch_stream(Z.device)))
         if gU is not None:
-            api._chk(api.lib().dojo_rollout_adjoint_dev(mech.h, H, _ptr(DZ), _ptr(DU), _ptr(gZ), 1, _ptr(Z), _ptr(status), _ptr(gU), None, _stream(Z.device)))
+            api._chk(api.lib().dojo_rollout_adjoint_dev(mech.h, H, api.addr(DZ), api.addr(DU), api.addr(gZ), 1, api.addr(Z), api.addr(status), api.addr(gU), None, api.torch_stream(Z.device)))
         if need[3] and gth is None:
             gth = torch.zeros((0, 5), dtype=Z.dtype, device=Z.device)
         return None, (lift_tangent(gz, z0) if gz is not None else None), gU, (gth.double().to(ctx.theta_device) if need[3] else None), None
@@ -200,7 +188,7 @@ class _Affine:
         return _want(W, "W", dt, [lead + (self.na, nobs)]), _want(bias, "bias", dt, [lead + (self.na,)])
 
     def struct(self, W, mean, scale, U_ff, act_off, bias=None):
-        return api.DojoPolicy(_addr(W), _addr(bias), _addr(mean), _addr(scale), _addr(U_ff), int(self.per_env), int(act_off), self.na, 0, 0, 0)
+        return api.DojoPolicy(api.addr(W), api.addr(bias), api.addr(mean), api.addr(scale), api.addr(U_ff), int(self.per_env), int(act_off), self.na, 0, 0, 0)
 
     def record(self, h, z0, pol, H, Z, OBS, U, ACT, *rest):
         return api.lib().dojo_rollout_policy_record_dev(h, z0, pol, H, Z, OBS, U, *rest)
@@ -223,7 +211,7 @@ class _Mlp:
         return _want(theta, "theta", dt, [(B, self.P) if self.per_env else (self.P,)]),
 
     def struct(self, theta, mean, scale, U_ff, act_off):
-        return api.mlp_policy_struct(_addr(theta), _addr(mean), _addr(scale), _addr(U_ff), self.per_env, act_off, self.widths)
+        return api.mlp_policy_struct(api.addr(theta), api.addr(mean), api.addr(scale), api.addr(U_ff), self.per_env, act_off, self.widths)
 
     def record(self, h, z0, pol, H, Z, OBS, U, ACT, *rest):
         return api.lib().dojo_rollout_mlp_record_dev(h, z0, pol, H, Z, OBS, U, ACT, *rest)
@@ -246,7 +234,7 @@ class _ClosedLoopRollout(torch.autograd.Function):
         Z, status, DZ, DU, OBS, U = _record(mech, H, dev, closed_loop=True)
         ACT = None if policy.nh is None else torch.empty((H, B, policy.nh), dtype=torch.float64, device=dev)
         pol = policy.struct(params[0], mc, sc, Uc, act_off, *params[1:])
-        api._chk(policy.record(mech.h, _ptr(z0c), C.byref(pol), H, _ptr(Z), _ptr(OBS), _ptr(U), _ptr(ACT), _ptr(status), _ptr(DZ), _ptr(DU), _stream(dev)))
+        api._chk(policy.record(mech.h, api.addr(z0c), C.byref(pol), H, api.addr(Z), api.addr(OBS), api.addr(U), api.addr(ACT), api.addr(status), api.addr(DZ), api.addr(DU), api.torch_stream(dev)))
         ctx.mech, ctx.policy, ctx.H, ctx.act_off, ctx.has_uff = mech, policy, H, int(act_off), U_ff is not None
         optional = (ACT, mc, sc) + tuple(params[1:])
         ctx.has = [t is not None for t in optional]
@@ -268,9 +256,9 @@ class _ClosedLoopRollout(torch.autograd.Function):
         gU = torch.empty((H, B, s.nu), dtype=dt, device=dev) if (ctx.has_uff and need[3]) else None
         gz = torch.empty((B, s.nx), dtype=dt, device=dev) if need[2] else None
         pol = policy.struct(theta, mean, scale, None, ctx.act_off)
-        record = [_addr(status), _addr(z0), _addr(Z), None, _addr(gZ), _addr(gU_out), _addr(gOBS)]      # .., M = None: computed from z0 and Z
-        api._chk(policy.sweep(mech.h, C.byref(pol), H, _addr(DZ), _addr(DU), _addr(OBS), _addr(ACT) if ACT is not None and ACT.numel() else None,
-                              record + [_addr(g) for g in gparams + [gU, gz]], _stream(dev)))
+        record = [api.addr(status), api.addr(z0), api.addr(Z), None, api.addr(gZ), api.addr(gU_out), api.addr(gOBS)]      # .., M = None: computed from z0 and Z
+        api._chk(policy.sweep(mech.h, C.byref(pol), H, api.addr(DZ), api.addr(DU), api.addr(OBS), api.addr(ACT) if ACT is not None and ACT.numel() else None,
+                              record + [api.addr(g) for g in gparams + [gU, gz]], api.torch_stream(dev)))
         return (None, None, (lift_tangent(gz, z0) if gz is not None else None), gU, None, None, None, None) + tuple(gparams)
 
 

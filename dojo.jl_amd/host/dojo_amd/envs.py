@@ -39,10 +39,6 @@ class BatchedEnvironment:
         import torch
         return torch.cat([torch.zeros(self.batch, self.n_unactuated, dtype=self.torch_dtype, device=self.device), inp.to(self.torch_dtype)], dim=1)
 
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def initialize(self, x0=None, **kw):
         """initialize!(environment, model; kwargs...) (environments.jl:112-114): every copy at the mechanism's nominal state
         (keywords as the reference's initialize_<model>!), or at the given minimal states x0 [B, 2nu]."""
@@ -59,8 +55,8 @@ class BatchedEnvironment:
         x = self.state_map(state).to(self.torch_dtype).contiguous()
         u = self.input_map(inp).contiguous()
         xn = torch.empty_like(x)
-        api._chk(api.lib().dojo_step_minimal_dev(self.mechanism.h, C.c_void_p(x.data_ptr()), C.c_void_p(u.data_ptr()), C.c_void_p(xn.data_ptr()),
-                                                 C.c_void_p(self.status.data_ptr()), C.c_void_p(self.iters.data_ptr()), self._stream()))
+        api._chk(api.lib().dojo_step_minimal_dev(self.mechanism.h, api.addr(x), api.addr(u), api.addr(xn),
+                                                 api.addr(self.status), api.addr(self.iters), api.torch_stream(self.device)))
         self._x = xn
         self._stepped = True
         self._keep = (x, u)                                     # inputs of kernels still in flight
@@ -74,7 +70,7 @@ class BatchedEnvironment:
             obs[:, :self.nx] = self._x
             return obs
         obs = torch.empty(self.batch, self.nobs, dtype=self.torch_dtype, device=self.device)
-        api._chk(api.lib().dojo_observe_dev(self.mechanism.h, None, C.c_void_p(obs.data_ptr()), int(self.contact_forces), self._stream()))
+        api._chk(api.lib().dojo_observe_dev(self.mechanism.h, None, api.addr(obs), int(self.contact_forces), api.torch_stream(self.device)))
         return obs
 
     def rollout_policy(self, theta, horizon, mean=None, scale=None, U_ff=None):
@@ -99,14 +95,14 @@ class BatchedEnvironment:
         mean, scale, U_ff = dev(mean, (self.nobs,)), dev(scale, (self.nobs,)), dev(U_ff, (H, B, nu))
         x0 = self._x.contiguous()
         z0 = torch.empty(B, 13 * self.spec.Nb, dtype=self.torch_dtype, device=self.device)
-        L, h, ptr = api.lib(), self.mechanism.h, lambda t: None if t is None else t.data_ptr()
-        api._chk(L.dojo_minimal_to_maximal_dev(h, C.c_void_p(x0.data_ptr()), C.c_void_p(z0.data_ptr()), self._stream()))
+        L, h = api.lib(), self.mechanism.h
+        api._chk(L.dojo_minimal_to_maximal_dev(h, api.addr(x0), api.addr(z0), api.torch_stream(self.device)))
         OBS = torch.empty(H + 1, B, self.nobs, dtype=self.torch_dtype, device=self.device)
         U = torch.empty(H, B, nu, dtype=self.torch_dtype, device=self.device)
         status = torch.empty(H, B, dtype=torch.int32, device=self.device)
-        pol = api.DojoPolicy(ptr(theta), None, ptr(mean), ptr(scale), ptr(U_ff), int(per_env), self.n_unactuated, na, int(self.contact_forces), 0, 0)
-        api._chk(L.dojo_rollout_policy_dev(h, C.c_void_p(z0.data_ptr()), C.byref(pol), H, None, C.c_void_p(OBS.data_ptr()), C.c_void_p(U.data_ptr()),
-                                           C.c_void_p(status.data_ptr()), self._stream()))
+        pol = api.DojoPolicy(api.addr(theta), None, api.addr(mean), api.addr(scale), api.addr(U_ff), int(per_env), self.n_unactuated, na, int(self.contact_forces), 0, 0)
+        api._chk(L.dojo_rollout_policy_dev(h, api.addr(z0), C.byref(pol), H, None, api.addr(OBS), api.addr(U),
+                                           api.addr(status), api.torch_stream(self.device)))
         self._keep = (x0, z0, theta, mean, scale, U_ff)          # inputs of kernels still in flight
         self._stepped = True
         return OBS, U, status

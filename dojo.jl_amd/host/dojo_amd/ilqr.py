@@ -16,14 +16,6 @@ import torch
 from . import api
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _dtype(gm):
     return torch.float32 if gm.dtype_code == 1 else torch.float64
 
@@ -48,9 +40,9 @@ def linearize_rollout(gm, x0, U):
     X = torch.empty((H + 1, B, n), dtype=dt, device=dev); X[0] = x0
     A = torch.empty((H, B, n, n), dtype=dt, device=dev); Bm = torch.empty((H, B, n, nu), dtype=dt, device=dev)
     status = torch.empty((H, B), dtype=torch.int32, device=dev); iters = torch.empty(B, dtype=torch.int32, device=dev)
-    L, st = api.lib(), _stream(dev)
+    L, st = api.lib(), api.torch_stream(dev)
     for k in range(H):
-        api._chk(L.dojo_minimal_gradients_dev(gm.h, _ptr(X[k]), _ptr(U[k]), _ptr(X[k + 1]), _ptr(status[k]), _ptr(iters), _ptr(A[k]), _ptr(Bm[k]), st))
+        api._chk(L.dojo_minimal_gradients_dev(gm.h, api.addr(X[k]), api.addr(U[k]), api.addr(X[k + 1]), api.addr(status[k]), api.addr(iters), api.addr(A[k]), api.addr(Bm[k]), st))
     return X, A, Bm, status
 
 
@@ -67,9 +59,8 @@ def riccati(gm, A, Bm, lx, lu, lxx, luu, lux=None, mu=None, status=None, act_off
     K = torch.empty((H, B, na, n), dtype=dt, device=dev); kff = torch.empty((H, B, na), dtype=dt, device=dev)
     dV = torch.empty((B, 2), dtype=dt, device=dev); fail = torch.empty(B, dtype=torch.int32, device=dev)
     Vx = torch.empty((B, n), dtype=dt, device=dev) if value else None; Vxx = torch.empty((B, n, n), dtype=dt, device=dev) if value else None
-    a_ = lambda t: None if t is None else t.data_ptr()
-    r = api.DojoRiccati(a_(A), a_(Bm), a_(status), a_(lx), a_(lu), a_(lxx), a_(luu), a_(lux), a_(mu), a_(K), a_(kff), a_(fail), a_(dV), a_(Vx), a_(Vxx), int(act_off), na)
-    api._chk(api.lib().dojo_riccati_dev(gm.h, H, C.byref(r), _stream(dev)))
+    r = api.DojoRiccati(*map(api.addr, (A, Bm, status, lx, lu, lxx, luu, lux, mu, K, kff, fail, dV, Vx, Vxx)), int(act_off), na)
+    api._chk(api.lib().dojo_riccati_dev(gm.h, H, C.byref(r), api.torch_stream(dev)))
     return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
 
 
@@ -103,10 +94,10 @@ def forward_pass(gm, Xbar, Ubar, K, kff, a, act_off, na):
     X = torch.empty_like(Xbar); X[0] = Xbar[0]
     U = Ubar.clone()
     status = torch.empty((H, B), dtype=torch.int32, device=dev); iters = torch.empty(B, dtype=torch.int32, device=dev)
-    L, st = api.lib(), _stream(dev)
+    L, st = api.lib(), api.torch_stream(dev)
     for k in range(H):
         U[k, :, act_off:act_off + na] += a * kff[k] + torch.einsum("bij,bj->bi", K[k], X[k] - Xbar[k])
-        api._chk(L.dojo_step_minimal_dev(gm.h, _ptr(X[k]), _ptr(U[k]), _ptr(X[k + 1]), _ptr(status[k]), _ptr(iters), st))
+        api._chk(L.dojo_step_minimal_dev(gm.h, api.addr(X[k]), api.addr(U[k]), api.addr(X[k + 1]), api.addr(status[k]), api.addr(iters), st))
     return X, U, status
 
 
@@ -115,9 +106,9 @@ def replay(gm, x0, U):
     H, B = U.shape[:2]
     X = torch.empty((H + 1, B, x0.shape[1]), dtype=x0.dtype, device=x0.device); X[0] = x0
     status = torch.empty(B, dtype=torch.int32, device=x0.device); iters = torch.empty(B, dtype=torch.int32, device=x0.device)
-    L, st = api.lib(), _stream(x0.device)
+    L, st = api.lib(), api.torch_stream(x0.device)
     for k in range(H):
-        api._chk(L.dojo_step_minimal_dev(gm.h, _ptr(X[k]), _ptr(U[k].contiguous()), _ptr(X[k + 1]), _ptr(status), _ptr(iters), st))
+        api._chk(L.dojo_step_minimal_dev(gm.h, api.addr(X[k]), api.addr(U[k].contiguous()), api.addr(X[k + 1]), api.addr(status), api.addr(iters), st))
     return X
 
 

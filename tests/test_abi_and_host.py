@@ -7,8 +7,9 @@ import os
 import re
 import numpy as np
 import pytest
+import abi_checks
 import dojo_amd as d
-from dojo_amd import api
+from dojo_amd import api, topology
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,6 +21,31 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(api.EXPORTED_SYMBOLS)
     for s in declared:
         assert hasattr(lib, s), s
+
+
+def test_signature_table_is_the_header():
+    """every entry point is bound with the return type and, position by position, the parameter kinds of its prototype: a plain Python int given for a
+    pointer then reaches the library as a 64-bit address, and a caller that passes too few or too many arguments gets a TypeError"""
+    protos = abi_checks.header_prototypes()
+    assert len(protos) == 74 and [name for _, name, _ in protos] == api.EXPORTED_SYMBOLS
+    L = api.lib()
+    for restype, name, argtypes in protos:
+        f = getattr(L, name)
+        assert f.restype == restype, name
+        assert f.argtypes is not None and len(f.argtypes) == len(argtypes), name
+        for i, (got, want) in enumerate(zip(f.argtypes, argtypes)):
+            assert got == want, (name, i)
+
+
+MIRRORS = [("DojoPolicy", api.DojoPolicy), ("DojoPolicyAdjoint", api.DojoPolicyAdjoint), ("DojoRiccati", api.DojoRiccati), ("DojoMlpPolicy", api.DojoMlpPolicy),
+           ("DojoMlpAdjoint", api.DojoMlpAdjoint), ("DojoBody", topology.CBody), ("DojoJointHalf", topology.CJointHalf), ("DojoJoint", topology.CJoint),
+           ("DojoContact", topology.CContact), ("DojoTopology", topology.CTopology), ("DojoSolverOptions", topology.CSolverOptions), ("DojoDims", topology.CDims)]
+
+
+@pytest.mark.parametrize("struct,mirror", MIRRORS, ids=[m[0] for m in MIRRORS])
+def test_every_ctypes_mirror_has_the_layout_of_its_c_struct(struct, mirror):
+    """sizeof, the member names in the header's order, and every offsetof, as a host-only C program compiled against the header prints them"""
+    abi_checks.assert_mirror_layout(struct, mirror, abi_checks.header_struct_members(struct))
 
 
 def test_no_gpu_means_loud_failure():

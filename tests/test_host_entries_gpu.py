@@ -16,6 +16,7 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api
+from gpu_util import assert_same, dev, host
 
 pytestmark = pytest.mark.gpu
 
@@ -23,32 +24,9 @@ UNSUPPORTED = -2
 CASES = [("cartpole", 129), ("sphere", 65)]
 
 
-def _dev(a):
-    return None if a is None else torch.from_numpy(np.array(a, order="C")).cuda()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def _same(what, got, ref):
-    got, ref = np.ascontiguousarray(got), np.ascontiguousarray(ref)
-    assert got.dtype == ref.dtype and got.shape == ref.shape, (what, got.dtype, ref.dtype, got.shape, ref.shape)
-    assert got.tobytes() == ref.tobytes(), (what, int((got != ref).sum()), got.size)
-
-
 def _state(gm):
     z = np.empty((gm.batch, gm.spec.nz), gm.np_dtype)
-    api._chk(api.lib().dojo_get_state(gm.h, api._p(z)))
+    api._chk(api.lib().dojo_get_state(gm.h, api.addr(z)))
     return z
 
 
@@ -71,24 +49,24 @@ class Dev:
         zn, st, it = self.new(B, s.nz), self.ints(), self.ints()
         dz = self.new(B, s.nx, s.nx) if with_gradient else None
         du = self.new(B, max(s.nu, 1), s.nx) if with_gradient else None
-        self.keep = (_dev(z), _dev(u))                      # dojo_contact_gradients_dev re-linearizes at them
-        api._chk(self.L.dojo_step_dev(self.gm.h, _ptr(self.keep[0]), _ptr(self.keep[1]), _ptr(zn), _ptr(st), _ptr(it), _ptr(dz), _ptr(du), _stream()))
+        self.keep = (dev(z), dev(u))                      # dojo_contact_gradients_dev re-linearizes at them
+        api._chk(self.L.dojo_step_dev(self.gm.h, api.addr(self.keep[0]), api.addr(self.keep[1]), api.addr(zn), api.addr(st), api.addr(it), api.addr(dz), api.addr(du), api.torch_stream()))
         self.zn = zn
         return zn, st, it, dz, du
 
     def contact_gradients(self):
         dc = self.new(self.B, 5 * len(self.s.contacts), self.s.nx)
-        api._chk(self.L.dojo_contact_gradients_dev(self.gm.h, _ptr(self.keep[0]), _ptr(self.keep[1]), _ptr(dc), _stream()))
+        api._chk(self.L.dojo_contact_gradients_dev(self.gm.h, api.addr(self.keep[0]), api.addr(self.keep[1]), api.addr(dc), api.torch_stream()))
         return dc
 
     def step_impulses(self, z, jf):
         """what dojo_step_impulses does: the impulses, divided by the time step in fp64, in the external-force slot of a step without controls"""
         s, B = self.s, self.B
-        folded = (torch.zeros(B, 6 * s.Nb, dtype=torch.float64, device="cuda") + _dev(jf).double() * (1.0 / s.timestep)).to(self.tdt)
+        folded = (torch.zeros(B, 6 * s.Nb, dtype=torch.float64, device="cuda") + dev(jf).double() * (1.0 / s.timestep)).to(self.tdt)
         zn, st, it = self.new(B, s.nz), self.ints(), self.ints()
-        zd = _dev(z)
-        api._chk(self.L.dojo_set_external_force_dev(self.gm.h, _ptr(folded)))
-        api._chk(self.L.dojo_step_dev(self.gm.h, _ptr(zd), None, _ptr(zn), _ptr(st), _ptr(it), None, None, _stream()))
+        zd = dev(z)
+        api._chk(self.L.dojo_set_external_force_dev(self.gm.h, api.addr(folded)))
+        api._chk(self.L.dojo_step_dev(self.gm.h, api.addr(zd), None, api.addr(zn), api.addr(st), api.addr(it), None, None, api.torch_stream()))
         torch.cuda.synchronize()
         api._chk(self.L.dojo_set_external_force_dev(self.gm.h, None))
         self.zn = zn
@@ -97,46 +75,46 @@ class Dev:
     def coords(self, a, to_max):
         out = self.new(self.B, self.s.nz if to_max else 2 * self.s.nu)
         f = self.L.dojo_minimal_to_maximal_dev if to_max else self.L.dojo_maximal_to_minimal_dev
-        ad = _dev(a)
-        api._chk(f(self.gm.h, _ptr(ad), _ptr(out), _stream()))
+        ad = dev(a)
+        api._chk(f(self.gm.h, api.addr(ad), api.addr(out), api.torch_stream()))
         torch.cuda.synchronize()
         return out
 
     def step_minimal(self, x, u, jac):
         s, B, nm = self.s, self.B, 2 * self.s.nu
         xn, st, it = self.new(B, nm), self.ints(), self.ints()
-        xd, ud = _dev(x), _dev(u)
+        xd, ud = dev(x), dev(u)
         if not jac:
-            api._chk(self.L.dojo_step_minimal_dev(self.gm.h, _ptr(xd), _ptr(ud), _ptr(xn), _ptr(st), _ptr(it), _stream()))
+            api._chk(self.L.dojo_step_minimal_dev(self.gm.h, api.addr(xd), api.addr(ud), api.addr(xn), api.addr(st), api.addr(it), api.torch_stream()))
             torch.cuda.synchronize()
             return xn, st, it
         jx, ju = self.new(B, nm, nm), self.new(B, nm, s.nu)
-        api._chk(self.L.dojo_minimal_gradients_dev(self.gm.h, _ptr(xd), _ptr(ud), _ptr(xn), _ptr(st), _ptr(it), _ptr(jx), _ptr(ju), _stream()))
+        api._chk(self.L.dojo_minimal_gradients_dev(self.gm.h, api.addr(xd), api.addr(ud), api.addr(xn), api.addr(st), api.addr(it), api.addr(jx), api.addr(ju), api.torch_stream()))
         torch.cuda.synchronize()
         return xn, st, it, jx, ju
 
     def observe(self, contact_forces):
         obs = self.new(self.B, 2 * self.s.nu + (len(self.s.contacts) if contact_forces else 0))
-        api._chk(self.L.dojo_observe_dev(self.gm.h, _ptr(self.zn), _ptr(obs), int(contact_forces), _stream()))
+        api._chk(self.L.dojo_observe_dev(self.gm.h, api.addr(self.zn), api.addr(obs), int(contact_forces), api.torch_stream()))
         return obs
 
     def next_state(self, z):
-        zo, zd = self.new(self.B, self.s.nz), _dev(z)
-        api._chk(self.L.dojo_next_state_dev(self.gm.h, _ptr(zd), _ptr(zo), _stream()))
+        zo, zd = self.new(self.B, self.s.nz), dev(z)
+        api._chk(self.L.dojo_next_state_dev(self.gm.h, api.addr(zd), api.addr(zo), api.torch_stream()))
         torch.cuda.synchronize()
         return zo
 
     def observation_jacobian(self, z):
-        M, zd = self.new(self.B, 2 * self.s.nu, 24, dtype=torch.float64), _dev(z)
-        api._chk(self.L.dojo_observation_jacobian_dev(self.gm.h, _ptr(zd), 1, _ptr(M), _stream()))
+        M, zd = self.new(self.B, 2 * self.s.nu, 24, dtype=torch.float64), dev(z)
+        api._chk(self.L.dojo_observation_jacobian_dev(self.gm.h, api.addr(zd), 1, api.addr(M), api.torch_stream()))
         torch.cuda.synchronize()
         return M
 
     def simulate(self, z0, U):
         H, s, B = U.shape[0], self.s, self.B
         Z, S, st = self.new(H, B, s.nz), self.new(H, B, s.Nb, 25), torch.full((H, B), -77, dtype=torch.int32, device="cuda")
-        zd, Ud = _dev(z0), _dev(U)
-        api._chk(self.L.dojo_simulate_dev(self.gm.h, _ptr(zd), _ptr(Ud), H, _ptr(Z), _ptr(S), _ptr(st), _stream()))
+        zd, Ud = dev(z0), dev(U)
+        api._chk(self.L.dojo_simulate_dev(self.gm.h, api.addr(zd), api.addr(Ud), H, api.addr(Z), api.addr(S), api.addr(st), api.torch_stream()))
         torch.cuda.synchronize()
         return Z, S, st
 
@@ -157,51 +135,82 @@ def test_host_entries_equal_the_device_entries(name, B, dtype):
         zn, st, it = gh.step(Z, U, with_gradient=True)
         dzn, dst, dit, ddz, ddu = dev.step(Z, U, True)
         assert (st == 0).any() and np.isfinite(zn[st == 0]).all()
-        _same("step z_next", zn, _host(dzn)); _same("step status", st, _host(dst)); _same("step iters", it, _host(dit))
-        _same("step get_state", _state(gh), zn)
+        assert_same("step z_next", zn, host(dzn)); assert_same("step status", st, host(dst)); assert_same("step iters", it, host(dit))
+        assert_same("step get_state", _state(gh), zn)
         dz, du = gh.gradients()
-        _same("gradients dz", dz, _host(ddz).transpose(0, 2, 1)); _same("gradients du", du, _host(ddu)[:, :spec.nu].transpose(0, 2, 1))
+        assert_same("gradients dz", dz, host(ddz).transpose(0, 2, 1)); assert_same("gradients du", du, host(ddu)[:, :spec.nu].transpose(0, 2, 1))
         if Nc:
-            _same("contact_gradients", gh.contact_gradients(), _host(dev.contact_gradients()).transpose(0, 2, 1))
-        _same("contact_gradients get_state", _state(gh), zn)
+            assert_same("contact_gradients", gh.contact_gradients(), host(dev.contact_gradients()).transpose(0, 2, 1))
+        assert_same("contact_gradients get_state", _state(gh), zn)
         # dojo_observe reads the state and the impulses that step left on the handle
         for cf in (False, True):
-            _same("observe %d" % cf, gh.observe(cf), _host(dev.observe(cf)))
-        _same("observe get_state", _state(gh), zn)
+            assert_same("observe %d" % cf, gh.observe(cf), host(dev.observe(cf)))
+        assert_same("observe get_state", _state(gh), zn)
         # the entries that work on the caller's arrays alone
-        _same("next_state", gh.next_state(zn), _host(dev.next_state(zn)))
-        _same("observation_jacobian", gh.observation_jacobian(zn), _host(dev.observation_jacobian(zn)))
+        assert_same("next_state", gh.next_state(zn), host(dev.next_state(zn)))
+        assert_same("observation_jacobian", gh.observation_jacobian(zn), host(dev.observation_jacobian(zn)))
         X = gh.maximal_to_minimal(Z)
-        _same("maximal_to_minimal", X, _host(dev.coords(Z, False)))
-        _same("minimal_to_maximal", gh.minimal_to_maximal(X), _host(dev.coords(X, True)))
-        _same("coordinate entries get_state", _state(gh), zn)
+        assert_same("maximal_to_minimal", X, host(dev.coords(Z, False)))
+        assert_same("minimal_to_maximal", gh.minimal_to_maximal(X), host(dev.coords(X, True)))
+        assert_same("coordinate entries get_state", _state(gh), zn)
         # dojo_step_impulses
         jf = (0.01 * np.random.default_rng(5).standard_normal((B, 6 * spec.Nb))).astype(gh.np_dtype)
         zi, st, it = gh.step_impulses(zn, jf)
         dzi, dst, dit = dev.step_impulses(zn, jf)
-        _same("step_impulses z_next", zi, _host(dzi)); _same("step_impulses status", st, _host(dst)); _same("step_impulses iters", it, _host(dit))
-        _same("step_impulses get_state", _state(gh), zi)
+        assert_same("step_impulses z_next", zi, host(dzi)); assert_same("step_impulses status", st, host(dst)); assert_same("step_impulses iters", it, host(dit))
+        assert_same("step_impulses get_state", _state(gh), zi)
         # dojo_step_minimal, dojo_minimal_gradients in both modes: the device entries leave the maximal state on the handle as well
         xn, st, it = gh.step_minimal(X, U)
         dxn, dst, dit = dev.step_minimal(X, U, False)
-        _same("step_minimal x_next", xn, _host(dxn)); _same("step_minimal status", st, _host(dst)); _same("step_minimal iters", it, _host(dit))
-        _same("step_minimal get_state", _state(gh), _state(gd))
+        assert_same("step_minimal x_next", xn, host(dxn)); assert_same("step_minimal status", st, host(dst)); assert_same("step_minimal iters", it, host(dit))
+        assert_same("step_minimal get_state", _state(gh), _state(gd))
         for mode in (0, 1):
             gh.set_gradient_mode(mode); gd.set_gradient_mode(mode)
             xn, st, it, jx, ju = gh.minimal_gradients(X, U)
             dxn, dst, dit, djx, dju = dev.step_minimal(X, U, True)
             for what, a, b in (("x_next", xn, dxn), ("status", st, dst), ("iters", it, dit), ("jx", jx, djx), ("ju", ju, dju)):
-                _same("minimal_gradients mode %d %s" % (mode, what), a, _host(b))
-            _same("minimal_gradients get_state", _state(gh), _state(gd))
+                assert_same("minimal_gradients mode %d %s" % (mode, what), a, host(b))
+            assert_same("minimal_gradients get_state", _state(gh), _state(gd))
             assert np.isfinite(jx[st == 0]).all() and np.isfinite(ju[st == 0]).all()
         # dojo_simulate: states, Storage rows and status of two steps
         Us = np.stack([U, -U])
         Zs, S, sts = gh.simulate(Z, Us)
         dZs, dS, dsts = dev.simulate(Z, Us)
-        _same("simulate Z", Zs, _host(dZs)); _same("simulate storage", S, _host(dS)); _same("simulate status", sts, _host(dsts))
-        _same("simulate get_state", _state(gh), Zs[-1])
+        assert_same("simulate Z", Zs, host(dZs)); assert_same("simulate storage", S, host(dS)); assert_same("simulate status", sts, host(dsts))
+        assert_same("simulate get_state", _state(gh), Zs[-1])
     finally:
         gh.close(); gd.close()
+
+
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_plain_integer_addresses(dtype):
+    """the handle, every pointer and the stream given as plain Python ints reach the library as the 64-bit values they are: three `_dev` entries write bit for
+    bit what they write for the same values wrapped in c_void_p (without argtypes ctypes would pass an int as a 32-bit C int)"""
+    spec, B, H = d.get_mechanism("cartpole"), 3, 2
+    L = api.lib()
+    entries = (L.dojo_maximal_to_minimal_dev, L.dojo_next_state_dev, L.dojo_rollout_record_dev)
+    assert all(f.argtypes and all(t is not None for t in f.argtypes) for f in entries)
+    Z0, U0 = d.synthetic_inputs(spec, B)
+    gm = api.BatchedMechanism(spec, B, dtype=dtype)
+    try:
+        tdt = torch.float32 if gm.dtype_code else torch.float64
+        z, U = dev(Z0, tdt), dev(np.stack([U0, -U0]), tdt)
+        nan = lambda *shape: torch.full(shape, float("nan"), dtype=tdt, device="cuda")
+        outs = []
+        for wrap in (int, C.c_void_p):
+            a = lambda t: wrap(t.data_ptr())
+            h, stream = wrap(gm.h.value), wrap(api.torch_stream())
+            x, zo, Z, DZ, DU = nan(B, 2 * spec.nu), nan(B, spec.nz), nan(H, B, spec.nz), nan(H, B, spec.nx, spec.nx), nan(H, B, spec.nu, spec.nx)
+            st = torch.full((H, B), -77, dtype=torch.int32, device="cuda")
+            api._chk(L.dojo_maximal_to_minimal_dev(h, a(z), a(x), stream))
+            api._chk(L.dojo_next_state_dev(h, a(z), a(zo), stream))
+            api._chk(L.dojo_rollout_record_dev(h, a(z), a(U), H, a(Z), a(st), a(DZ), a(DU), stream))
+            outs.append([host(t) for t in (x, zo, Z, st, DZ, DU)])
+        assert np.isfinite(outs[0][0]).all() and np.isfinite(outs[0][1]).all() and (outs[0][3] == 0).any()      # the entries ran and wrote
+        for what, got, ref in zip(("x", "z_out", "Z", "status", "DZ", "DU"), *outs):
+            assert_same(what, got, ref)
+    finally:
+        gm.close()
 
 
 # the texts are the literals of the entries' source
@@ -221,7 +230,7 @@ def test_loop_refusals():
     try:
         buf = torch.zeros(4096, dtype=torch.float64, device="cuda"); ibuf = torch.zeros(16, dtype=torch.int32, device="cuda")
         hbuf = np.zeros(4096)
-        p, ip, st = _ptr(buf), _ptr(ibuf), _stream()
+        p, ip, st = api.addr(buf), api.addr(ibuf), api.torch_stream()
         pol = api.DojoPolicy(buf.data_ptr(), None, None, None, None, 1, 0, 1, 0, 0, 0)
         mlp = api.mlp_policy_struct(buf.data_ptr(), None, None, None, 1, 0, [2 * spec.nu, 1])
         ric = api.DojoRiccati()
@@ -232,7 +241,7 @@ def test_loop_refusals():
                  "dojo_rollout_mlp_dev": lambda: L.dojo_rollout_mlp_dev(gm.h, p, C.byref(mlp), 1, p, p, p, None, ip, st),
                  "dojo_riccati_dev": lambda: L.dojo_riccati_dev(gm.h, 1, C.byref(ric), st),
                  "dojo_observation_jacobian_dev": lambda: L.dojo_observation_jacobian_dev(gm.h, p, 1, p, st),
-                 "dojo_observation_jacobian": lambda: L.dojo_observation_jacobian(gm.h, api._p(hbuf), api._p(hbuf)),
+                 "dojo_observation_jacobian": lambda: L.dojo_observation_jacobian(gm.h, api.addr(hbuf), api.addr(hbuf)),
                  "dojo_minimal_to_maximal_dev": lambda: L.dojo_minimal_to_maximal_dev(gm.h, p, p, st),
                  "dojo_maximal_to_minimal_dev": lambda: L.dojo_maximal_to_minimal_dev(gm.h, p, p, st),
                  "dojo_observe_dev": lambda: L.dojo_observe_dev(gm.h, p, p, 0, st),

@@ -27,6 +27,7 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api, coords
+from gpu_util import dev, same, tdt_of
 
 pytestmark = pytest.mark.gpu
 
@@ -69,42 +70,17 @@ def teardown_module(module):
     _handles.clear()
 
 
-def _dev(a):
-    return None if a is None else torch.from_numpy(np.array(a, order="C")).cuda()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _dp(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def same(a, b):
-    """bit for bit (NaN-safe)"""
-    return a.shape == b.shape and a.dtype == b.dtype and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
-
-def _tdt(gm):
-    return torch.float32 if gm.dtype_code else torch.float64
-
-
 def sweep_raw(gm, H, t, per_env, act_off, na, cot_space=0, contact_forces=0):
     """dojo_rollout_policy_adjoint_dev on a dict of torch tensors (missing / None = NULL) -> return code"""
-    g = lambda k: _dp(t.get(k))
+    g = lambda k: api.addr(t.get(k))
     pol = api.DojoPolicy(g("W"), None, g("mean"), g("scale"), None, int(per_env), int(act_off), int(na), int(contact_forces), 0, 0)
     a = api.DojoPolicyAdjoint(g("DZ"), g("DU"), g("OBS"), g("status"), g("z0"), g("Z"), g("M"), g("G"), g("G_u"), g("G_obs"),
                               g("gW"), g("gbias"), g("gU"), g("gz"), int(cot_space), 0)
-    return api.lib().dojo_rollout_policy_adjoint_dev(gm.h, C.byref(pol), int(H), C.byref(a), _stream())
+    return api.lib().dojo_rollout_policy_adjoint_dev(gm.h, C.byref(pol), int(H), C.byref(a), api.torch_stream())
 
 
 def out_tensors(gm, H, per_env, na, fill=float("nan")):
-    s, B, tdt = gm.spec, gm.batch, _tdt(gm)
+    s, B, tdt = gm.spec, gm.batch, tdt_of(gm)
     nobs = 2 * s.nu
     f = lambda shape: torch.full(shape, fill, dtype=tdt, device="cuda")
     return {"gW": f((B, na, nobs) if per_env else (na, nobs)), "gbias": f((B, na) if per_env else (na,)), "gU": f((H, B, s.nu)), "gz": f((B, s.nx))}
@@ -113,7 +89,7 @@ def out_tensors(gm, H, per_env, na, fill=float("nan")):
 def sweep(gm, H, inp, per_env, act_off, na, cot_space=0, outs=None):
     """NumPy in, NumPy out (dict over OUTS); the outputs start as NaN so that an entry the kernels leave out shows.
     outs: the caller's own device tensors instead (a missing key = NULL, and missing from the result)"""
-    t = {k: _dev(v) for k, v in inp.items()}
+    t = {k: dev(v) for k, v in inp.items()}
     t.update(out_tensors(gm, H, per_env, na) if outs is None else outs)
     api._chk(sweep_raw(gm, H, t, per_env, act_off, na, cot_space))
     torch.cuda.synchronize()
@@ -290,9 +266,9 @@ def test_zero_policy_is_the_open_loop_sweep(dtype):
     gm = _handle("ant", dtype, B); s = gm.spec; act_off, na = ACT["ant"]
     inp = dict(synthetic("ant", dtype, H, B)); inp["W"] = np.zeros_like(inp["W"]); inp["G_u"] = None; inp["G_obs"] = None
     out = sweep(gm, H, inp, 1, act_off, na)
-    gU = torch.full((H, B, s.nu), float("nan"), dtype=_tdt(gm), device="cuda"); gz = torch.full((B, s.nx), float("nan"), dtype=_tdt(gm), device="cuda")
-    keep = [_dev(inp[k]) for k in ("DZ", "DU", "G")]
-    api._chk(api.lib().dojo_rollout_adjoint_dev(gm.h, H, _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), 0, None, None, _ptr(gU), _ptr(gz), _stream()))
+    gU = torch.full((H, B, s.nu), float("nan"), dtype=tdt_of(gm), device="cuda"); gz = torch.full((B, s.nx), float("nan"), dtype=tdt_of(gm), device="cuda")
+    keep = [dev(inp[k]) for k in ("DZ", "DU", "G")]
+    api._chk(api.lib().dojo_rollout_adjoint_dev(gm.h, H, api.addr(keep[0]), api.addr(keep[1]), api.addr(keep[2]), 0, None, None, api.addr(gU), api.addr(gz), api.torch_stream()))
     torch.cuda.synchronize()
     abs_ = recursion(s, absolute(inp), act_off, na, absolute=True)
     n_step = s.nx + 2 * s.nu + na + 8
@@ -303,9 +279,9 @@ def test_zero_policy_is_the_open_loop_sweep(dtype):
 def observation_jacobian_dev(gm, z):
     """dojo_observation_jacobian_dev on z [n,B,13Nb] -> compact [n,B,2nu,24]; starts as NaN"""
     n = z.shape[0]
-    zd = _dev(np.asarray(z, gm.np_dtype))
+    zd = dev(np.asarray(z, gm.np_dtype))
     M = torch.full((n, gm.batch, 2 * gm.spec.nu, 24), float("nan"), dtype=torch.float64, device="cuda")
-    api._chk(api.lib().dojo_observation_jacobian_dev(gm.h, _ptr(zd), n, _ptr(M), _stream()))
+    api._chk(api.lib().dojo_observation_jacobian_dev(gm.h, api.addr(zd), n, api.addr(M), api.torch_stream()))
     torch.cuda.synchronize()
     return M.cpu().numpy()
 
@@ -349,17 +325,17 @@ def ant_record(B, H=4):
         p = dict(z0=d.synthetic_inputs(s, B)[0], W=0.1 * rng.standard_normal((B, na, nobs)), bias=0.1 * rng.standard_normal((B, na)),
                  mean=0.1 * rng.standard_normal(nobs), scale=rng.uniform(0.5, 1.5, nobs), U_ff=np.zeros((H, B, s.nu)))
         p["U_ff"][:, :, act_off:act_off + na] = 0.2 * rng.standard_normal((H, B, na))
-        t = {k: _dev(v) for k, v in p.items()}
+        t = {k: dev(v) for k, v in p.items()}
         pol = api.DojoPolicy(*[t[k].data_ptr() for k in ("W", "bias", "mean", "scale", "U_ff")], 1, act_off, na, 0, 0, 0)
         f = lambda shape, dt=torch.float64: torch.full(shape, float("nan") if dt == torch.float64 else -123456, dtype=dt, device="cuda")
         L = api.lib()
         a = dict(Z=f((H, B, s.nz)), OBS=f((H + 1, B, nobs)), U=f((H, B, s.nu)), S=f((H, B), torch.int32))
-        api._chk(L.dojo_rollout_policy_dev(gm.h, _ptr(t["z0"]), C.byref(pol), H, _ptr(a["Z"]), _ptr(a["OBS"]), _ptr(a["U"]), _ptr(a["S"]), _stream()))
+        api._chk(L.dojo_rollout_policy_dev(gm.h, api.addr(t["z0"]), C.byref(pol), H, api.addr(a["Z"]), api.addr(a["OBS"]), api.addr(a["U"]), api.addr(a["S"]), api.torch_stream()))
         r = dict(Z=f((H, B, s.nz)), OBS=f((H + 1, B, nobs)), U=f((H, B, s.nu)), S=f((H, B), torch.int32), DZ=f((H, B, s.nx, s.nx)), DU=f((H, B, s.nu, s.nx)))
-        api._chk(L.dojo_rollout_policy_record_dev(gm.h, _ptr(t["z0"]), C.byref(pol), H, _ptr(r["Z"]), _ptr(r["OBS"]), _ptr(r["U"]), _ptr(r["S"]),
-                                                  _ptr(r["DZ"]), _ptr(r["DU"]), _stream()))
+        api._chk(L.dojo_rollout_policy_record_dev(gm.h, api.addr(t["z0"]), C.byref(pol), H, api.addr(r["Z"]), api.addr(r["OBS"]), api.addr(r["U"]), api.addr(r["S"]),
+                                                  api.addr(r["DZ"]), api.addr(r["DU"]), api.torch_stream()))
         o = dict(Z=f((H, B, s.nz)), S=f((H, B), torch.int32), DZ=f((H, B, s.nx, s.nx)), DU=f((H, B, s.nu, s.nx)))
-        api._chk(L.dojo_rollout_record_dev(gm.h, _ptr(t["z0"]), _ptr(r["U"]), H, _ptr(o["Z"]), _ptr(o["S"]), _ptr(o["DZ"]), _ptr(o["DU"]), _stream()))
+        api._chk(L.dojo_rollout_record_dev(gm.h, api.addr(t["z0"]), api.addr(r["U"]), H, api.addr(o["Z"]), api.addr(o["S"]), api.addr(o["DZ"]), api.addr(o["DU"]), api.torch_stream()))
         torch.cuda.synchronize()
         _records[B] = (p, {k: v.cpu().numpy() for k, v in a.items()}, {k: v.cpu().numpy() for k, v in r.items()}, {k: v.cpu().numpy() for k, v in o.items()})
     return _records[B]
@@ -486,12 +462,12 @@ def test_shared_policy_is_the_sum_over_the_batch():
     assert sh[4].shape == (na, 2 * spec.nu) and sh[5].shape == (na,)
     # abs_: the recursion on the magnitudes of the record the sweep saw
     Z, OBS, st = pe[0], pe[1], pe[3]
-    t = {k: _dev(v) for k, v in dict(z0=z0, W=np.tile(W1, (B, 1, 1)), bias=kB["bias"], mean=kw["mean"], scale=kw["scale"], U_ff=kw["U_ff"]).items()}
+    t = {k: dev(v) for k, v in dict(z0=z0, W=np.tile(W1, (B, 1, 1)), bias=kB["bias"], mean=kw["mean"], scale=kw["scale"], U_ff=kw["U_ff"]).items()}
     pol = api.DojoPolicy(*[t[k].data_ptr() for k in ("W", "bias", "mean", "scale", "U_ff")], 1, act_off, na, 0, 0, 0)
     f = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device="cuda")
     r = dict(Z=f((H, B, spec.nz)), OBS=f((H + 1, B, 2 * spec.nu)), U=f((H, B, spec.nu)), S=f((H, B), torch.int32), DZ=f((H, B, spec.nx, spec.nx)), DU=f((H, B, spec.nu, spec.nx)))
-    api._chk(api.lib().dojo_rollout_policy_record_dev(gm.h, _ptr(t["z0"]), C.byref(pol), H, _ptr(r["Z"]), _ptr(r["OBS"]), _ptr(r["U"]), _ptr(r["S"]),
-                                                      _ptr(r["DZ"]), _ptr(r["DU"]), _stream()))
+    api._chk(api.lib().dojo_rollout_policy_record_dev(gm.h, api.addr(t["z0"]), C.byref(pol), H, api.addr(r["Z"]), api.addr(r["OBS"]), api.addr(r["U"]), api.addr(r["S"]),
+                                                      api.addr(r["DZ"]), api.addr(r["DU"]), api.torch_stream()))
     torch.cuda.synchronize()
     r = {k: v.cpu().numpy() for k, v in r.items()}
     assert same(r["Z"], Z) and (r["S"] == 0).all()
@@ -528,10 +504,10 @@ def test_autograd_wrapper():
     z0, W, A, Bc, Cc = f(z0), f(W), f(A), f(Bc), f(Cc); kw = {k: f(v) for k, v in kw.items()}
     gm = _handle("cartpole", "f32", B)
     Zh, Oh, Uh, sh, gW, gb, gU, gz = gm.rollout_policy_gradients(z0, W, A, act_off=act_off, G_u=Bc, G_obs=Cc, cot_space="state", **kw)
-    zt, Wt, bt, Ut = (_dev(a).requires_grad_(True) for a in (z0, W, kw["bias"], kw["U_ff"]))
-    Z, OBS, U = differentiable_policy_rollout(gm, zt, Wt, bias=bt, U_ff=Ut, mean=_dev(kw["mean"]), scale=_dev(kw["scale"]), act_off=act_off)
+    zt, Wt, bt, Ut = (dev(a).requires_grad_(True) for a in (z0, W, kw["bias"], kw["U_ff"]))
+    Z, OBS, U = differentiable_policy_rollout(gm, zt, Wt, bias=bt, U_ff=Ut, mean=dev(kw["mean"]), scale=dev(kw["scale"]), act_off=act_off)
     assert Z.status.dtype == torch.int32 and not Z.status.requires_grad
-    loss = (Z * _dev(A)).sum() + (U * _dev(Bc)).sum() + (OBS * _dev(Cc)).sum()
+    loss = (Z * dev(A)).sum() + (U * dev(Bc)).sum() + (OBS * dev(Cc)).sum()
     gzt, gWt, gbt, gUt = torch.autograd.grad(loss, [zt, Wt, bt, Ut])
     torch.cuda.synchronize()
     assert same(Z.detach().cpu().numpy(), Zh) and same(OBS.detach().cpu().numpy(), Oh) and same(U.detach().cpu().numpy(), Uh) and same(Z.status.cpu().numpy(), sh)
@@ -548,7 +524,7 @@ def test_argument_errors():
     H, B = 2, 3
     gm = _handle("cartpole", "f64", B); s = gm.spec; act_off, na = ACT["cartpole"]
     who = "dojo_rollout_policy_adjoint_dev"
-    t = {k: _dev(v) for k, v in synthetic("cartpole", "f64", H, B).items()}
+    t = {k: dev(v) for k, v in synthetic("cartpole", "f64", H, B).items()}
     t["M"] = torch.nan_to_num(t["M"])
     t["Z"] = torch.zeros((H, B, s.nz), dtype=torch.float64, device="cuda"); t["z0"] = torch.zeros((B, s.nz), dtype=torch.float64, device="cuda")
     outs = out_tensors(gm, H, 1, na, fill=77.0)
@@ -586,7 +562,7 @@ def test_argument_errors():
     assert sweep_raw(g0, H, t0, 1, 0, 1) == INVALID and who in g0.last_error() and "no inputs" in g0.last_error()
     assert (t0["gz"] == 77.0).all()
     Mz = torch.full((B, 1, 24), 77.0, dtype=torch.float64, device="cuda")
-    assert api.lib().dojo_observation_jacobian_dev(g0.h, _ptr(z), 1, _ptr(Mz), _stream()) == INVALID and "dojo_observation_jacobian_dev" in g0.last_error()
+    assert api.lib().dojo_observation_jacobian_dev(g0.h, api.addr(z), 1, api.addr(Mz), api.torch_stream()) == INVALID and "dojo_observation_jacobian_dev" in g0.last_error()
     assert (Mz == 77.0).all()
     # the record entry on a mechanism without gradients
     spec = _spec("sphere_linear")
@@ -596,9 +572,9 @@ def test_argument_errors():
         f = lambda shape, dt=torch.float64: torch.full(shape, 77, dtype=dt, device="cuda")
         W = torch.zeros((spec.nu, nobs), dtype=torch.float64, device="cuda")
         pol = api.DojoPolicy(W.data_ptr(), None, None, None, None, 0, 0, spec.nu, 0, 0, 0)
-        z0 = _dev(np.tile(d.initialize(spec), (4, 1)))
+        z0 = dev(np.tile(d.initialize(spec), (4, 1)))
         r = dict(Z=f((2, 4, spec.nz)), OBS=f((3, 4, nobs)), U=f((2, 4, spec.nu)), S=f((2, 4), torch.int32), DZ=f((2, 4, spec.nx, spec.nx)), DU=f((2, 4, spec.nu, spec.nx)))
-        rc = api.lib().dojo_rollout_policy_record_dev(gs.h, _ptr(z0), C.byref(pol), 2, _ptr(r["Z"]), _ptr(r["OBS"]), _ptr(r["U"]), _ptr(r["S"]), _ptr(r["DZ"]), _ptr(r["DU"]), _stream())
+        rc = api.lib().dojo_rollout_policy_record_dev(gs.h, api.addr(z0), C.byref(pol), 2, api.addr(r["Z"]), api.addr(r["OBS"]), api.addr(r["U"]), api.addr(r["S"]), api.addr(r["DZ"]), api.addr(r["DU"]), api.torch_stream())
         torch.cuda.synchronize()
         assert rc == UNSUPPORTED and "dojo_rollout_policy_record_dev" in gs.last_error() and "LinearContact" in gs.last_error(), gs.last_error()
         for k, v in r.items():

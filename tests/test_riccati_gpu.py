@@ -11,13 +11,13 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api
+from gpu_util import dev, guarded, guards_intact, tdt_of
 
 import riccati_cases as RC
 
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = -1, -2
-GUARD, SENTINEL = 64, 77.0
 _handles = {}
 
 
@@ -45,36 +45,11 @@ def teardown_module(module):
     _handles.clear()
 
 
-def tdt_of(gm):
-    return torch.float32 if gm.dtype_code else torch.float64
-
-
-def guarded(shape, tdt):
-    """an output that starts as NaN (int32: -77), with GUARD elements of SENTINEL in front of it and behind it"""
-    n = int(np.prod(shape))
-    flat = torch.full((n + 2 * GUARD,), SENTINEL, dtype=tdt, device="cuda")
-    flat[GUARD:GUARD + n] = -77 if tdt == torch.int32 else float("nan")
-    return flat[GUARD:GUARD + n].view(tuple(shape))
-
-
-def guards_intact(t):
-    flat, n = t._base, t.numel()
-    return bool((flat[:GUARD] == SENTINEL).all() and (flat[GUARD + n:] == SENTINEL).all())
-
-
-def _dev(a, tdt):
-    return None if a is None else torch.from_numpy(np.array(a, order="C")).to(tdt).cuda()
-
-
-def _addr(t):
-    return None if t is None else t.data_ptr()
-
-
 def launch(gm, H, dev_in, outs, act_off, m):
     """dojo_riccati_dev on torch tensors (None = NULL) -> return code"""
-    r = api.DojoRiccati(*[_addr(dev_in.get(k)) for k in ("A", "Bm", "status", "lx", "lu", "lxx", "luu", "lux", "mu")],
-                        *[_addr(outs.get(k)) for k in ("K", "kff", "fail", "dV", "Vx", "Vxx")], int(act_off), int(m))
-    return api.lib().dojo_riccati_dev(gm.h, int(H), C.byref(r), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    r = api.DojoRiccati(*[api.addr(dev_in.get(k)) for k in ("A", "Bm", "status", "lx", "lu", "lxx", "luu", "lux", "mu")],
+                        *[api.addr(outs.get(k)) for k in ("K", "kff", "fail", "dV", "Vx", "Vxx")], int(act_off), int(m))
+    return api.lib().dojo_riccati_dev(gm.h, int(H), C.byref(r), api.torch_stream())
 
 
 def outputs(gm, H, m, omit=()):
@@ -87,8 +62,8 @@ def run(gm, inp, act_off, m, mu=None, status=None, omit=(), raw=False):
     """NumPy in (inp: the dict of riccati_cases.inputs; lux may be None) -> dict of NumPy outputs (raw: device tensors).  Every output starts as NaN between guard
     elements, which must come back untouched; every element must have been written."""
     H, tdt = inp["A"].shape[0], tdt_of(gm)
-    dev_in = {k: _dev(v, tdt) for k, v in inp.items()}
-    dev_in["mu"] = _dev(mu, tdt); dev_in["status"] = _dev(status, torch.int32)
+    dev_in = {k: dev(v, tdt) for k, v in inp.items()}
+    dev_in["mu"] = dev(mu, tdt); dev_in["status"] = dev(status, torch.int32)
     outs = outputs(gm, H, m, omit)
     api._chk(launch(gm, H, dev_in, outs, act_off, m))
     torch.cuda.synchronize()
@@ -261,7 +236,7 @@ def test_refusals_with_their_text():
     name, n, nu, act_off, m = RC.SHAPES["cartpole1"]
     H, B = 3, 5
     gm = handle(name, "f64", B)
-    dev_in = {k: _dev(v, torch.float64) for k, v in RC.inputs("cartpole1", H, B).items()}
+    dev_in = {k: dev(v, torch.float64) for k, v in RC.inputs("cartpole1", H, B).items()}
     outs = outputs(gm, H, m)
     refused(gm, 0, dev_in, outs, act_off, m, INVALID, "dojo_riccati_dev: H must be >= 1")
     for k in ("A", "Bm", "lx", "lu", "lxx", "luu"):

@@ -1,35 +1,27 @@
 """Reverse-mode rollouts at the ABI (CPU tier): the three entry points are declared in include/dojo_hip.h, listed in
 api.EXPORTED_SYMBOLS, exported by the built library, and the Julia shim names the host-pointer one."""
-import ctypes
-import os
-import re
-
+import abi_checks
 from dojo_amd import api
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dojo_rollout_record_dev", "dojo_rollout_adjoint_dev", "dojo_rollout_gradients")
 
 
 def test_header_declares_the_entry_points():
-    hdr = open(os.path.join(ROOT, "include", "dojo_hip.h")).read()
-    for n in NAMES:
-        assert re.search(r"^int\s+%s\s*\(\s*DojoHandle\b" % n, hdr, re.M), n
+    abi_checks.assert_declared(NAMES)
 
 
 def test_python_binding_lists_them():
     for n in NAMES:
         assert n in api.EXPORTED_SYMBOLS, n
     assert hasattr(api.BatchedMechanism, "rollout_gradients")
-    src = open(os.path.join(ROOT, "dojo.jl_amd", "host", "dojo_amd", "autograd.py")).read()      # (importing it needs torch: the text is enough here)
+    src = abi_checks.host_source("autograd")      # (importing it needs torch: the text is enough here)
     assert "def differentiable_rollout(" in src
 
 
 def test_library_exports_them():
-    lib = ctypes.CDLL(os.path.join(ROOT, "dojo.jl_amd", "csrc", "libdojo_hip.so"))
-    for n in NAMES:
-        assert hasattr(lib, n), n
+    abi_checks.assert_exported_and_bound(NAMES)
 
 
 def test_julia_shim_names_the_host_entry():
-    jl = open(os.path.join(ROOT, "dojo.jl_amd", "julia", "DojoHIP.jl")).read()
+    jl = abi_checks.text(abi_checks.JULIA_SHIM)
     assert "fn(:dojo_rollout_gradients)" in jl and "function rollout_gradients(" in jl

@@ -11,7 +11,6 @@ addition of g, all in fp64; two summation orders of such a dot product differ by
 Stability of Numerical Algorithms, 3.1), so with `abs` the same recursion run on |DZ|, |DU|, |G|
     |out - ref| <= 2 H (nx + 2) 2^-53 abs   (+ 2^-23 |ref| for fp32 outputs: one rounding of the result, a whole ulp)
 and (nx + 12) where the cotangent is first pulled back from state coordinates (the ten extra operations of the quaternion product)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -19,6 +18,7 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api, quat
+from gpu_util import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -50,21 +50,9 @@ def teardown_module(module):
     _handles.clear()
 
 
-def _dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def adjoint_raw(gm, H, DZ, DU, G, cot_space=0, Z=None, status=None, gU=None, gz=None):
     """dojo_rollout_adjoint_dev on torch tensors (None = NULL) -> return code"""
-    return api.lib().dojo_rollout_adjoint_dev(gm.h, int(H), _ptr(DZ), _ptr(DU), _ptr(G), int(cot_space), _ptr(Z), _ptr(status), _ptr(gU), _ptr(gz), _stream())
+    return api.lib().dojo_rollout_adjoint_dev(gm.h, int(H), api.addr(DZ), api.addr(DU), api.addr(G), int(cot_space), api.addr(Z), api.addr(status), api.addr(gU), api.addr(gz), api.torch_stream())
 
 
 def adjoint(gm, DZ, DU, G, cot_space=0, Z=None, status=None, outs=None):
@@ -78,7 +66,7 @@ def adjoint(gm, DZ, DU, G, cot_space=0, Z=None, status=None, outs=None):
         gz = torch.full((B, nx), float("nan"), dtype=tdt, device="cuda")
     else:
         gU, gz = (outs.get("gU") if nu else None), outs.get("gz")
-    keep = [_dev(DZ), _dev(DU) if nu else None, _dev(G), _dev(Z), _dev(status)]
+    keep = [dev(DZ), dev(DU) if nu else None, dev(G), dev(Z), dev(status)]
     api._chk(adjoint_raw(gm, H, keep[0], keep[1], keep[2], cot_space, keep[3], keep[4], gU, gz))
     torch.cuda.synchronize()
     return (None if gU is None else gU.cpu().numpy()), (None if gz is None else gz.cpu().numpy())
@@ -230,8 +218,8 @@ def record(gm, z0, U, H):
     tdt = torch.float32 if gm.dtype_code else torch.float64
     Z = torch.empty((H, B, s.nz), dtype=tdt, device="cuda"); st = torch.empty((H, B), dtype=torch.int32, device="cuda")
     DZ = torch.empty((H, B, s.nx, s.nx), dtype=tdt, device="cuda"); DU = torch.empty((H, B, max(s.nu, 1), s.nx), dtype=tdt, device="cuda")
-    z0d, Ud = _dev(z0.astype(gm.np_dtype)), _dev(None if U is None else U.astype(gm.np_dtype))
-    rc = api.lib().dojo_rollout_record_dev(gm.h, _ptr(z0d), _ptr(Ud), int(H), _ptr(Z), _ptr(st), _ptr(DZ), _ptr(DU), _stream())
+    z0d, Ud = dev(z0.astype(gm.np_dtype)), dev(None if U is None else U.astype(gm.np_dtype))
+    rc = api.lib().dojo_rollout_record_dev(gm.h, api.addr(z0d), api.addr(Ud), int(H), api.addr(Z), api.addr(st), api.addr(DZ), api.addr(DU), api.torch_stream())
     torch.cuda.synchronize()
     return rc, Z.cpu().numpy(), st.cpu().numpy(), DZ.cpu().numpy(), DU.cpu().numpy()[:, :, :s.nu]
 
@@ -361,10 +349,10 @@ def test_autograd_wrapper():
     U = np.stack([u * rng.uniform(0.5, 1.0) for _ in range(H)]).astype(np.float32); z0 = z0.astype(np.float32)
     W = rng.standard_normal((H, B, spec.nz)).astype(np.float32)
     Zh, sh, gU, gz = gm.rollout_gradients(z0, U, W, cot_space="state")
-    zt = _dev(z0).requires_grad_(True); Ut = _dev(U).requires_grad_(True)
+    zt = dev(z0).requires_grad_(True); Ut = dev(U).requires_grad_(True)
     Z = differentiable_rollout(gm, zt, Ut)
     assert Z.status.dtype == torch.int32 and not Z.status.requires_grad
-    gzt, gUt = torch.autograd.grad((Z * _dev(W)).sum(), [zt, Ut])
+    gzt, gUt = torch.autograd.grad((Z * dev(W)).sum(), [zt, Ut])
     torch.cuda.synchronize()
     assert np.array_equal(Z.detach().cpu().numpy(), Zh) and np.array_equal(Z.status.cpu().numpy(), sh)
     assert np.array_equal(gUt.cpu().numpy(), gU) and np.abs(gU).max() > 0
@@ -378,7 +366,7 @@ def test_argument_errors():
     """9. every argument error of dojo_rollout_adjoint_dev: DOJO_ERR_INVALID, a message on the handle, nothing launched (the outputs keep their fill)"""
     H, B = 2, 3
     gm = _handle("cartpole", "f64", B); s = gm.spec
-    DZ, DU, G = (_dev(a) for a in synthetic("cartpole", "f64", H, B))
+    DZ, DU, G = (dev(a) for a in synthetic("cartpole", "f64", H, B))
     Z = torch.zeros((H, B, s.nz), dtype=torch.float64, device="cuda")
     gU = torch.full((H, B, s.nu), 77.0, dtype=torch.float64, device="cuda"); gz = torch.full((B, s.nx), 77.0, dtype=torch.float64, device="cuda")
     bad = {"H < 1": dict(H=0), "DZ NULL": dict(DZ=None), "G NULL": dict(G=None), "cot_space 1 without Z": dict(cot_space=1, Z=None),

@@ -27,6 +27,7 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api, quat
+from gpu_util import dev, same
 
 pytestmark = pytest.mark.gpu
 
@@ -69,25 +70,13 @@ def teardown_module(module):
     _handles.clear()
 
 
-def _dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _nth(gm):
     return 5 * len(gm.spec.contacts)
 
 
 def data_adjoint_raw(gm, H, DZ, DC, G, cot_space=0, Z=None, status=None, gte=None, gt=None, gz=None):
     """dojo_rollout_data_adjoint_dev on torch tensors (None = NULL) -> return code"""
-    return api.lib().dojo_rollout_data_adjoint_dev(gm.h, int(H), _ptr(DZ), _ptr(DC), _ptr(G), int(cot_space), _ptr(Z), _ptr(status), _ptr(gte), _ptr(gt), _ptr(gz), _stream())
+    return api.lib().dojo_rollout_data_adjoint_dev(gm.h, int(H), api.addr(DZ), api.addr(DC), api.addr(G), int(cot_space), api.addr(Z), api.addr(status), api.addr(gte), api.addr(gt), api.addr(gz), api.torch_stream())
 
 
 def data_adjoint(gm, DZ, DC, G, cot_space=0, Z=None, status=None, want=("env", "sum", "gz"), outs=None):
@@ -99,7 +88,7 @@ def data_adjoint(gm, DZ, DC, G, cot_space=0, Z=None, status=None, want=("env", "
     nan = lambda *shape: torch.full(shape, float("nan"), dtype=tdt, device="cuda")
     own = lambda k, *shape: None if k not in want else nan(*shape) if outs is None else outs[k]
     gte, gt, gz = own("env", B, nth), own("sum", nth), own("gz", B, nx)
-    keep = [_dev(DZ), _dev(DC), _dev(G), _dev(Z), _dev(status)]
+    keep = [dev(DZ), dev(DC), dev(G), dev(Z), dev(status)]
     api._chk(data_adjoint_raw(gm, H, keep[0], keep[1], keep[2], cot_space, keep[3], keep[4], gte, gt, gz))
     torch.cuda.synchronize()
     return tuple(None if t is None else t.cpu().numpy() for t in (gte, gt, gz))
@@ -273,11 +262,11 @@ def record(gm, z0, U, H, with_dc=True):
     Z = torch.empty((H, B, s.nz), dtype=tdt, device="cuda"); st = torch.empty((H, B), dtype=torch.int32, device="cuda")
     DZ = torch.empty((H, B, s.nx, s.nx), dtype=tdt, device="cuda"); DU = torch.empty((H, B, max(s.nu, 1), s.nx), dtype=tdt, device="cuda")
     DC = torch.full((H, B, max(_nth(gm), 1), s.nx), 77.0, dtype=tdt, device="cuda")
-    z0d, Ud = _dev(z0.astype(gm.np_dtype)), _dev(None if U is None else U.astype(gm.np_dtype))
+    z0d, Ud = dev(z0.astype(gm.np_dtype)), dev(None if U is None else U.astype(gm.np_dtype))
     if with_dc:
-        rc = api.lib().dojo_rollout_data_record_dev(gm.h, _ptr(z0d), _ptr(Ud), int(H), _ptr(Z), _ptr(st), _ptr(DZ), _ptr(DU), _ptr(DC), _stream())
+        rc = api.lib().dojo_rollout_data_record_dev(gm.h, api.addr(z0d), api.addr(Ud), int(H), api.addr(Z), api.addr(st), api.addr(DZ), api.addr(DU), api.addr(DC), api.torch_stream())
     else:
-        rc = api.lib().dojo_rollout_record_dev(gm.h, _ptr(z0d), _ptr(Ud), int(H), _ptr(Z), _ptr(st), _ptr(DZ), _ptr(DU), _stream())
+        rc = api.lib().dojo_rollout_record_dev(gm.h, api.addr(z0d), api.addr(Ud), int(H), api.addr(Z), api.addr(st), api.addr(DZ), api.addr(DU), api.torch_stream())
     torch.cuda.synchronize()
     return rc, Z.cpu().numpy(), st.cpu().numpy(), DZ.cpu().numpy(), DU.cpu().numpy()[:, :, :s.nu], DC.cpu().numpy()[:, :, :_nth(gm)]
 
@@ -363,7 +352,7 @@ def test_set_contact_data_is_a_fresh_handle(name):
         assert not np.array_equal(Zs, Zold)                                  # (the data did change the rollout)
         # a negative radius: INVALID, and nothing changed
         bad = th1.copy(); bad[0, 1] = -0.1
-        assert api.lib().dojo_set_contact_data(gm.h, C.c_void_p(bad.ctypes.data)) == INVALID and "dojo_set_contact_data" in gm.last_error()
+        assert api.lib().dojo_set_contact_data(gm.h, api.addr(bad)) == INVALID and "dojo_set_contact_data" in gm.last_error()
         assert np.array_equal(gm.contact_data(), th1)
     finally:
         gm.close()
@@ -379,7 +368,7 @@ def test_set_contact_data_refuses_impact_friction():
         th = gm.contact_data()
         assert th[0, 0] == 0.0
         th[0, 0] = 0.3
-        assert api.lib().dojo_set_contact_data(gm.h, C.c_void_p(th.ctypes.data)) == UNSUPPORTED and "ImpactContact" in gm.last_error()
+        assert api.lib().dojo_set_contact_data(gm.h, api.addr(th)) == UNSUPPORTED and "ImpactContact" in gm.last_error()
         th[0, 0] = 0.0; th[0, 1] = 0.4
         gm.set_contact_data(th)
         assert np.array_equal(gm.contact_data(), th)
@@ -526,11 +515,11 @@ def test_autograd_wrapper():
     W = rng.standard_normal((H, B, spec.nz)).astype(np.float32)
     th = gm.contact_data()
     Zh, sh, gth, _, gU, gz = gm.rollout_data_gradients(z0, U, W, cot_space="state")
-    zt = _dev(z0).requires_grad_(True); Ut = _dev(U).requires_grad_(True)
-    for theta in (torch.from_numpy(th.copy()).requires_grad_(True), _dev(th).requires_grad_(True)):      # CPU and device
+    zt = dev(z0).requires_grad_(True); Ut = dev(U).requires_grad_(True)
+    for theta in (torch.from_numpy(th.copy()).requires_grad_(True), dev(th).requires_grad_(True)):      # CPU and device
         Z = differentiable_data_rollout(gm, zt, Ut, theta)
         assert Z.status.dtype == torch.int32 and not Z.status.requires_grad
-        gtt, gUt, gzt = torch.autograd.grad((Z * _dev(W)).sum(), [theta, Ut, zt])
+        gtt, gUt, gzt = torch.autograd.grad((Z * dev(W)).sum(), [theta, Ut, zt])
         torch.cuda.synchronize()
         assert np.array_equal(Z.detach().cpu().numpy(), Zh) and np.array_equal(Z.status.cpu().numpy(), sh)
         assert gtt.dtype == torch.float64 and gtt.device == theta.device and tuple(gtt.shape) == th.shape
@@ -547,7 +536,7 @@ def test_argument_errors():
     outputs keep their fill); mechanisms without contact-data gradients: DOJO_ERR_UNSUPPORTED before any launch"""
     H, B = 2, 3
     gm = _handle("block", "f64", B); s = gm.spec; nth = _nth(gm)
-    DZ, DC, G = (_dev(a) for a in synthetic("block", "f64", H, B))
+    DZ, DC, G = (dev(a) for a in synthetic("block", "f64", H, B))
     Z = torch.zeros((H, B, s.nz), dtype=torch.float64, device="cuda")
     fill = lambda *shape: torch.full(shape, 77.0, dtype=torch.float64, device="cuda")
     gte, gt, gz = fill(B, nth), fill(nth), fill(B, s.nx)
@@ -570,10 +559,10 @@ def test_argument_errors():
         assert rc == INVALID and "16-byte" in gm.last_error() and "dojo_rollout_data_adjoint_dev" in gm.last_error(), (what, gm.last_error())
         assert untouched(), what
     # the record entry: its own argument errors ...
-    z0 = _dev(np.tile(d.initialize(s), (B, 1)))
+    z0 = dev(np.tile(d.initialize(s), (B, 1)))
     Zr = fill(H, B, s.nz); DZr = fill(H, B, s.nx, s.nx); DUr = fill(H, B, s.nu, s.nx); DCr = fill(H, B, nth, s.nx)
-    rec = lambda **kw: api.lib().dojo_rollout_data_record_dev(gm.h, _ptr(kw.get("z0", z0)), None, int(kw.get("H", H)), _ptr(kw.get("Z", Zr)), None,
-                                                              _ptr(kw.get("DZ", DZr)), _ptr(kw.get("DU", DUr)), _ptr(DCr), _stream())
+    rec = lambda **kw: api.lib().dojo_rollout_data_record_dev(gm.h, api.addr(kw.get("z0", z0)), None, int(kw.get("H", H)), api.addr(kw.get("Z", Zr)), None,
+                                                              api.addr(kw.get("DZ", DZr)), api.addr(kw.get("DU", DUr)), api.addr(DCr), api.torch_stream())
     for what, kw in {"H < 1": dict(H=0), "z0 NULL": dict(z0=None), "Z NULL": dict(Z=None), "DZ NULL": dict(DZ=None), "DU NULL": dict(DU=None)}.items():
         rc = rec(**kw)
         torch.cuda.synchronize()
@@ -598,7 +587,7 @@ def test_argument_errors():
 def _gradients_call(entry, gm, spec, H, z0, G, theta, status, gz):
     """one raw call of a *_gradients host entry on host arrays: no controls, tangent-space cotangents, a shared policy on input 0 (theta: W, or the network's
     parameters for the widths [2 nu, 3, 1]); of the outputs, status and gz alone are asked for"""
-    L, p, nobs = api.lib(), api._p, 2 * spec.nu
+    L, p, nobs = api.lib(), api.addr, 2 * spec.nu
     if entry == "dojo_rollout_gradients":
         return L.dojo_rollout_gradients(gm.h, p(z0), None, H, p(G), 0, None, p(status), None, p(gz))
     if entry == "dojo_rollout_data_gradients":

@@ -2,26 +2,22 @@
 entry points are listed in api.EXPORTED_SYMBOLS and exported by the built library, the Julia shim names the two host-pointer ones, the ctypes mirrors
 of `DojoMlpPolicy` and `DojoMlpAdjoint` have the layout the C compiler gives the structs, and pack_mlp / unpack_mlp are each other's inverse in the
 layout the header states."""
-import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_checks
 from dojo_amd import api
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dojo_rollout_mlp_dev", "dojo_rollout_mlp", "dojo_rollout_mlp_record_dev", "dojo_rollout_mlp_adjoint_dev", "dojo_rollout_mlp_gradients")
 POLICY_FIELDS = ("theta", "mean", "scale", "U_ff", "per_env", "act_off", "n_layers", "width", "contact_forces", "contact_init", "reserved")
 ADJOINT_FIELDS = ("DZ", "DU", "OBS", "ACT", "status", "z0", "Z", "M", "G", "G_u", "G_obs", "gtheta", "gU", "gz", "cot_space", "reserved")
 
 
 def test_header_declares_the_entry_points():
-    hdr = open(os.path.join(ROOT, "include", "dojo_hip.h")).read()
-    for n in NAMES:
-        assert re.search(r"^int\s+%s\s*\(\s*DojoHandle\b" % n, hdr, re.M), n
+    abi_checks.assert_declared(NAMES)
+    hdr = abi_checks.text(abi_checks.HEADER)
     assert re.search(r"typedef\s+struct\s+DojoMlpPolicy\s*\{", hdr) and re.search(r"typedef\s+struct\s+DojoMlpAdjoint\s*\{", hdr)
     assert re.search(r"^#define\s+DOJO_MLP_MAX_LAYERS\s+%d\s*$" % api.MLP_MAX_LAYERS, hdr, re.M)
     assert "non-affine policies" not in hdr
@@ -32,36 +28,24 @@ def test_python_binding_lists_them():
         assert n in api.EXPORTED_SYMBOLS, n
     for m in ("rollout_mlp", "rollout_mlp_gradients"):
         assert hasattr(api.BatchedMechanism, m), m
-    src = open(os.path.join(ROOT, "dojo.jl_amd", "host", "dojo_amd", "autograd.py")).read()      # (importing it needs torch: the text is enough here)
+    src = abi_checks.host_source("autograd")      # (importing it needs torch: the text is enough here)
     assert "def differentiable_mlp_rollout(mech, z0, theta, widths, U_ff=None, steps=None, mean=None, scale=None, act_off=0)" in src
 
 
 def test_library_exports_them():
-    lib = ctypes.CDLL(os.path.join(ROOT, "dojo.jl_amd", "csrc", "libdojo_hip.so"))
-    for n in NAMES:
-        assert hasattr(lib, n), n
+    abi_checks.assert_exported_and_bound(NAMES)
 
 
 def test_julia_shim_names_the_host_entries():
-    jl = open(os.path.join(ROOT, "dojo.jl_amd", "julia", "DojoHIP.jl")).read()
+    jl = abi_checks.text(abi_checks.JULIA_SHIM)
     assert "fn(:dojo_rollout_mlp)" in jl and "function rollout_mlp(" in jl
     assert "fn(:dojo_rollout_mlp_gradients)" in jl and "function rollout_mlp_gradients(" in jl
 
 
 @pytest.mark.parametrize("struct,fields", [("DojoMlpPolicy", POLICY_FIELDS), ("DojoMlpAdjoint", ADJOINT_FIELDS)])
-def test_ctypes_mirrors_have_the_layout_of_the_c_structs(tmp_path, struct, fields):
-    """a host-only C program compiled against include/dojo_hip.h prints sizeof and every offsetof"""
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "dojo_hip.h"\nint main(void) {\n    printf("sizeof %%zu\\n", sizeof(%s));\n' % struct
-                   + "".join('    printf("%s %%zu\\n", offsetof(%s, %s));\n' % (f, struct, f) for f in fields) + "    return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["cc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True, capture_output=True, text=True, timeout=120)
-    out = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout.splitlines())
+def test_ctypes_mirrors_have_the_layout_of_the_c_structs(struct, fields):
     mirror = getattr(api, struct)
-    assert int(out["sizeof"]) == ctypes.sizeof(mirror)
-    assert [f for f, _ in mirror._fields_] == list(fields)
-    for f in fields:
-        assert int(out[f]) == getattr(mirror, f).offset, f
+    abi_checks.assert_mirror_layout(struct, mirror, fields)
     if struct == "DojoMlpPolicy":
         assert mirror.width.size == 4 * (api.MLP_MAX_LAYERS + 1)
 

@@ -26,12 +26,13 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api
+from gpu_util import dev, same, tdt_of
 import test_policy_adjoint_gpu as P        # the conventions and helpers of the affine tests: same(), synthetic(), check(), absolute(), CASES, ...
 
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = -1, -2
-same, _dev, _ptr, _dp, _stream, _tdt, _spec, ACT_OF = P.same, P._dev, P._ptr, P._dp, P._stream, P._tdt, P._spec, P.ACT
+_spec, ACT_OF = P._spec, P.ACT
 U53 = 2.0 ** -53
 
 _handles = {}
@@ -76,7 +77,7 @@ def hidden_slices(widths):
 
 
 def policy(t, per_env, act_off, widths, contact_forces=0):
-    g = lambda k: _dp(t.get(k))
+    g = lambda k: api.addr(t.get(k))
     return api.mlp_policy_struct(g("theta"), g("mean"), g("scale"), g("U_ff"), per_env, act_off, widths, contact_forces, 0)
 
 
@@ -86,9 +87,9 @@ def fill(shape, dt):
 
 def forward(gm, p, widths, H, per_env, act_off, contact_forces=0, with_act=True, record=False):
     """dojo_rollout_mlp_dev (or the recording entry) on NumPy inputs p (z0, theta, mean, scale, U_ff) -> dict of NumPy outputs; outputs start as NaN"""
-    s, B, tdt = gm.spec, gm.batch, _tdt(gm)
+    s, B, tdt = gm.spec, gm.batch, tdt_of(gm)
     nobs, nh = widths[0], sum(widths[1:-1])
-    t = {k: _dev(np.asarray(v, gm.np_dtype)) for k, v in p.items() if v is not None}
+    t = {k: dev(np.asarray(v, gm.np_dtype)) for k, v in p.items() if v is not None}
     pol = policy(t, per_env, act_off, widths, contact_forces)
     o = dict(Z=fill((H, B, s.nz), tdt), OBS=fill((H + 1, B, nobs), tdt), U=fill((H, B, s.nu), tdt), S=fill((H, B), torch.int32))
     if with_act:
@@ -96,10 +97,10 @@ def forward(gm, p, widths, H, per_env, act_off, contact_forces=0, with_act=True,
     L = api.lib()
     if record:
         o["DZ"] = fill((H, B, s.nx, s.nx), tdt); o["DU"] = fill((H, B, s.nu, s.nx), tdt)
-        api._chk(L.dojo_rollout_mlp_record_dev(gm.h, _ptr(t["z0"]), C.byref(pol), H, _ptr(o["Z"]), _ptr(o["OBS"]), _ptr(o["U"]), _ptr(o.get("ACT")), _ptr(o["S"]),
-                                               _ptr(o["DZ"]), _ptr(o["DU"]), _stream()))
+        api._chk(L.dojo_rollout_mlp_record_dev(gm.h, api.addr(t["z0"]), C.byref(pol), H, api.addr(o["Z"]), api.addr(o["OBS"]), api.addr(o["U"]), api.addr(o.get("ACT")), api.addr(o["S"]),
+                                               api.addr(o["DZ"]), api.addr(o["DU"]), api.torch_stream()))
     else:
-        api._chk(L.dojo_rollout_mlp_dev(gm.h, _ptr(t["z0"]), C.byref(pol), H, _ptr(o["Z"]), _ptr(o["OBS"]), _ptr(o["U"]), _ptr(o.get("ACT")), _ptr(o["S"]), _stream()))
+        api._chk(L.dojo_rollout_mlp_dev(gm.h, api.addr(t["z0"]), C.byref(pol), H, api.addr(o["Z"]), api.addr(o["OBS"]), api.addr(o["U"]), api.addr(o.get("ACT")), api.addr(o["S"]), api.torch_stream()))
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in o.items()}
 
@@ -119,15 +120,15 @@ def closed_loop_inputs(name, dtype, B, H, widths, per_env=1, seed=5, contact_for
 def test_one_layer_forward_is_the_affine_rollout(name, B, cf, dtype, per_env):
     """1a. theta = [W | bias]: Z, OBS, U_out, status of dojo_rollout_mlp_dev are dojo_rollout_policy_dev's (Ant also with its contact observations)"""
     H = 3
-    gm = _handle(name, dtype, B); s = gm.spec; act_off, na = ACT_OF[name]; tdt = _tdt(gm)
+    gm = _handle(name, dtype, B); s = gm.spec; act_off, na = ACT_OF[name]; tdt = tdt_of(gm)
     widths = widths_of(name, [], bool(cf)); nobs = widths[0]
     p = closed_loop_inputs(name, dtype, B, H, widths, per_env)
     (W,), (b,) = api.unpack_mlp(p["theta"], widths)
     m = forward(gm, p, widths, H, per_env, act_off, cf)
-    t = {k: _dev(np.ascontiguousarray(v)) for k, v in dict(p, W=W, bias=b).items()}
+    t = {k: dev(np.ascontiguousarray(v)) for k, v in dict(p, W=W, bias=b).items()}
     pol = api.DojoPolicy(*[t[k].data_ptr() for k in ("W", "bias", "mean", "scale", "U_ff")], per_env, act_off, na, cf, 0, 0)
     a = dict(Z=fill((H, B, s.nz), tdt), OBS=fill((H + 1, B, nobs), tdt), U=fill((H, B, s.nu), tdt), S=fill((H, B), torch.int32))
-    api._chk(api.lib().dojo_rollout_policy_dev(gm.h, _ptr(t["z0"]), C.byref(pol), H, _ptr(a["Z"]), _ptr(a["OBS"]), _ptr(a["U"]), _ptr(a["S"]), _stream()))
+    api._chk(api.lib().dojo_rollout_policy_dev(gm.h, api.addr(t["z0"]), C.byref(pol), H, api.addr(a["Z"]), api.addr(a["OBS"]), api.addr(a["U"]), api.addr(a["S"]), api.torch_stream()))
     torch.cuda.synchronize()
     for k in ("Z", "OBS", "U", "S"):
         assert same(m[k], a[k].cpu().numpy()), k
@@ -136,18 +137,18 @@ def test_one_layer_forward_is_the_affine_rollout(name, B, cf, dtype, per_env):
 
 def mlp_sweep_raw(gm, H, t, per_env, act_off, widths, cot_space=0, contact_forces=0):
     """dojo_rollout_mlp_adjoint_dev on a dict of torch tensors (missing / None = NULL) -> return code"""
-    g = lambda k: _dp(t.get(k))
+    g = lambda k: api.addr(t.get(k))
     pol = policy(t, per_env, act_off, widths, contact_forces)
     a = api.DojoMlpAdjoint(g("DZ"), g("DU"), g("OBS"), g("ACT"), g("status"), g("z0"), g("Z"), g("M"), g("G"), g("G_u"), g("G_obs"), g("gtheta"), g("gU"), g("gz"),
                            int(cot_space), 0)
-    return api.lib().dojo_rollout_mlp_adjoint_dev(gm.h, C.byref(pol), int(H), C.byref(a), _stream())
+    return api.lib().dojo_rollout_mlp_adjoint_dev(gm.h, C.byref(pol), int(H), C.byref(a), api.torch_stream())
 
 
 OUTS = ("gtheta", "gU", "gz")
 
 
 def mlp_out_tensors(gm, H, per_env, widths, fill_=float("nan")):
-    s, B, tdt = gm.spec, gm.batch, _tdt(gm)
+    s, B, tdt = gm.spec, gm.batch, tdt_of(gm)
     Pn = api.mlp_sizes(widths)[0]
     f = lambda shape: torch.full(shape, fill_, dtype=tdt, device="cuda")
     return {"gtheta": f((B, Pn) if per_env else (Pn,)), "gU": f((H, B, s.nu)), "gz": f((B, s.nx))}
@@ -156,7 +157,7 @@ def mlp_out_tensors(gm, H, per_env, widths, fill_=float("nan")):
 def mlp_sweep(gm, H, inp, per_env, act_off, widths, cot_space=0, outs=None):
     """NumPy in, NumPy out (dict over OUTS); the outputs start as NaN so that an entry the kernels leave out shows.
     outs: the caller's own device tensors instead (a missing key = NULL, and missing from the result)"""
-    t = {k: _dev(v) for k, v in inp.items() if v is not None}
+    t = {k: dev(v) for k, v in inp.items() if v is not None}
     t.update(mlp_out_tensors(gm, H, per_env, widths) if outs is None else outs)
     api._chk(mlp_sweep_raw(gm, H, t, per_env, act_off, widths, cot_space))
     torch.cuda.synchronize()
@@ -230,7 +231,7 @@ def test_forward_layer_by_layer(name, hidden, B, dtype):
     NumPy's).  Output: the same dot-product term, 2^-53 |ref| for the fp64 addition of U_ff, plus one rounding to the handle dtype (2^-24 |ref| in fp32).  Z is `rollout` fed the returned
     U_out, bit for bit; ACT = NULL changes nothing."""
     H = 3
-    gm = _handle(name, dtype, B, groups=2 if B == 200 else None); s = gm.spec; act_off, na = ACT_OF[name]; tdt = _tdt(gm)
+    gm = _handle(name, dtype, B, groups=2 if B == 200 else None); s = gm.spec; act_off, na = ACT_OF[name]; tdt = tdt_of(gm)
     widths = widths_of(name, hidden)
     p = closed_loop_inputs(name, dtype, B, H, widths)
     out = forward(gm, p, widths, H, 1, act_off)
@@ -238,9 +239,9 @@ def test_forward_layer_by_layer(name, hidden, B, dtype):
     assert envs.mean() >= 0.9
     assert np.isfinite(out["OBS"][:, envs]).all() and np.isfinite(out["U"][:, envs]).all()
     check_layers(p, out, widths, act_off, dtype == "f32", envs)
-    Ud = _dev(out["U"]); z0 = _dev(p["z0"])
+    Ud = dev(out["U"]); z0 = dev(p["z0"])
     Z2, S2 = fill((H, B, s.nz), tdt), fill((H, B), torch.int32)
-    api._chk(api.lib().dojo_rollout_dev(gm.h, _ptr(z0), _ptr(Ud), H, _ptr(Z2), _ptr(S2), _stream()))
+    api._chk(api.lib().dojo_rollout_dev(gm.h, api.addr(z0), api.addr(Ud), H, api.addr(Z2), api.addr(S2), api.torch_stream()))
     torch.cuda.synchronize()
     assert same(Z2.cpu().numpy(), out["Z"]) and same(S2.cpu().numpy(), out["S"])
     bare = forward(gm, p, widths, H, 1, act_off, with_act=False)
@@ -416,8 +417,8 @@ def ant_record():
         r = forward(gm, p, widths, H, 1, act_off, record=True)
         f = lambda shape, dt=torch.float64: fill(shape, dt)
         o = dict(Z=f((H, B, s.nz)), S=f((H, B), torch.int32), DZ=f((H, B, s.nx, s.nx)), DU=f((H, B, s.nu, s.nx)))
-        z0, Ud = _dev(p["z0"]), _dev(r["U"])
-        api._chk(api.lib().dojo_rollout_record_dev(gm.h, _ptr(z0), _ptr(Ud), H, _ptr(o["Z"]), _ptr(o["S"]), _ptr(o["DZ"]), _ptr(o["DU"]), _stream()))
+        z0, Ud = dev(p["z0"]), dev(r["U"])
+        api._chk(api.lib().dojo_rollout_record_dev(gm.h, api.addr(z0), api.addr(Ud), H, api.addr(o["Z"]), api.addr(o["S"]), api.addr(o["DZ"]), api.addr(o["DU"]), api.torch_stream()))
         torch.cuda.synchronize()
         _records["ant"] = (p, widths, a, r, {k: v.cpu().numpy() for k, v in o.items()})
     return _records["ant"]
@@ -541,10 +542,10 @@ def test_autograd_wrapper(per_env):
     z0, theta, A, Bc, Cc = f(z0), f(theta), f(A), f(Bc), f(Cc); kw = {k: f(v) for k, v in kw.items()}
     gm = _handle(name, "f32", B)
     Zh, Oh, Uh, sh, gth, gU, gz = gm.rollout_mlp_gradients(z0, theta, widths, A, act_off=act_off, G_u=Bc, G_obs=Cc, cot_space="state", **kw)
-    zt, tt, Ut = (_dev(a).requires_grad_(True) for a in (z0, theta, kw["U_ff"]))
-    Z, OBS, U = differentiable_mlp_rollout(gm, zt, tt, widths, U_ff=Ut, mean=_dev(kw["mean"]), scale=_dev(kw["scale"]), act_off=act_off)
+    zt, tt, Ut = (dev(a).requires_grad_(True) for a in (z0, theta, kw["U_ff"]))
+    Z, OBS, U = differentiable_mlp_rollout(gm, zt, tt, widths, U_ff=Ut, mean=dev(kw["mean"]), scale=dev(kw["scale"]), act_off=act_off)
     assert Z.status.dtype == torch.int32 and not Z.status.requires_grad
-    loss = (Z * _dev(A)).sum() + (U * _dev(Bc)).sum() + (OBS * _dev(Cc)).sum()
+    loss = (Z * dev(A)).sum() + (U * dev(Bc)).sum() + (OBS * dev(Cc)).sum()
     gzt, gtt, gUt = torch.autograd.grad(loss, [zt, tt, Ut])
     torch.cuda.synchronize()
     assert same(Z.detach().cpu().numpy(), Zh) and same(OBS.detach().cpu().numpy(), Oh) and same(U.detach().cpu().numpy(), Uh) and same(Z.status.cpu().numpy(), sh)
@@ -564,7 +565,7 @@ def test_forward_argument_errors():
     gm = _handle(name, "f64", B); s = gm.spec; act_off, na = ACT_OF[name]
     widths = widths_of(name, [5, 3]); nh = 8
     p = closed_loop_inputs(name, "f64", B, H, widths)
-    t = {k: _dev(v) for k, v in p.items()}
+    t = {k: dev(v) for k, v in p.items()}
     f = lambda shape, dt=torch.float64: torch.full(shape, 77, dtype=dt, device="cuda")
     o = dict(Z=f((H, B, s.nz)), OBS=f((H + 1, B, 2 * s.nu)), U=f((H, B, s.nu)), ACT=f((H, B, nh)), S=f((H, B), torch.int32), DZ=f((H, B, s.nx, s.nx)), DU=f((H, B, s.nu, s.nx)))
     L = api.lib()
@@ -575,9 +576,9 @@ def test_forward_argument_errors():
         if n_layers is not None:
             pol.n_layers = n_layers
         if record:
-            return L.dojo_rollout_mlp_record_dev(gm.h, _ptr(t.get(z0)), C.byref(pol), H_, _ptr(a["Z"]), _ptr(a["OBS"]), _ptr(a["U"]), _ptr(a["ACT"]), _ptr(a["S"]),
-                                                 _ptr(a["DZ"]), _ptr(a["DU"]), _stream())
-        return L.dojo_rollout_mlp_dev(gm.h, _ptr(t.get(z0)), C.byref(pol), H_, _ptr(a["Z"]), _ptr(a["OBS"]), _ptr(a["U"]), _ptr(a["ACT"]), _ptr(a["S"]), _stream())
+            return L.dojo_rollout_mlp_record_dev(gm.h, api.addr(t.get(z0)), C.byref(pol), H_, api.addr(a["Z"]), api.addr(a["OBS"]), api.addr(a["U"]), api.addr(a["ACT"]), api.addr(a["S"]),
+                                                 api.addr(a["DZ"]), api.addr(a["DU"]), api.torch_stream())
+        return L.dojo_rollout_mlp_dev(gm.h, api.addr(t.get(z0)), C.byref(pol), H_, api.addr(a["Z"]), api.addr(a["OBS"]), api.addr(a["U"]), api.addr(a["ACT"]), api.addr(a["S"]), api.torch_stream())
 
     def refused(what, code, text="", entries=(0, 1), **kw):
         for record in entries:
@@ -614,7 +615,7 @@ def test_forward_argument_errors():
     gf = api.BatchedMechanism(s, B, dtype="f64")
     try:
         pol = policy(t, 1, act_off, widths); pol.contact_init = 1
-        rc = L.dojo_rollout_mlp_dev(gf.h, _ptr(t["z0"]), C.byref(pol), H, _ptr(o["Z"]), _ptr(o["OBS"]), _ptr(o["U"]), _ptr(o["ACT"]), _ptr(o["S"]), _stream())
+        rc = L.dojo_rollout_mlp_dev(gf.h, api.addr(t["z0"]), C.byref(pol), H, api.addr(o["Z"]), api.addr(o["OBS"]), api.addr(o["U"]), api.addr(o["ACT"]), api.addr(o["S"]), api.torch_stream())
         torch.cuda.synchronize()
         assert rc == INVALID and "dojo_rollout_mlp_dev" in gf.last_error() and "contact_init" in gf.last_error(), gf.last_error()
     finally:
@@ -623,7 +624,7 @@ def test_forward_argument_errors():
     g0 = _handle("fixed3", "f64", B)
     z = torch.zeros((H, B, g0.spec.nz), dtype=torch.float64, device="cuda")
     pol = api.mlp_policy_struct(z.data_ptr(), None, None, None, 1, 0, [1, 1])
-    assert L.dojo_rollout_mlp_dev(g0.h, _ptr(z), C.byref(pol), H, None, None, None, None, None, _stream()) == INVALID
+    assert L.dojo_rollout_mlp_dev(g0.h, api.addr(z), C.byref(pol), H, None, None, None, None, None, api.torch_stream()) == INVALID
     assert "dojo_rollout_mlp_dev" in g0.last_error() and "no inputs" in g0.last_error()
     gl = api.BatchedMechanism(d.get_fourbar(), 2, dtype="f64")
     try:
@@ -631,7 +632,7 @@ def test_forward_argument_errors():
         z0l = torch.zeros((2, sl.nz), dtype=torch.float64, device="cuda"); th = torch.zeros(api.mlp_sizes(w)[0], dtype=torch.float64, device="cuda")
         Ul = f((H, 2, sl.nu))
         pol = api.mlp_policy_struct(th.data_ptr(), None, None, None, 0, 0, w)
-        rc = L.dojo_rollout_mlp_dev(gl.h, _ptr(z0l), C.byref(pol), H, None, None, _ptr(Ul), None, None, _stream())
+        rc = L.dojo_rollout_mlp_dev(gl.h, api.addr(z0l), C.byref(pol), H, None, None, api.addr(Ul), None, None, api.torch_stream())
         torch.cuda.synchronize()
         assert rc == UNSUPPORTED and "dojo_rollout_mlp_dev" in gl.last_error() and "loop" in gl.last_error(), gl.last_error()
         assert (Ul == 77).all()
@@ -643,9 +644,9 @@ def test_forward_argument_errors():
         nobs = 2 * spec.nu; w = [nobs, 3, spec.nu]
         th = torch.zeros(api.mlp_sizes(w)[0], dtype=torch.float64, device="cuda")
         pol = api.mlp_policy_struct(th.data_ptr(), None, None, None, 0, 0, w)
-        z0 = _dev(np.tile(d.initialize(spec), (4, 1)))
+        z0 = dev(np.tile(d.initialize(spec), (4, 1)))
         r = dict(Z=f((2, 4, spec.nz)), OBS=f((3, 4, nobs)), U=f((2, 4, spec.nu)), ACT=f((2, 4, 3)), S=f((2, 4), torch.int32), DZ=f((2, 4, spec.nx, spec.nx)), DU=f((2, 4, spec.nu, spec.nx)))
-        rc = L.dojo_rollout_mlp_record_dev(gs.h, _ptr(z0), C.byref(pol), 2, _ptr(r["Z"]), _ptr(r["OBS"]), _ptr(r["U"]), _ptr(r["ACT"]), _ptr(r["S"]), _ptr(r["DZ"]), _ptr(r["DU"]), _stream())
+        rc = L.dojo_rollout_mlp_record_dev(gs.h, api.addr(z0), C.byref(pol), 2, api.addr(r["Z"]), api.addr(r["OBS"]), api.addr(r["U"]), api.addr(r["ACT"]), api.addr(r["S"]), api.addr(r["DZ"]), api.addr(r["DU"]), api.torch_stream())
         torch.cuda.synchronize()
         assert rc == UNSUPPORTED and "dojo_rollout_mlp_record_dev" in gs.last_error() and "LinearContact" in gs.last_error(), gs.last_error()
         for k, v in r.items():
@@ -659,7 +660,7 @@ def test_adjoint_argument_errors():
     H, B, name, hidden = 2, 3, "cartpole", [5, 3]
     gm = _handle(name, "f64", B); s = gm.spec; act_off, na = ACT_OF[name]; widths = widths_of(name, hidden)
     who = "dojo_rollout_mlp_adjoint_dev"
-    t = {k: _dev(v) for k, v in mlp_synthetic(name, "f64", H, B, hidden).items()}
+    t = {k: dev(v) for k, v in mlp_synthetic(name, "f64", H, B, hidden).items()}
     t["M"] = torch.nan_to_num(t["M"])
     t["Z"] = torch.zeros((H, B, s.nz), dtype=torch.float64, device="cuda"); t["z0"] = torch.zeros((B, s.nz), dtype=torch.float64, device="cuda")
     outs = mlp_out_tensors(gm, H, 1, widths, fill_=77.0)
@@ -670,10 +671,10 @@ def test_adjoint_argument_errors():
         if n_layers is None:
             rc = mlp_sweep_raw(gm, H_, a, 1, act, w, cot_space, contact_forces)
         else:
-            g = lambda k: _dp(a.get(k))
+            g = lambda k: api.addr(a.get(k))
             pol = policy(a, 1, act, w, contact_forces); pol.n_layers = n_layers
             ad = api.DojoMlpAdjoint(g("DZ"), g("DU"), g("OBS"), g("ACT"), g("status"), g("z0"), g("Z"), g("M"), g("G"), g("G_u"), g("G_obs"), g("gtheta"), g("gU"), g("gz"), 0, 0)
-            rc = api.lib().dojo_rollout_mlp_adjoint_dev(gm.h, C.byref(pol), H_, C.byref(ad), _stream())
+            rc = api.lib().dojo_rollout_mlp_adjoint_dev(gm.h, C.byref(pol), H_, C.byref(ad), api.torch_stream())
         torch.cuda.synchronize()
         assert rc == code, (what, rc)
         assert text in gm.last_error() and who in gm.last_error(), (what, gm.last_error())
@@ -710,7 +711,7 @@ def test_adjoint_argument_errors():
     z0 = np.zeros((B, s.nz)); th = np.zeros(api.mlp_sizes(widths)[0]); G = np.zeros((H, B, s.nx)); gth = np.full_like(th, 77.0)
     for cf, w, code, text in ((1, widths, UNSUPPORTED, "contact_forces"), (0, [4, 5, 3, 3], INVALID, ""), (0, [4, 9000, 1], UNSUPPORTED, "LDS")):
         pol = api.mlp_policy_struct(th.ctypes.data, None, None, None, 0, act_off, w, cf, 0)
-        rc = api.lib().dojo_rollout_mlp_gradients(gm.h, api._p(z0), C.byref(pol), H, api._p(G), 0, None, None, None, None, None, None, api._p(gth), None, None)
+        rc = api.lib().dojo_rollout_mlp_gradients(gm.h, api.addr(z0), C.byref(pol), H, api.addr(G), 0, None, None, None, None, None, None, api.addr(gth), None, None)
         assert rc == code and whoh in gm.last_error() and text in gm.last_error(), (cf, w, rc, gm.last_error())
         assert (gth == 77.0).all()
     with pytest.raises(api.DojoError, match="dojo_rollout_mlp:"):
@@ -746,7 +747,7 @@ def test_sweep_lds_limit():
         big, fits = [120, 1700, 1], [120, 1670, 1]
         assert 4 * (120 + 1700) * 8 <= 65536 < (3180 + 3 * 1700) * 8 and (3180 + 3 * 1670) * 8 <= 65536
         inp = nslider60_inputs(big, H, B)
-        t = {k: _dev(v) for k, v in inp.items()}
+        t = {k: dev(v) for k, v in inp.items()}
         t["M"] = torch.nan_to_num(t["M"])
         outs = mlp_out_tensors(gm, H, 1, big, fill_=77.0)
         t.update(outs)
@@ -758,7 +759,7 @@ def test_sweep_lds_limit():
         z0 = np.zeros((B, spec.nz)); th = np.zeros(api.mlp_sizes(big)[0]); G = np.zeros((H, B, spec.nx)); gth = np.full_like(th, 77.0)
         gU = np.full((H, B, spec.nu), 77.0); gz = np.full((B, spec.nx), 77.0)
         pol = api.mlp_policy_struct(th.ctypes.data, None, None, None, 0, 0, big)
-        rc = api.lib().dojo_rollout_mlp_gradients(gm.h, api._p(z0), C.byref(pol), H, api._p(G), 0, None, None, None, None, None, None, api._p(gth), api._p(gU), api._p(gz))
+        rc = api.lib().dojo_rollout_mlp_gradients(gm.h, api.addr(z0), C.byref(pol), H, api.addr(G), 0, None, None, None, None, None, None, api.addr(gth), api.addr(gU), api.addr(gz))
         assert rc == UNSUPPORTED and "dojo_rollout_mlp_gradients" in gm.last_error() and SWEEP_LDS in gm.last_error(), (rc, gm.last_error())
         assert (gth == 77.0).all() and (gU == 77.0).all() and (gz == 77.0).all()
         del t, outs

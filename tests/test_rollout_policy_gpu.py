@@ -21,6 +21,7 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api
+from gpu_util import dev, same
 
 pytestmark = pytest.mark.gpu
 
@@ -62,23 +63,6 @@ def teardown_module(module):
     _handles.clear()
 
 
-def _dev(a):
-    return None if a is None else torch.from_numpy(np.array(a, order="C")).cuda()      # (a copy: the cached inputs are read-only)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def same(a, b):
-    """bit for bit (NaN-safe)"""
-    return a.shape == b.shape and a.dtype == b.dtype and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
-
 def dims(gm, name):
     act_off, na, cf = POLICY[name]
     nu = gm.spec.nu
@@ -110,7 +94,7 @@ def inputs(name, dtype, B, steps=H, seed=11):
 
 
 def policy_raw(gm, z0, pol, steps, Z, OBS, U, st, handle=True):
-    return api.lib().dojo_rollout_policy_dev(gm.h if handle else None, _ptr(z0), None if pol is None else C.byref(pol), int(steps), _ptr(Z), _ptr(OBS), _ptr(U), _ptr(st), _stream())
+    return api.lib().dojo_rollout_policy_dev(gm.h if handle else None, api.addr(z0), None if pol is None else C.byref(pol), int(steps), api.addr(Z), api.addr(OBS), api.addr(U), api.addr(st), api.torch_stream())
 
 
 def rollout_policy_dev(gm, name, inp, steps=H, want="ZOUS", contact_init=0, per_env=True, act=None):
@@ -120,7 +104,7 @@ def rollout_policy_dev(gm, name, inp, steps=H, want="ZOUS", contact_init=0, per_
     if act is not None:
         act_off, na = act
     tdt = torch.float32 if gm.dtype_code else torch.float64
-    keep = {k: _dev(inp.get(k)) for k in ("z0", "W", "bias", "mean", "scale", "U_ff")}
+    keep = {k: dev(inp.get(k)) for k in ("z0", "W", "bias", "mean", "scale", "U_ff")}
     pol = api.DojoPolicy(*[None if keep[k] is None else keep[k].data_ptr() for k in ("W", "bias", "mean", "scale", "U_ff")], int(per_env), act_off, na, int(cf), int(contact_init), 0)
     out = {"Z": torch.full((steps, B, s.nz), float("nan"), dtype=tdt, device="cuda") if "Z" in want else None,
            "O": torch.full((steps + 1, B, nobs), float("nan"), dtype=tdt, device="cuda") if "O" in want else None,
@@ -135,9 +119,9 @@ def rollout_dev(gm, z0, U):
     """dojo_rollout_dev (open loop) -> Z, status"""
     steps, B = U.shape[:2]
     tdt = torch.float32 if gm.dtype_code else torch.float64
-    z0d, Ud = _dev(z0), _dev(U)
+    z0d, Ud = dev(z0), dev(U)
     Z = torch.full((steps, B, gm.spec.nz), float("nan"), dtype=tdt, device="cuda"); st = torch.full((steps, B), UNWRITTEN, dtype=torch.int32, device="cuda")
-    api._chk(api.lib().dojo_rollout_dev(gm.h, _ptr(z0d), _ptr(Ud), steps, _ptr(Z), _ptr(st), _stream()))
+    api._chk(api.lib().dojo_rollout_dev(gm.h, api.addr(z0d), api.addr(Ud), steps, api.addr(Z), api.addr(st), api.torch_stream()))
     torch.cuda.synchronize()
     return Z.cpu().numpy(), st.cpu().numpy()
 
@@ -145,18 +129,18 @@ def rollout_dev(gm, z0, U):
 def step_observe(gm, z, u, cf, nobs):
     """dojo_step_dev + dojo_observe_dev of the new state -> z_next, obs"""
     tdt = torch.float32 if gm.dtype_code else torch.float64
-    zd, ud = _dev(z), _dev(u)
+    zd, ud = dev(z), dev(u)
     zn = torch.empty_like(zd); obs = torch.full((gm.batch, nobs), float("nan"), dtype=tdt, device="cuda")
-    api._chk(api.lib().dojo_step_dev(gm.h, _ptr(zd), _ptr(ud), _ptr(zn), None, None, None, None, _stream()))
-    api._chk(api.lib().dojo_observe_dev(gm.h, _ptr(zn), _ptr(obs), int(cf), _stream()))
+    api._chk(api.lib().dojo_step_dev(gm.h, api.addr(zd), api.addr(ud), api.addr(zn), None, None, None, None, api.torch_stream()))
+    api._chk(api.lib().dojo_observe_dev(gm.h, api.addr(zn), api.addr(obs), int(cf), api.torch_stream()))
     torch.cuda.synchronize()
     return zn.cpu().numpy(), obs.cpu().numpy()
 
 
 def max2min(gm, z):
     tdt = torch.float32 if gm.dtype_code else torch.float64
-    zd = _dev(z); x = torch.full((gm.batch, 2 * gm.spec.nu), float("nan"), dtype=tdt, device="cuda")
-    api._chk(api.lib().dojo_maximal_to_minimal_dev(gm.h, _ptr(zd), _ptr(x), _stream()))
+    zd = dev(z); x = torch.full((gm.batch, 2 * gm.spec.nu), float("nan"), dtype=tdt, device="cuda")
+    api._chk(api.lib().dojo_maximal_to_minimal_dev(gm.h, api.addr(zd), api.addr(x), api.torch_stream()))
     torch.cuda.synchronize()
     return x.cpu().numpy()
 
@@ -334,7 +318,7 @@ def test_null_outputs(name, dtype, B):
     r = rollout_policy_dev(gm, name, inp, want="S")
     assert same(r["S"], full["S"])
     z = np.full((B, gm.spec.nz), np.nan, gm.np_dtype)
-    api._chk(api.lib().dojo_get_state(gm.h, C.c_void_p(z.ctypes.data)))
+    api._chk(api.lib().dojo_get_state(gm.h, api.addr(z)))
     assert same(z, full["Z"][H - 1])
     for leave in "ZOUS":
         r = rollout_policy_dev(gm, name, inp, want="ZOUS".replace(leave, ""))
@@ -374,7 +358,7 @@ def test_refusals():
         act_off, na, cf, nobs = dims(gm, name)
         inp = inputs(name, dtype, B)
         nu = gm.spec.nu
-        z0, W = _dev(inp["z0"]), _dev(inp["W"])
+        z0, W = dev(inp["z0"]), dev(inp["W"])
         shapes = [(H, B, gm.spec.nz), (H + 1, B, nobs), (H, B, nu), (H, B)]
         pol = lambda **kw: api.DojoPolicy(**{**dict(W=W.data_ptr(), per_env=1, act_off=act_off, na=na, contact_forces=1), **kw})
         _refused(gm, INVALID, z0, pol(), H, shapes, handle=False)
@@ -450,7 +434,7 @@ def test_batched_environment_rollout_policy():
         assert 2 * nu == 28 and nobs > 28 and bool((OBS[0, :, 28:] == 1).all())
         x0 = env.initialize()
         z0 = torch.empty(B, env.spec.nz, dtype=torch.float64, device="cuda")
-        api._chk(api.lib().dojo_minimal_to_maximal_dev(env.mechanism.h, _ptr(x0), _ptr(z0), _stream()))
+        api._chk(api.lib().dojo_minimal_to_maximal_dev(env.mechanism.h, api.addr(x0), api.addr(z0), api.torch_stream()))
         O2 = torch.full_like(OBS, float("nan")); U2 = torch.full_like(U, float("nan")); s2 = torch.full_like(st, UNWRITTEN)
         pol = api.DojoPolicy(theta.data_ptr(), None, mean.data_ptr(), scale.data_ptr(), None, 1, env.n_unactuated, na, 1, 0, 0)
         api._chk(policy_raw(env.mechanism, z0, pol, steps, None, O2, U2, s2))

@@ -4,7 +4,6 @@ across T, B and runs, optional inputs, argument errors; then real rollouts (cent
 host entry end to end, and the Gauss-Newton path of the sphere example.
 
 The bound of every comparison is the one of tests/tangent_cases.py: 2 H (nx + nu + 5Nc + 2) 2^-53 abs_ (+ 2^-23 |ref| for fp32 outputs)."""
-import ctypes as C
 import os
 import sys
 
@@ -14,6 +13,7 @@ import torch
 
 import dojo_amd as d
 from dojo_amd import api
+from gpu_util import dev, guarded, guards_intact, tdt_of
 
 import sweep_cases as S
 import tangent_cases as TC
@@ -22,10 +22,6 @@ pytestmark = pytest.mark.gpu
 
 O, D = S.O, S.D
 INVALID, UNSUPPORTED = -1, -2
-_dev, _ptr, _stream = O._dev, O._ptr, O._stream
-GUARD, SENTINEL = 64, 77.0
-
-
 def teardown_module(module):
     """the handles live in the two modules' caches (whose own teardown may have run already)"""
     for mod in (O, D):
@@ -34,27 +30,10 @@ def teardown_module(module):
         mod._handles.clear()
 
 
-def tdt_of(gm):
-    return torch.float32 if gm.dtype_code else torch.float64
-
-
-def guarded(shape, tdt):
-    """an output that starts as NaN, with GUARD elements of SENTINEL in front of it and behind it"""
-    n = int(np.prod(shape))
-    flat = torch.full((n + 2 * GUARD,), SENTINEL, dtype=tdt, device="cuda")
-    flat[GUARD:GUARD + n] = float("nan")
-    return flat[GUARD:GUARD + n].view(tuple(shape))
-
-
-def guards_intact(t):
-    flat, n = t._base, t.numel()
-    return bool((flat[:GUARD] == SENTINEL).all() and (flat[GUARD + n:] == SENTINEL).all())
-
-
 def tangent_raw(gm, H, T, DZ, DU, DC, dz0, dU, dth, tan_space=0, Z=None, status=None, dZ=None):
     """dojo_rollout_tangent_dev on torch tensors (None = NULL) -> return code"""
-    return api.lib().dojo_rollout_tangent_dev(gm.h, int(H), int(T), _ptr(DZ), _ptr(DU), _ptr(DC), _ptr(dz0), _ptr(dU), _ptr(dth), int(tan_space), _ptr(Z), _ptr(status),
-                                              _ptr(dZ), _stream())
+    return api.lib().dojo_rollout_tangent_dev(gm.h, int(H), int(T), api.addr(DZ), api.addr(DU), api.addr(DC), api.addr(dz0), api.addr(dU), api.addr(dth), int(tan_space), api.addr(Z), api.addr(status),
+                                              api.addr(dZ), api.torch_stream())
 
 
 def sweep(gm, rec, tans, tan_space=0, Z=None, status=None, raw=False):
@@ -64,7 +43,7 @@ def sweep(gm, rec, tans, tan_space=0, Z=None, status=None, raw=False):
     H, B = DZ.shape[:2]
     T = [a.shape[i] for a, i in ((dz0, 1), (dU, 2), (dth, 0)) if a is not None][0]
     out = guarded((H, B, T, gm.spec.nz if tan_space else gm.spec.nx), tdt_of(gm))
-    keep = [_dev(a) for a in (DZ, DU, DC, dz0, dU, dth, Z, status)]
+    keep = [dev(a) for a in (DZ, DU, DC, dz0, dU, dth, Z, status)]
     api._chk(tangent_raw(gm, H, T, *keep[:6], tan_space, keep[6], keep[7], out))
     torch.cuda.synchronize()
     assert guards_intact(out)
@@ -266,10 +245,10 @@ def test_inputs_without_columns_are_ignored(name):
     gm = O._handle(name, "f64", B); nx, nu = gm.spec.nx, gm.spec.nu
     rec = TC.record(name, "f64", H, B)
     dz0, dU, _ = TC.tangents("f64", H, B, T, nx, nu, 0)
-    junk = _dev(np.full(64, np.nan))
+    junk = dev(np.full(64, np.nan))
     base = sweep(gm, rec, (dz0, dU, None), raw=True)
     out = guarded((H, B, T, nx), torch.float64)
-    keep = [_dev(a) for a in (rec[0], rec[1], dz0, dU)]
+    keep = [dev(a) for a in (rec[0], rec[1], dz0, dU)]
     if name == "fixed3":
         assert nu == 0
         rc = tangent_raw(gm, H, T, keep[0], None, None, keep[2], junk, None, dZ=out)
@@ -288,8 +267,8 @@ def test_argument_errors():
     """every refusal of dojo_rollout_tangent_dev: DOJO_ERR_INVALID, a text on the handle that names the entry, nothing launched (the output stays NaN)"""
     H, B, T = 2, 3, 4
     gm = D._handle("ant", "f64", B); s = gm.spec; nx, nu, nth = s.nx, s.nu, 5 * len(s.contacts)
-    DZ, DU, DC = (_dev(a) for a in TC.record("ant", "f64", H, B, data=True))
-    dz0, dU, dth = (_dev(a) for a in TC.tangents("f64", H, B, T, nx, nu, nth))
+    DZ, DU, DC = (dev(a) for a in TC.record("ant", "f64", H, B, data=True))
+    dz0, dU, dth = (dev(a) for a in TC.tangents("f64", H, B, T, nx, nu, nth))
     Z = torch.zeros((H, B, s.nz), dtype=torch.float64, device="cuda")
     out = torch.full((H, B, T, s.nz), float("nan"), dtype=torch.float64, device="cuda")
     good = dict(H=H, T=T, DZ=DZ, DU=DU, DC=DC, dz0=dz0, dU=dU, dth=dth, tan_space=0, Z=Z, status=None, dZ=out)
@@ -424,7 +403,7 @@ def test_call_larger_than_the_device_is_refused():
     gm = api.BatchedMechanism(spec, B, dtype="f64")
     try:
         one, out = np.zeros(1), np.full(1, 77.0)
-        p = api._p
+        p = api.addr
         rc = api.lib().dojo_rollout_tangents(gm.h, p(one), None, H, T, p(one), p(one), p(one), 0, None, None, p(out))
         err = gm.last_error()
         print("H", H, "record", record, "rc", rc, err)

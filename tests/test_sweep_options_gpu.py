@@ -17,11 +17,11 @@ import pytest
 import torch
 
 import sweep_cases as S
+from gpu_util import dev, guarded, guards_intact, same, tdt_of
 
 pytestmark = pytest.mark.gpu
 
 O, P, N, D = S.O, S.P, S.N, S.D
-same = P.same
 
 
 def teardown_module(module):
@@ -258,23 +258,6 @@ def nan_like(gm, shape):
 
 
 # ---------------------------------------------------------------- e. output subsets ----------------------------------------------------------------
-GUARD, SENTINEL = 64, 77.0
-
-
-def guarded(shape, tdt):
-    """an output that starts as NaN, with GUARD elements of SENTINEL in front of it and behind it"""
-    n = int(np.prod(shape))
-    flat = torch.full((n + 2 * GUARD,), SENTINEL, dtype=tdt, device="cuda")
-    flat[GUARD:GUARD + n] = float("nan")
-    return flat[GUARD:GUARD + n].view(tuple(shape))
-
-
-def guards_intact(t):
-    flat, n = t._base, t.numel()
-    assert flat.numel() == n + 2 * GUARD
-    return bool((flat[:GUARD] == SENTINEL).all() and (flat[GUARD + n:] == SENTINEL).all())
-
-
 def subsets(keys, pairs=False):
     import itertools
     return [(k,) for k in keys] + (list(itertools.combinations(keys, 2)) if pairs else [])
@@ -307,7 +290,7 @@ def test_output_subsets_open_loop(name, dtype):
     def run(outs):
         gU, gz = O.adjoint(gm, DZ, DU, G, outs=outs)
         return {k: v for k, v in (("gU", gU), ("gz", gz)) if v is not None}
-    assert_subsets(run, {"gU": (H, B, s.nu), "gz": (B, s.nx)}, P._tdt(gm))
+    assert_subsets(run, {"gU": (H, B, s.nu), "gz": (B, s.nx)}, tdt_of(gm))
 
 
 @pytest.mark.parametrize("per_env", [1, 0])
@@ -322,7 +305,7 @@ def test_output_subsets_closed_loop(name, hidden, dtype, per_env):
         gm = P._handle(name, dtype, B); proto = P.out_tensors(gm, H, per_env, na)
     else:
         gm = N._handle(name, dtype, B); proto = N.mlp_out_tensors(gm, H, per_env, N.widths_of(name, hidden))
-    assert_subsets(lambda outs: closed_sweep(name, dtype, B, H, inp, hidden, per_env, outs=outs), {k: tuple(v.shape) for k, v in proto.items()}, P._tdt(gm))
+    assert_subsets(lambda outs: closed_sweep(name, dtype, B, H, inp, hidden, per_env, outs=outs), {k: tuple(v.shape) for k, v in proto.items()}, tdt_of(gm))
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -336,7 +319,7 @@ def test_output_subsets_data(name, dtype):
     def run(outs):
         res = D.data_adjoint(gm, DZ, DC, G, want=tuple(outs), outs=outs)
         return {k: v for k, v in zip(("env", "sum", "gz"), res) if v is not None}
-    assert_subsets(run, {"env": (B, D._nth(gm)), "sum": (D._nth(gm),), "gz": (B, s.nx)}, P._tdt(gm), pairs=True)
+    assert_subsets(run, {"env": (B, D._nth(gm)), "sum": (D._nth(gm),), "gz": (B, s.nx)}, tdt_of(gm), pairs=True)
 
 
 # ---------------------------------------------------------------- f. data_reduce_kernel beyond one pass ----------------------------------------------------------------

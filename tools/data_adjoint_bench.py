@@ -17,7 +17,6 @@ A last line is the same as JSON.  Needs a GPU: there is no fallback.
     python tools/data_adjoint_bench.py [--batch 4096] [--steps 20] [--dtype f32] [--reps 7] [--config 3] [--cot-space state|tangent]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
@@ -56,7 +55,6 @@ def main():
     rng = np.random.default_rng(1)
     U = np.stack([u * rng.uniform(0.5, 1.0) for _ in range(H)])
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x.astype(gm.np_dtype))).cuda()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     z0d, Ud = dev(z0), dev(U)
     Z = torch.empty((H, B, nz), dtype=tdt, device="cuda"); st = torch.empty((H, B), dtype=torch.int32, device="cuda")
     DZ = torch.empty((H, B, nx, nx), dtype=tdt, device="cuda"); DU = torch.empty((H, B, max(nu, 1), nx), dtype=tdt, device="cuda")
@@ -65,23 +63,23 @@ def main():
     G = dev(rng.standard_normal((H, B, nz if cs else nx)))
     gU = torch.empty((H, B, max(nu, 1)), dtype=tdt, device="cuda"); gz = torch.empty((B, nx), dtype=tdt, device="cuda")
     gte = torch.empty((B, nth), dtype=tdt, device="cuda"); gt = torch.empty((nth,), dtype=tdt, device="cuda"); gz2 = torch.empty((B, nx), dtype=tdt, device="cuda")
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = api.torch_stream()
     L = api.lib()
 
     def record():
-        api._chk(L.dojo_rollout_record_dev(gm.h, ptr(z0d), ptr(Ud), H, ptr(Z), ptr(st), ptr(DZ), ptr(DU), stream))
+        api._chk(L.dojo_rollout_record_dev(gm.h, api.addr(z0d), api.addr(Ud), H, api.addr(Z), api.addr(st), api.addr(DZ), api.addr(DU), stream))
 
     def data_record():
-        api._chk(L.dojo_rollout_data_record_dev(gm.h, ptr(z0d), ptr(Ud), H, ptr(Z), ptr(st), ptr(DZ), ptr(DU), ptr(DC), stream))
+        api._chk(L.dojo_rollout_data_record_dev(gm.h, api.addr(z0d), api.addr(Ud), H, api.addr(Z), api.addr(st), api.addr(DZ), api.addr(DU), api.addr(DC), stream))
 
     def sweep():
-        api._chk(L.dojo_rollout_adjoint_dev(gm.h, H, ptr(DZ), ptr(DU), ptr(G), cs, ptr(Z), ptr(st), ptr(gU), ptr(gz), stream))
+        api._chk(L.dojo_rollout_adjoint_dev(gm.h, H, api.addr(DZ), api.addr(DU), api.addr(G), cs, api.addr(Z), api.addr(st), api.addr(gU), api.addr(gz), stream))
 
     def data_sweep():
-        api._chk(L.dojo_rollout_data_adjoint_dev(gm.h, H, ptr(DZ), ptr(DC), ptr(G), cs, ptr(Z), ptr(st), ptr(gte), ptr(gt), ptr(gz2), stream))
+        api._chk(L.dojo_rollout_data_adjoint_dev(gm.h, H, api.addr(DZ), api.addr(DC), api.addr(G), cs, api.addr(Z), api.addr(st), api.addr(gte), api.addr(gt), api.addr(gz2), stream))
 
     def data_sweep_env():
-        api._chk(L.dojo_rollout_data_adjoint_dev(gm.h, H, ptr(DZ), ptr(DC), ptr(G), cs, ptr(Z), ptr(st), ptr(gte), None, ptr(gz2), stream))
+        api._chk(L.dojo_rollout_data_adjoint_dev(gm.h, H, api.addr(DZ), api.addr(DC), api.addr(G), cs, api.addr(Z), api.addr(st), api.addr(gte), None, api.addr(gz2), stream))
 
     def timed(f):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

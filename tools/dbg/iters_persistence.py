@@ -1,5 +1,5 @@
 """does a solve that was long in one step stay long in the next?  (what dojo_set_dispatch_order's prediction rests on)"""
-import os, sys, ctypes as C
+import os, sys
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "dojo.jl_amd", "host"), ROOT]
@@ -15,9 +15,8 @@ dev = torch.device("cuda:0"); torch.cuda.init()
 gm = api.BatchedMechanism(spec, B, dtype="f32", device=0); gm.set_async(True)
 z = torch.tensor(Z, dtype=torch.float32, device=dev); zn = torch.empty_like(z); u = torch.tensor(U, dtype=torch.float32, device=dev)
 it = torch.zeros((K, B), dtype=torch.int32, device=dev); st = torch.zeros(B, dtype=torch.int32, device=dev)
-p = lambda t: C.c_void_p(t.data_ptr())
 for k in range(K):
-    api._chk(api.lib().dojo_step_dev(gm.h, p(z), p(u), p(zn), p(st), p(it[k]), C.c_void_p(0), C.c_void_p(0), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    api._chk(api.lib().dojo_step_dev(gm.h, api.addr(z), api.addr(u), api.addr(zn), api.addr(st), api.addr(it[k]), None, None, api.torch_stream()))
     z, zn = zn, z
 gm.join(torch.cuda.current_stream().cuda_stream); torch.cuda.synchronize()
 I = it.cpu().numpy().astype(float)

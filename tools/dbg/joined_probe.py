@@ -1,5 +1,5 @@
 """joined-per-step time of one handle under different group settings (after an asynchronous phase, like bench.py's sync leg)"""
-import os, sys, time, ctypes as C
+import os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "dojo.jl_amd", "host"), ROOT]
@@ -15,10 +15,9 @@ z = torch.tensor(Z, dtype=torch.float32, device=dev); zn = torch.empty_like(z); 
 nx = 12 * spec.Nb
 dz = torch.empty((B, nx, nx), dtype=torch.float32, device=dev); du = torch.empty((B, spec.nu, nx), dtype=torch.float32, device=dev)
 st = torch.empty(B, dtype=torch.int32, device=dev); it = torch.empty(B, dtype=torch.int32, device=dev)
-p = lambda t: C.c_void_p(t.data_ptr())
 def step():
     global z, zn
-    api._chk(lib.dojo_step_dev(gm.h, p(z), p(u), p(zn), p(st), p(it), p(dz), p(du), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    api._chk(lib.dojo_step_dev(gm.h, api.addr(z), api.addr(u), api.addr(zn), api.addr(st), api.addr(it), api.addr(dz), api.addr(du), api.torch_stream()))
     z, zn = zn, z
 zsave = None
 def timed(n, label):

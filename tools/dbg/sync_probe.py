@@ -1,5 +1,5 @@
 """joined steps (a barrier per step) of the Ant batch with / without the iteration cap: wall time per step, status / iteration statistics"""
-import ctypes as C, os, sys, time
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [os.path.join(ROOT, "dojo.jl_amd", "host")]
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
@@ -22,11 +22,11 @@ dz = torch.empty((B, spec.nx, spec.nx), dtype=torch.float32, device=dev); du = t
 gm = api.BatchedMechanism(spec, B, dtype="f32")
 gm.set_iteration_cap(cap)
 if groups > 0: gm.set_groups(groups)
-lib = api.lib(); p = lambda t: C.c_void_p(t.data_ptr())
+lib = api.lib()
 ts = []
 for k in range(K + 3):
     torch.cuda.synchronize(); t0 = time.perf_counter()
-    api._chk(lib.dojo_step_dev(gm.h, p(z), p(U[k]), p(zn), p(st), p(it), p(dz), p(du), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    api._chk(lib.dojo_step_dev(gm.h, api.addr(z), api.addr(U[k]), api.addr(zn), api.addr(st), api.addr(it), api.addr(dz), api.addr(du), api.torch_stream()))
     torch.cuda.synchronize(); ts.append(1e3 * (time.perf_counter() - t0))
     z, zn = zn, z
     if k >= 3: print("step %2d: %.3f ms  max iters %d  >16: %d  failed %d  mean %.2f" % (k, ts[-1], int(it.max()), int((it > 16).sum()), int((st != 0).sum()), float(it.float().mean())))

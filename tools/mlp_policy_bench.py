@@ -63,9 +63,8 @@ def main():
     w = 4 if a.dtype == "f32" else 8
     rng = np.random.default_rng(1)
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(np.asarray(x).astype(gm.np_dtype))).cuda()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     e = lambda *shape, dt=tdt: torch.empty(shape, dtype=dt, device="cuda")
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = api.torch_stream()
     L = api.lib()
 
     def theta(lead):
@@ -96,12 +95,12 @@ def main():
     mlp_s = api.mlp_policy_struct(th_s.data_ptr(), mean.data_ptr(), scale.data_ptr(), Uff.data_ptr(), 0, act_off, widths)
     mlp_e = api.mlp_policy_struct(th_e.data_ptr(), mean.data_ptr(), scale.data_ptr(), Uff.data_ptr(), 1, act_off, widths)
     aff_e = api.DojoPolicy(W_e.data_ptr(), b_e.data_ptr(), mean.data_ptr(), scale.data_ptr(), Uff.data_ptr(), 1, act_off, na, 0, 0, 0)
-    closed_s = lambda: api._chk(L.dojo_rollout_mlp_dev(gm.h, ptr(z0), C.byref(mlp_s), H, ptr(Z), ptr(OBS), ptr(U), ptr(ACT), ptr(st), stream))
-    closed_e = lambda: api._chk(L.dojo_rollout_mlp_dev(gm.h, ptr(z0), C.byref(mlp_e), H, ptr(Z), ptr(OBS), ptr(U), ptr(ACT), ptr(st), stream))
-    affine = lambda: api._chk(L.dojo_rollout_policy_dev(gm.h, ptr(z0), C.byref(aff_e), H, ptr(Z), ptr(OBS), ptr(U), ptr(st), stream))
+    closed_s = lambda: api._chk(L.dojo_rollout_mlp_dev(gm.h, api.addr(z0), C.byref(mlp_s), H, api.addr(Z), api.addr(OBS), api.addr(U), api.addr(ACT), api.addr(st), stream))
+    closed_e = lambda: api._chk(L.dojo_rollout_mlp_dev(gm.h, api.addr(z0), C.byref(mlp_e), H, api.addr(Z), api.addr(OBS), api.addr(U), api.addr(ACT), api.addr(st), stream))
+    affine = lambda: api._chk(L.dojo_rollout_policy_dev(gm.h, api.addr(z0), C.byref(aff_e), H, api.addr(Z), api.addr(OBS), api.addr(U), api.addr(st), stream))
     closed_s(); torch.cuda.synchronize()                        # warm-up: code objects, workspaces, the streams of the environment groups
     Urec = U.clone(); solved = int((st == 0).sum().item())
-    open_loop = lambda: api._chk(L.dojo_rollout_dev(gm.h, ptr(z0), ptr(Urec), H, ptr(Z), ptr(st), stream))
+    open_loop = lambda: api._chk(L.dojo_rollout_dev(gm.h, api.addr(z0), api.addr(Urec), H, api.addr(Z), api.addr(st), stream))
     for f in (open_loop, closed_e, affine):
         f(); torch.cuda.synchronize()
     ta, tb, tc, td = [], [], [], []
@@ -148,7 +147,7 @@ def main():
                                                 Go.data_ptr(), gW.data_ptr(), gb.data_ptr(), gU.data_ptr(), gz.data_ptr(), 1, 0)
     ms, me, as_, ae = madj(gth_s), madj(gth_e), aadj(gW_s, gb_s), aadj(gW_e, gb_e)
     legs = [
-        ("a", lambda: api._chk(L.dojo_rollout_mlp_record_dev(gm.h, ptr(z0), C.byref(mlp_s), H, ptr(Z), ptr(OBS), ptr(U), ptr(ACT), ptr(st), ptr(DZ), ptr(DU), stream))),
+        ("a", lambda: api._chk(L.dojo_rollout_mlp_record_dev(gm.h, api.addr(z0), C.byref(mlp_s), H, api.addr(Z), api.addr(OBS), api.addr(U), api.addr(ACT), api.addr(st), api.addr(DZ), api.addr(DU), stream))),
         ("b", lambda: api._chk(L.dojo_rollout_mlp_adjoint_dev(gm.h, C.byref(mlp_s), H, C.byref(ms), stream))),
         ("c", lambda: api._chk(L.dojo_rollout_mlp_adjoint_dev(gm.h, C.byref(mlp_e), H, C.byref(me), stream))),
         ("d", lambda: api._chk(L.dojo_rollout_policy_adjoint_dev(gm.h, C.byref(aff_s), H, C.byref(as_), stream))),

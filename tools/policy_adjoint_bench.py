@@ -54,7 +54,6 @@ def main():
     z0, _ = d.synthetic_inputs(spec, B)
     rng = np.random.default_rng(1)
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x.astype(gm.np_dtype))).cuda()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     Bw = 1 if a.shared else B
     U_ff = np.zeros((H, B, nu)); U_ff[:, :, act_off:] = 0.2 * rng.standard_normal((H, B, na))
     z0d, Wd, bd = dev(z0), dev(0.1 * rng.standard_normal((Bw, na, nobs))), dev(0.1 * rng.standard_normal((Bw, na)))
@@ -68,17 +67,17 @@ def main():
     gU2, gz2 = e(H, B, nu), e(B, nx)
     adj = api.DojoPolicyAdjoint(DZ.data_ptr(), DU.data_ptr(), OBS.data_ptr(), st.data_ptr(), z0d.data_ptr(), Z.data_ptr(), None, G.data_ptr(), Gu.data_ptr(),
                                 Go.data_ptr(), gW.data_ptr(), gb.data_ptr(), gU.data_ptr(), gz.data_ptr(), 1, 0)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = api.torch_stream()
     L = api.lib()
 
     def forward():
-        api._chk(L.dojo_rollout_policy_record_dev(gm.h, ptr(z0d), C.byref(pol), H, ptr(Z), ptr(OBS), ptr(U), ptr(st), ptr(DZ), ptr(DU), stream))
+        api._chk(L.dojo_rollout_policy_record_dev(gm.h, api.addr(z0d), C.byref(pol), H, api.addr(Z), api.addr(OBS), api.addr(U), api.addr(st), api.addr(DZ), api.addr(DU), stream))
 
     def backward():
         api._chk(L.dojo_rollout_policy_adjoint_dev(gm.h, C.byref(pol), H, C.byref(adj), stream))
 
     def open_loop():
-        api._chk(L.dojo_rollout_adjoint_dev(gm.h, H, ptr(DZ), ptr(DU), ptr(G), 1, ptr(Z), ptr(st), ptr(gU2), ptr(gz2), stream))
+        api._chk(L.dojo_rollout_adjoint_dev(gm.h, H, api.addr(DZ), api.addr(DU), api.addr(G), 1, api.addr(Z), api.addr(st), api.addr(gU2), api.addr(gz2), stream))
 
     def timed(f):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

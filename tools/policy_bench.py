@@ -51,24 +51,23 @@ def main():
     tdt = torch.float32 if a.dtype == "f32" else torch.float64
     rng = np.random.default_rng(1)
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(np.asarray(x).astype(gm.np_dtype))).cuda()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     z0 = dev(d.synthetic_inputs(spec, B)[0])
     W = dev(0.1 * rng.standard_normal((B, na, nobs))); mean = dev(0.1 * rng.standard_normal(nobs)); scale = dev(rng.uniform(0.5, 1.5, nobs))
     Uff = np.zeros((H, B, nu)); Uff[:, :, act_off:] = 0.2 * rng.standard_normal((H, B, na)); Uff = dev(Uff)
     Z = torch.empty((H, B, nz), dtype=tdt, device="cuda"); st = torch.empty((H, B), dtype=torch.int32, device="cuda")
     OBS = torch.empty((H + 1, B, nobs), dtype=tdt, device="cuda"); U = torch.empty((H, B, nu), dtype=tdt, device="cuda")
     pol = api.DojoPolicy(W.data_ptr(), None, mean.data_ptr(), scale.data_ptr(), Uff.data_ptr(), 1, act_off, na, 1, 0, 0)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = api.torch_stream()
     L = api.lib()
 
     def closed():
-        api._chk(L.dojo_rollout_policy_dev(gm.h, ptr(z0), C.byref(pol), H, ptr(Z), ptr(OBS), ptr(U), ptr(st), stream))
+        api._chk(L.dojo_rollout_policy_dev(gm.h, api.addr(z0), C.byref(pol), H, api.addr(Z), api.addr(OBS), api.addr(U), api.addr(st), stream))
 
     closed(); torch.cuda.synchronize()                          # warm-up: code objects, workspaces, the streams of the environment groups
     Urec = U.clone(); solved = int((st == 0).sum().item())
 
     def open_loop():
-        api._chk(L.dojo_rollout_dev(gm.h, ptr(z0), ptr(Urec), H, ptr(Z), ptr(st), stream))
+        api._chk(L.dojo_rollout_dev(gm.h, api.addr(z0), api.addr(Urec), H, api.addr(Z), api.addr(st), stream))
 
     def timed(f):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

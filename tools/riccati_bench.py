@@ -112,7 +112,6 @@ def measure(a, config, B, act_off, na, gated):
     rng = np.random.default_rng(1)
     U = np.stack([u * rng.uniform(0.5, 1.0) for _ in range(H)])
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(np.asarray(x).astype(gm.np_dtype))).cuda()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     empty = lambda *shape: torch.empty(shape, dtype=tdt, device="cuda")
     X = empty(H + 1, B, n); X[0] = dev(gm.maximal_to_minimal(z0.astype(gm.np_dtype)))
     Ud = dev(U)
@@ -121,14 +120,14 @@ def measure(a, config, B, act_off, na, gated):
     lx, lu = dev(rng.standard_normal((H + 1, B, n))), dev(rng.standard_normal((H, B, na)))
     lxx = torch.eye(n, dtype=tdt, device="cuda").expand(H + 1, B, n, n).contiguous(); luu = torch.eye(na, dtype=tdt, device="cuda").expand(H, B, na, na).contiguous()
     K, kff, dV, fail = empty(H, B, na, n), empty(H, B, na), empty(B, 2), torch.empty(B, dtype=torch.int32, device="cuda")
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = api.torch_stream()
     L = api.lib()
     rec = api.DojoRiccati(A.data_ptr(), Bm.data_ptr(), st.data_ptr(), lx.data_ptr(), lu.data_ptr(), lxx.data_ptr(), luu.data_ptr(), None, None,
                           K.data_ptr(), kff.data_ptr(), fail.data_ptr(), dV.data_ptr(), None, None, act_off, na)
 
     def linearize():
         for k in range(H):
-            api._chk(L.dojo_minimal_gradients_dev(gm.h, ptr(X[k]), ptr(Ud[k]), ptr(X[k + 1]), ptr(st[k]), ptr(it), ptr(A[k]), ptr(Bm[k]), stream))
+            api._chk(L.dojo_minimal_gradients_dev(gm.h, api.addr(X[k]), api.addr(Ud[k]), api.addr(X[k + 1]), api.addr(st[k]), api.addr(it), api.addr(A[k]), api.addr(Bm[k]), stream))
 
     def kernel():
         api._chk(L.dojo_riccati_dev(gm.h, H, C.byref(rec), stream))

@@ -14,7 +14,6 @@ Conditions (the tool exits with status 1 when one is missed): (d) <= 0.25 (a);  
     python tools/tangent_bench.py [--batch 4096] [--steps 20] [--dtype f32] [--reps 7] [--config 3]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
@@ -50,7 +49,6 @@ def main():
     rng = np.random.default_rng(1)
     U = np.stack([u * rng.uniform(0.5, 1.0) for _ in range(H)])
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x.astype(gm.np_dtype))).cuda()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     empty = lambda *shape: torch.empty(shape, dtype=tdt, device="cuda")
     z0d, Ud = dev(z0), dev(U)
     Z = empty(H, B, nz); st = torch.empty((H, B), dtype=torch.int32, device="cuda")
@@ -60,18 +58,18 @@ def main():
     TS = (1, 4, 8)
     dz0 = torch.randn((B, max(TS), nx), dtype=tdt, device="cuda")           # [B][T][nx] of a smaller T is not a slice of it: one buffer per T
     tan = {T: (dz0[:, :T].contiguous(), torch.randn((H, B, T, max(nu, 1)), dtype=tdt, device="cuda"), empty(H, B, T, nz)) for T in TS}
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = api.torch_stream()
     L = api.lib()
 
     def forward():
-        api._chk(L.dojo_rollout_data_record_dev(gm.h, ptr(z0d), ptr(Ud), H, ptr(Z), ptr(st), ptr(DZ), ptr(DU), ptr(DC), stream))
+        api._chk(L.dojo_rollout_data_record_dev(gm.h, api.addr(z0d), api.addr(Ud), H, api.addr(Z), api.addr(st), api.addr(DZ), api.addr(DU), api.addr(DC), stream))
 
     def backward():
-        api._chk(L.dojo_rollout_adjoint_dev(gm.h, H, ptr(DZ), ptr(DU), ptr(G), 1, ptr(Z), ptr(st), ptr(gU), ptr(gz), stream))
+        api._chk(L.dojo_rollout_adjoint_dev(gm.h, H, api.addr(DZ), api.addr(DU), api.addr(G), 1, api.addr(Z), api.addr(st), api.addr(gU), api.addr(gz), stream))
 
     def tangent(T):
         d0, dU, out = tan[T]
-        return lambda: api._chk(L.dojo_rollout_tangent_dev(gm.h, H, T, ptr(DZ), ptr(DU), None, ptr(d0), ptr(dU) if nu else None, None, 1, ptr(Z), ptr(st), ptr(out), stream))
+        return lambda: api._chk(L.dojo_rollout_tangent_dev(gm.h, H, T, api.addr(DZ), api.addr(DU), None, api.addr(d0), api.addr(dU) if nu else None, None, 1, api.addr(Z), api.addr(st), api.addr(out), stream))
 
     def timed(f):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
