@@ -18,6 +18,8 @@
 #include "dojo_data_adjoint.hpp"
 #include "dojo_tangent.hpp"
 #include "dojo_riccati.hpp"
+#include "dojo_tracking.hpp"
+#include "../../include/dojo_hip_trajopt.h"
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -95,6 +97,9 @@ struct RolloutIO {
     const Controller* controller = nullptr; // closed loop (checked by the caller): the controls of step k are made on the group's stream, directly in front of the step, by the policy kernel ...
     void* OBS = nullptr;                    // ... [H+1][B][nobs] what it saw
     void* U_out = nullptr;                  // ... [H][B][nu] what it made (null: one [B][nu] buffer of the handle, a group's launches being serial)
+    // A rollout in minimal coordinates (the tracking controller, dojo_rollout_minimal_dev): z0 is the minimal state [B][2nu], OBS is X [H+1][B][2nu], Z is not recorded -- the
+    // controller re-projects X[k] into the handle's d_z, the step goes from there into d_zn, as dojo_step_minimal_dev does it -- and with
+    void *A = nullptr, *Bm = nullptr;       // ... [H][B][2nu][2nu], [H][B][2nu][nu] the chain of dojo_minimal_gradients_dev runs behind every step of a group, on its span and stream
 };
 struct Mode {
     int phase;
@@ -625,13 +630,20 @@ template <class TIO> int launch_fold_impulses(const DojoSim* s, const void* jf, 
 }
 // the chain of get_minimal_gradients! over the handle's d_dz, d_du: the min -> max Jacobian at (x, z) into d_jm, the max -> min blocks at d_zn (advanced by a step with
 // `advance`) into d_jb, d_jt = dz d_jm, and jx, ju = blocks * (d_jt, du).  The two Jacobian kernels per environment / per (environment, joint), the products one workgroup per environment.
-template <class TIO> int launch_minimal_chain(const DojoSim* s, const void* x, const void* z, int advance, void* jx, void* ju, hipStream_t st) {
-    const int B = s->B, Nb = s->M.Nb, nu = (int)s->M.nu, T_ = 256;
-    double *jm = (double*)s->d_jm, *jt = (double*)s->d_jt, *jb = (double*)s->d_jb;
-    TRY(launch_items(dj::ckern::min2max_jac_kernel<TIO>, B, 64, st, node_table(s), (const int*)s->d_order, Nb, nu, s->M.dt, B, (const TIO*)x, (const TIO*)z, jm));
-    TRY(launch_items(dj::ckern::max2min_jac_kernel<TIO>, (long long)B * Nb, T_, st, node_table(s), Nb, s->M.dt, B, (const TIO*)s->d_zn, advance, jb));
-    TRY(launch_items(dj::ckern::chain_mid_kernel<TIO>, (long long)B * T_, T_, st, 12 * Nb, 2 * nu, B, (const TIO*)s->d_dz, (const double*)jm, jt));
-    return launch_items(dj::ckern::chain_out_kernel<TIO>, (long long)B * T_, T_, st, node_table(s), Nb, nu, B, (const double*)jb, (const double*)jt, (const TIO*)s->d_du, (TIO*)jx, (TIO*)ju);
+// For the environments of `sp` on its stream: all pointers are batch-level, the kernels index from 0 and are given the span's slice of each (the workspaces are batch-sized, so
+// the groups of a rollout own disjoint slices of them).
+template <class TIO> int launch_minimal_chain(const DojoSim* s, const Span& sp, const void* x, const void* z, int advance, void* jx, void* ju) {
+    const int B = sp.nenv, Nb = s->M.Nb, nu = (int)s->M.nu, T_ = 256;
+    const size_t e0 = sp.env0, nx = 12 * (size_t)Nb, nm = 2 * (size_t)nu;
+    hipStream_t st = sp.stream;
+    double *jm = (double*)s->d_jm + e0 * nx * nm, *jt = (double*)s->d_jt + e0 * nx * nm, *jb = (double*)s->d_jb + e0 * Nb * 12 * 24;
+    const TIO *xs = (const TIO*)x + e0 * nm, *zs = (const TIO*)z + e0 * 13 * Nb, *zn = (const TIO*)s->d_zn + e0 * 13 * Nb;
+    const TIO *dz = (const TIO*)s->d_dz + e0 * nx * nx, *du = (const TIO*)s->d_du + e0 * nx * nu;
+    TRY(launch_items(dj::ckern::min2max_jac_kernel<TIO>, B, 64, st, node_table(s), (const int*)s->d_order, Nb, nu, s->M.dt, B, xs, zs, jm));
+    TRY(launch_items(dj::ckern::max2min_jac_kernel<TIO>, (long long)B * Nb, T_, st, node_table(s), Nb, s->M.dt, B, zn, advance, jb));
+    TRY(launch_items(dj::ckern::chain_mid_kernel<TIO>, (long long)B * T_, T_, st, 12 * Nb, 2 * nu, B, dz, (const double*)jm, jt));
+    return launch_items(dj::ckern::chain_out_kernel<TIO>, (long long)B * T_, T_, st, node_table(s), Nb, nu, B, (const double*)jb, (const double*)jt, du,
+                        (TIO*)jx + e0 * nm * nm, ju ? (TIO*)ju + e0 * nm * nu : nullptr);
 }
 
 // Launches the step (and IFT) kernels for the environments of `sp`; all pointers of `io` are the batch-level buffers.
@@ -1016,17 +1028,39 @@ int launch_mlp(const DojoSim* s, const DojoMlpPolicy& p, const dj::mlp::Shape& s
     return DOJO_OK;
 }
 
-// The controller of a closed-loop rollout, as rollout_core sees it: the affine policy or the network (exactly one is set), and what the network records
+// dojo_rollout_minimal_dev: the tracking controller of step k on the environments and the stream of `sp`.  z: the state the previous step left, or -- k = 0 -- the
+// initial MINIMAL state; x: X[k]; zproj: where the re-projected state goes, which step k reads.  X[k] by max2min_kernel (k = 0: a copy), the control law
+// (dojo_tracking.hpp), the re-projection by min2max_kernel: the two maps are the kernels of dojo_step_minimal_dev, which index environments from 0 and are given
+// the span's slice of every array.  The observation of the final state (u = null) is the first of the three alone.
+template <class TIO>
+int launch_tracking(const DojoSim* s, const DojoTracking& t, int k, const void* z, const void* uff, void* x, void* u, void* zproj, const Span& sp) {
+    const size_t B = s->B, Nb = s->M.Nb, nu = s->M.nu, n = 2 * nu, kB = (size_t)k * B, e0 = sp.env0;
+    TIO* const xs = (TIO*)x + e0 * n;
+    if (k == 0) HIPCHK(hipMemcpyAsync(xs, (const TIO*)z + e0 * n, (size_t)sp.nenv * n * sizeof(TIO), hipMemcpyDeviceToDevice, sp.stream));
+    else TRY(launch_items(dj::ckern::max2min_kernel<TIO>, (long long)sp.nenv * Nb, 256, sp.stream, node_table(s), (int)Nb, (int)nu, s->M.dt, sp.nenv, (const TIO*)z + e0 * 13 * Nb, xs, (int)n));
+    if (!u) return DOJO_OK;
+    auto row = [&](const void* p, size_t per) { return p ? (const TIO*)p + kB * per : nullptr; };      // step k of an input that is given
+    const dj::tracking::Args<TIO> A{(const TIO*)x, (const TIO*)uff, row(t.Xbar, n), row(t.K, (size_t)t.na * n), row(t.kff, (size_t)t.na), (const TIO*)t.alpha, (TIO*)u,
+                                    (int)sp.env0, sp.nenv, (int)nu, t.act_off, t.na};
+    hipLaunchKernelGGL((dj::tracking::rollout_tracking_kernel<TIO>), dim3((unsigned)((sp.nenv + dj::policy::ENVS - 1) / dj::policy::ENVS)), dim3(dj::policy::THREADS), 0, sp.stream, A);
+    HIPCHK(hipGetLastError());
+    return launch_items(dj::ckern::min2max_kernel<TIO>, sp.nenv, 64, sp.stream, node_table(s), (const int*)s->d_order, (int)Nb, (int)nu, s->M.dt, sp.nenv, (const TIO*)xs, (TIO*)zproj + e0 * 13 * Nb);
+}
+
+// The controller of a closed-loop rollout, as rollout_core sees it: the affine policy, the network or the tracking controller of a rollout in minimal coordinates
+// (exactly one is set), and what the network records
 struct Controller {
     const DojoPolicy* affine = nullptr;
     const DojoMlpPolicy* mlp = nullptr;
+    const DojoTracking* tracking = nullptr;
     dj::mlp::Shape shape{};
     double* ACT = nullptr;              // [H][B][nh] or null
-    bool contact_forces() const { return affine ? affine->contact_forces != 0 : mlp->contact_forces != 0; }
-    bool contact_init() const { return affine ? affine->contact_init != 0 : mlp->contact_init != 0; }
+    bool contact_forces() const { return tracking ? false : affine ? affine->contact_forces != 0 : mlp->contact_forces != 0; }
+    bool contact_init() const { return tracking ? false : affine ? affine->contact_init != 0 : mlp->contact_init != 0; }
 };
-// the controls of step k (u != null) or the observation of the final state (u = null, k = H)
-int launch_controller(const DojoSim* s, const Controller& c, int k, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp) {
+// the controls of step k (u != null) or the observation of the final state (u = null, k = H).  zproj: the tracking controller's re-projected state (the others make none)
+int launch_controller(const DojoSim* s, const Controller& c, int k, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp, void* zproj = nullptr) {
+    if (c.tracking) return by_dtype(s, [&](auto t) { return launch_tracking<decltype(t)>(s, *c.tracking, k, z, uff, obs, u, zproj, sp); });
     if (c.affine) return launch_policy_any(s, *c.affine, z, csg, uff, obs, u, sp);
     double* const act = (c.ACT && u) ? c.ACT + (size_t)k * s->B * c.shape.nh : nullptr;
     return by_dtype(s, [&](auto t) { return launch_mlp<decltype(t)>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp); });
@@ -1382,6 +1416,12 @@ static int ensure_rollout(DojoHandle s, const RolloutIO& io) {
     ENSURE(s->d_csg, B * (csg_per(s) * s->M.Nc + 1) * w);
     if (io.storage) ENSURE(s->d_res, B * 6 * s->M.Nb * w);
     if (io.controller && !io.U_out) ENSURE(s->d_pu, B * s->M.nu * w);
+    if (io.A) {                                      // (the buffers of dojo_minimal_gradients_dev, sized as there)
+        const size_t Nb = s->M.Nb, nx = 12 * Nb, nu = s->M.nu, nm = 2 * nu;
+        ENSURE(s->d_dz, B * nx * nx * w); ENSURE(s->d_du, B * nx * (nu + 1) * w);
+        ENSURE(s->d_jm, B * nx * (nm + 1) * sizeof(double)); ENSURE(s->d_jt, B * nx * (nm + 1) * sizeof(double));
+        ENSURE(s->d_jb, B * Nb * 12 * 24 * sizeof(double));
+    }
     return DOJO_OK;
 }
 
@@ -1395,6 +1435,14 @@ static int rollout_core(DojoHandle s, int32_t H, const RolloutIO& io, void* stre
     const Controller* pol = io.controller;
     const size_t nobs = pol ? 2 * nu + (pol->contact_forces() ? (size_t)s->M.Nc : 0) : 0;
     auto at = [](void* p, size_t offset) -> char* { return p ? (char*)p + offset : nullptr; };      // step k of an array that is recorded
+    // in minimal coordinates: the chain of dojo_minimal_gradients_dev for step k of a group into A[k], Bm[k], from the handle's d_dz, d_du that step has just written
+    const bool minimal = pol && pol->tracking, literal = io.A && s->grad_mode == DOJO_GRAD_REFERENCE;
+    auto minimal_chain = [&](int k, const Span& sp) {
+        const size_t kB = (size_t)k * B, n = 2 * nu;
+        const void* xj = at(io.OBS, (literal ? kB + B : kB) * n * w);                              // where the min -> max Jacobian is evaluated: X[k + 1] / X[k] ...
+        const void* zj = literal ? (const void*)s->d_zn : (const void*)s->d_z;                     // ... and the maximal state that belongs to it
+        return by_dtype(s, [&](auto t) { return launch_minimal_chain<decltype(t)>(s, sp, xj, zj, literal ? 1 : 0, at(io.A, kB * n * n * w), at(io.Bm, kB * n * nu * w)); });
+    };
     hipStream_t st = (hipStream_t)stream;
     const char* cur = (const char*)io.z0;   // the state a group's next step starts from; behind the loops: the last state (the same buffer for every group)
     int slot = -1; TRY(begin_timing(s, &slot, st));
@@ -1402,7 +1450,10 @@ static int rollout_core(DojoHandle s, int32_t H, const RolloutIO& io, void* stre
     // contains an environment that runs into max_iter (one wavefront, ~5x the mean step time) delays only itself while
     // the other groups' launches keep the GPU busy.  (ROCm runs at most GPU_MAX_HW_QUEUES streams concurrently.)
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight)
-    const size_t NG = group_count(s, H >= 2);
+    // With A, Bm the batch is one group on the caller's stream: min2max_jac_kernel keeps 8.9 KB of scratch per lane, and ROCr sizes a hardware queue's scratch for a
+    // full GPU of such wavefronts -- on the groups' internal queues as well that ends in HSA_STATUS_ERROR_OUT_OF_RESOURCES (group_count has the same rule for the
+    // builds with large scratch).  The chain then runs where dojo_minimal_gradients_dev runs it: one queue's worth of scratch.
+    const size_t NG = io.A ? 1 : group_count(s, H >= 2);
     const Partition P(B, NG);
     const Mode m = step_mode(s, NG, false, true);
     ForkGuard guard{s, st, NG > 1};
@@ -1413,20 +1464,27 @@ static int rollout_core(DojoHandle s, int32_t H, const RolloutIO& io, void* stre
         cur = (const char*)io.z0;
         for (int k = 0; k < H; ++k) {
             const size_t kB = (size_t)k * B;
-            char* nxt = io.Z ? at(io.Z, kB * nz * w) : (char*)((k & 1) ? s->d_z : s->d_zn);
+            char* nxt = io.Z ? at(io.Z, kB * nz * w) : (char*)((minimal || !(k & 1)) ? s->d_zn : s->d_z);
             const char* uk = nu ? at((void*)io.U, kB * nu * w) : nullptr;
             if (pol) {
                 char* upol = io.U_out ? at(io.U_out, kB * nu * w) : (char*)s->d_pu;
-                TRY(launch_controller(s, *pol, k, cur, (k > 0 || pol->contact_init()) ? s->d_csg : nullptr, uk, at(io.OBS, kB * nobs * w), upol, sp));
+                TRY(launch_controller(s, *pol, k, cur, (k > 0 || pol->contact_init()) ? s->d_csg : nullptr, uk, at(io.OBS, kB * nobs * w), upol, sp, minimal ? s->d_z : nullptr));
                 uk = upol;
+                if (minimal) cur = (const char*)s->d_z;      // the step starts from the re-projected X[k]
             }
+            // DOJO_GRAD_REFERENCE evaluates the chain of step k - 1 at X[k], which that controller has just written, and at the state step k - 1 left: in front of step k, which overwrites it
+            if (literal && k > 0) TRY(minimal_chain(k - 1, sp));
             int32_t* stk = io.status ? io.status + kB : nullptr;
-            TRY(launch_any(s, StepIO{cur, uk, nxt, stk, nullptr, at(io.DZ, kB * nx * nx * w), nu ? at(io.DU, kB * nx * nu * w) : nullptr, nullptr, at(io.storage, kB * 25 * s->M.Nb * w)}, sp, m));
+            void* const dzk = io.A ? s->d_dz : at(io.DZ, kB * nx * nx * w); void* const duk = io.A ? s->d_du : nu ? at(io.DU, kB * nx * nu * w) : nullptr;
+            TRY(launch_any(s, StepIO{cur, uk, nxt, stk, nullptr, dzk, duk, nullptr, at(io.storage, kB * 25 * s->M.Nb * w)}, sp, m));
             // (the same Mode: the same hand-off record, no timing slot -- m.slot is null --, and a launch with io.dc never reorders the dispatch)
             if (io.DC && s->M.Nc > 0) TRY(launch_any(s, StepIO{cur, uk, nxt, nullptr, nullptr, nullptr, nullptr, at(io.DC, kB * nx * 5 * s->M.Nc * w), nullptr}, sp, m));
+            // DOJO_GRAD_CONSISTENT evaluates it at X[k] and the step's input: behind the step, in front of the next controller, which overwrites that input
+            if (io.A && !literal) TRY(minimal_chain(k, sp));
             cur = nxt;
         }
         if (pol && io.OBS) TRY(launch_controller(s, *pol, H, cur, s->d_csg, nullptr, at(io.OBS, (size_t)H * B * nobs * w), nullptr, sp));      // the observation of the final state
+        if (literal) TRY(minimal_chain(H - 1, sp));
         if (NG > 1) { HIPCHK(hipEventRecord(s->gevents[gi], sp.stream)); HIPCHK(hipStreamWaitEvent(st, s->gevents[gi], 0)); }
     }
     TRY(end_timing(s, slot, false, H, st));
@@ -1746,6 +1804,49 @@ int dojo_riccati(DojoHandle s, int32_t H, const DojoRiccati* r) {
     d.K = dK.p; d.kff = dk.p; d.fail = (int32_t*)dF.p; d.dV = ddV.p; d.Vx = dVx.p; d.Vxx = dVxx.p;
     TRY(dojo_riccati_dev(s, H, &d, nullptr));
     return st.finish();      // (no state: the handle's own is left alone)
+}
+
+// ---- rollouts in minimal coordinates with the tracking controller (dojo_tracking.hpp, include/dojo_hip_trajopt.h): iLQR's forward pass and its linearization, one call each ----
+// what both entries refuse, before anything is allocated or launched
+static int refuse_tracking(DojoHandle s, int32_t H, const DojoTracking* t, const char* who) {
+    const std::string w_ = std::string(who) + ": ";
+    if (!s || !t) { g_err = w_ + "bad argument (the handle and the DojoTracking record are required)"; return DOJO_ERR_INVALID; }
+    if (H < 1) { g_err = w_ + "H must be >= 1"; return DOJO_ERR_INVALID; }
+    if (!t->x0 || !t->X || !t->U_out) { g_err = w_ + "x0, X and U_out must not be NULL"; return DOJO_ERR_INVALID; }
+    if (s->M.nu == 0) { g_err = w_ + "the mechanism has no inputs"; return DOJO_ERR_INVALID; }
+    if (t->na < 1 || t->act_off < 0 || (long long)t->act_off + t->na > (long long)s->M.nu) { g_err = w_ + "the controller must drive inputs act_off .. act_off + na - 1 inside 0 .. nu - 1, na >= 1"; return DOJO_ERR_INVALID; }
+    if ((t->A == nullptr) != (t->Bm == nullptr)) { g_err = w_ + "A and Bm must both be given or both be NULL"; return DOJO_ERR_INVALID; }
+    TRY(refuse_minimal(s, who));
+    if (t->A) TRY(refuse_record(s, who));
+    return DOJO_OK;      // (the controller keeps nothing in LDS: there is no shape it cannot hold)
+}
+
+int dojo_rollout_minimal_dev(DojoHandle s, int32_t H, const DojoTracking* t, void* stream) {
+    Enter enter_(s);
+    TRY(refuse_tracking(s, H, t, "dojo_rollout_minimal_dev"));
+    const DojoTracking tr = *t;      // (the caller's struct is read during the call only)
+    Controller c; c.tracking = &tr;
+    RolloutIO io; io.z0 = tr.x0; io.U = tr.Ubar; io.status = tr.status; io.controller = &c; io.OBS = tr.X; io.U_out = tr.U_out; io.A = tr.A; io.Bm = tr.Bm;
+    return rollout_core(s, H, io, stream);
+}
+
+// host pointers (the members of *t): upload, roll out on the device, download
+int dojo_rollout_minimal(DojoHandle s, int32_t H, const DojoTracking* t) {
+    Enter enter_(s);
+    TRY(refuse_tracking(s, H, t, "dojo_rollout_minimal"));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)t->na, HB = (size_t)H * B;
+    Staging st;
+    const auto &dx0 = st.input(B * n * w, t->x0), &dUb = st.input(HB * nu * w, t->Ubar), &dXb = st.input((HB + B) * n * w, t->Xbar);
+    const auto &dK = st.input(HB * m * n * w, t->K), &dk = st.input(HB * m * w, t->kff), &da = st.input(B * w, t->alpha);
+    const auto &dX = st.output((HB + B) * n * w, t->X), &dU = st.output(HB * nu * w, t->U_out), &dS = st.output(HB * sizeof(int32_t), t->status);
+    const auto &dA = st.output(HB * n * n * w, t->A), &dB = st.output(HB * n * nu * w, t->Bm);
+    TRY(st.allocate());
+    DojoTracking d = *t;
+    d.x0 = dx0.p; d.Ubar = dUb.p; d.Xbar = dXb.p; d.K = dK.p; d.kff = dk.p; d.alpha = da.p;
+    d.X = dX.p; d.U_out = dU.p; d.status = (int32_t*)dS.p; d.A = dA.p; d.Bm = dB.p;
+    TRY(dojo_rollout_minimal_dev(s, H, &d, nullptr));
+    return st.finish();      // (the handle keeps the last step's states itself)
 }
 
 // ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----
@@ -2200,7 +2301,7 @@ int dojo_minimal_gradients_dev(DojoHandle s, const void* x, const void* u, void*
     const bool literal = s->grad_mode == DOJO_GRAD_REFERENCE;
     const void* xj = literal ? (const void*)x_next : x;                // where the min -> max Jacobian is evaluated ...
     const void* zj = literal ? (const void*)s->d_zn : (const void*)s->d_z;   // ... and the maximal state that belongs to it
-    return by_dtype(s, [&](auto t) { return launch_minimal_chain<decltype(t)>(s, xj, zj, literal ? 1 : 0, jx, ju, st); });
+    return by_dtype(s, [&](auto t) { return launch_minimal_chain<decltype(t)>(s, whole_batch(s, st), xj, zj, literal ? 1 : 0, jx, ju); });
 }
 int dojo_minimal_gradients(DojoHandle s, const void* x, const void* u, void* x_next, int32_t* status, int32_t* iters, void* jx, void* ju) {
     Enter enter_(s);

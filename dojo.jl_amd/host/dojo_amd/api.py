@@ -56,6 +56,9 @@ _SIGNATURES = {
     "dojo_kernel_time_totals": (C.c_int, "ppppi"),
 }
 EXPORTED_SYMBOLS = list(_SIGNATURES)
+# include/dojo_hip_trajopt.h, the second public header, in the same notation
+_TRAJOPT_SIGNATURES = {"dojo_rollout_minimal_dev": (C.c_int, "pipp"), "dojo_rollout_minimal": (C.c_int, "pip")}
+TRAJOPT_SYMBOLS = list(_TRAJOPT_SIGNATURES)
 
 
 def lib():
@@ -64,7 +67,7 @@ def lib():
         if not os.path.exists(_LIB_PATH):
             raise DojoError("libdojo_hip.so not built (run __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(_LIB_PATH)
-        for name, (restype, args) in _SIGNATURES.items():
+        for name, (restype, args) in {**_SIGNATURES, **_TRAJOPT_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, [_KINDS[k] for k in args]
         _lib = L
@@ -108,6 +111,13 @@ class DojoRiccati(C.Structure):
     _fields_ = [("A", C.c_void_p), ("Bm", C.c_void_p), ("status", C.c_void_p), ("lx", C.c_void_p), ("lu", C.c_void_p), ("lxx", C.c_void_p), ("luu", C.c_void_p),
                 ("lux", C.c_void_p), ("mu", C.c_void_p), ("K", C.c_void_p), ("kff", C.c_void_p), ("fail", C.c_void_p), ("dV", C.c_void_p), ("Vx", C.c_void_p),
                 ("Vxx", C.c_void_p), ("act_off", C.c_int32), ("na", C.c_int32)]
+
+
+class DojoTracking(C.Structure):
+    """include/dojo_hip_trajopt.h `DojoTracking`: the inputs (x0, the reference Ubar / Xbar, the gains K / kff, the step lengths alpha) and the outputs (X, U_out, status
+    and -- both or neither -- the Jacobians A, Bm) of a rollout in minimal coordinates; device pointers for dojo_rollout_minimal_dev, host pointers for dojo_rollout_minimal"""
+    _fields_ = [("x0", C.c_void_p), ("Ubar", C.c_void_p), ("Xbar", C.c_void_p), ("K", C.c_void_p), ("kff", C.c_void_p), ("alpha", C.c_void_p),
+                ("X", C.c_void_p), ("U_out", C.c_void_p), ("status", C.c_void_p), ("A", C.c_void_p), ("Bm", C.c_void_p), ("act_off", C.c_int32), ("na", C.c_int32)]
 
 
 MLP_MAX_LAYERS = 4      # DOJO_MLP_MAX_LAYERS
@@ -495,6 +505,28 @@ class BatchedMechanism:
         r = DojoRiccati(*map(addr, (A, Bm, status, lx, lu, lxx, luu, lux, mu, K, kff, fail, dV, Vx, Vxx)), int(act_off), na)
         _chk(lib().dojo_riccati(self.h, H, C.byref(r)))
         return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
+
+    def rollout_minimal(self, x0, steps=None, Ubar=None, Xbar=None, K=None, kff=None, alpha=None, act_off=0, na=None, jacobians=False):
+        """dojo_rollout_minimal (host arrays): H steps in minimal coordinates from x0 [B,n], n = 2 nu, under the tracking controller
+        u_k = Ubar[k] + E (alpha kff[k] + K[k] (x_k - Xbar[k])) evaluated on the device between the steps.  Ubar [H,B,nu], Xbar [H+1,B,n], K [H,B,na,n], kff [H,B,na]
+        (the outputs of `riccati`), alpha [B]; each may be None (zeros; alpha: ones).  The horizon is that of Ubar, K or kff, or `steps`.  The controller drives the
+        inputs act_off .. act_off + na - 1 (na = nu - act_off by default).  -> (X [H+1,B,n], U [H,B,nu], status [H,B]) and, with jacobians, A [H,B,n,n], Bm [H,B,n,nu]:
+        `minimal_gradients`' jx, ju of every step, in the handle's gradient mode."""
+        B, nu = self.batch, self.spec.nu; n = 2 * nu
+        na = int(nu - act_off if na is None else na)
+        Hs = [np.shape(a)[0] for a in (Ubar, K, kff) if a is not None] + ([int(steps)] if steps is not None else [])
+        if not Hs:
+            raise ValueError("rollout_minimal needs the horizon: Ubar, K, kff or steps")
+        H = int(Hs[0])
+        if any(int(h) != H for h in Hs):
+            raise ValueError("Ubar, K, kff and steps disagree about the horizon: %s" % Hs)
+        opt = lambda a, shape: None if a is None else self._arr(a, shape)
+        ins = (self._arr(x0, (B, n)), opt(Ubar, (H, B, nu)), opt(Xbar, (H + 1, B, n)), opt(K, (H, B, na, n)), opt(kff, (H, B, na)), opt(alpha, (B,)))
+        X = np.empty((H + 1, B, n), self.np_dtype); U = np.empty((H, B, nu), self.np_dtype); st = np.empty((H, B), np.int32)
+        A = np.empty((H, B, n, n), self.np_dtype) if jacobians else None; Bm = np.empty((H, B, n, nu), self.np_dtype) if jacobians else None
+        t = DojoTracking(*map(addr, ins + (X, U, st, A, Bm)), int(act_off), na)
+        _chk(lib().dojo_rollout_minimal(self.h, H, C.byref(t)))
+        return (X, U, st, A, Bm) if jacobians else (X, U, st)
 
     def rollout_policy(self, z0, W, steps, bias=None, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):
         """Closed-loop rollout (dojo_rollout_policy): simulate! with the affine feedback policy u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale))

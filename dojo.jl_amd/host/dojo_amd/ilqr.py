@@ -3,12 +3,14 @@ the Riccati backward pass are the library's kernels).  The reference's examples/
 the same loop for B environments at once -- one trajectory, one regularisation and one line search per environment, one launch per stage for the whole batch.
 
     X, A, Bm, status = linearize_rollout(gm, x0, U)                   # H calls of dojo_minimal_gradients_dev, writing into slices of A and Bm
+    X, A, Bm, status = linearize_rollout_fused(gm, x0, U)             # the same as ONE call of dojo_rollout_minimal_dev, no join of the environment groups inside
+    X, U, status = forward_pass_fused(gm, Xbar, Ubar, K, kff, a, ..)  # the closed-loop rollout around (Xbar, Ubar) for the step lengths a [B], ONE call
     K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu)           # ONE launch of dojo_riccati_dev for all H steps
     res = solve(gm, x0, U0, QuadraticCost(Q, R, Qf, x_goal), iters=10)
 
 Everything is enqueued on torch's current stream.  The driver reads one flag per trial step length (have all environments accepted?) and nothing else.
-Not here (include/dojo_hip.h, "Batched iLQR"): the forward pass as one fused call, costs shared across the batch, control limits, second-order dynamics terms,
-constraints, kinematic loops."""
+Not here (include/dojo_hip.h, "Batched iLQR"; include/dojo_hip_trajopt.h): costs shared across the batch, control limits, second-order dynamics terms, constraints,
+running the step lengths of a line search side by side, kinematic loops."""
 import ctypes as C
 
 import torch
@@ -112,8 +114,42 @@ def replay(gm, x0, U):
     return X
 
 
+def rollout_minimal(gm, x0, Ubar, Xbar=None, K=None, kff=None, alpha=None, act_off=0, na=None, jacobians=False):
+    """dojo_rollout_minimal_dev on device tensors: ONE call for the H steps from x0 [B,n] under u_k = Ubar[k] + E (alpha kff[k] + K[k] (x_k - Xbar[k])), every
+    environment group at its own pace.  Ubar [H,B,nu], Xbar [H+1,B,n], K [H,B,na,n], kff [H,B,na] (riccati's outputs), alpha [B]; each of the last four may be None
+    (zeros; alpha: ones).  -> X [H+1,B,n], U [H,B,nu], status [H,B] int32 and, with jacobians, A [H,B,n,n], Bm [H,B,n,nu]: what H calls of
+    dojo_step_minimal_dev / dojo_minimal_gradients_dev at (X[k], U[k]) give, bit for bit."""
+    B, nu = gm.batch, gm.spec.nu; n, dt = 2 * nu, _dtype(gm)
+    if Ubar.dim() != 3:
+        raise ValueError("Ubar must be [H, B, nu]")
+    H = int(Ubar.shape[0]); na = int(nu - act_off if na is None else na)
+    x0 = _want(x0, "x0", dt, (B, n)); Ubar = _want(Ubar, "Ubar", dt, (H, B, nu)); Xbar = _want(Xbar, "Xbar", dt, (H + 1, B, n))
+    K = _want(K, "K", dt, (H, B, na, n)); kff = _want(kff, "kff", dt, (H, B, na)); alpha = _want(alpha, "alpha", dt, (B,))
+    dev = x0.device
+    X = torch.empty((H + 1, B, n), dtype=dt, device=dev); U = torch.empty((H, B, nu), dtype=dt, device=dev)
+    status = torch.empty((H, B), dtype=torch.int32, device=dev)
+    A = torch.empty((H, B, n, n), dtype=dt, device=dev) if jacobians else None; Bm = torch.empty((H, B, n, nu), dtype=dt, device=dev) if jacobians else None
+    t = api.DojoTracking(*map(api.addr, (x0, Ubar, Xbar, K, kff, alpha, X, U, status, A, Bm)), int(act_off), na)
+    api._chk(api.lib().dojo_rollout_minimal_dev(gm.h, H, C.byref(t), api.torch_stream(dev)))
+    return (X, U, status, A, Bm) if jacobians else (X, U, status)
+
+
+def linearize_rollout_fused(gm, x0, U):
+    """linearize_rollout as one call of dojo_rollout_minimal_dev: the same X, A, Bm, status, bit for bit"""
+    X, _, status, A, Bm = rollout_minimal(gm, x0, U, na=1, jacobians=True)
+    return X, A, Bm, status
+
+
+def forward_pass_fused(gm, Xbar, Ubar, K, kff, alpha, act_off, na):
+    """forward_pass as one call of dojo_rollout_minimal_dev, the feedback law evaluated on the device in fp64; alpha: a float or a [B] tensor (one step length per
+    environment) -> X [H+1,B,n], U [H,B,nu], status [H,B]"""
+    if not torch.is_tensor(alpha):
+        alpha = torch.full((gm.batch,), float(alpha), dtype=_dtype(gm), device=Xbar.device)
+    return rollout_minimal(gm, Xbar[0].contiguous(), Ubar, Xbar, K, kff, alpha, act_off, na)
+
+
 def solve(gm, x0, U0, cost, iters, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625, 0.0078125),
-          mu_init=0.0, mu_min=1e-6, mu_grow=10.0, mu_shrink=0.1):
+          mu_init=0.0, mu_min=1e-6, mu_grow=10.0, mu_shrink=0.1, fused=False):
     """iLQR for B environments.  x0 [B,n], U0 [H,B,nu] (all inputs; the policy drives act_off .. act_off + na - 1, na = nu - act_off by default, the others keep
     U0's values), cost: an object with value(X, U_act) -> J [B] and quadratize(X, U_act) -> (lx, lu, lxx, luu, lux).  Each of the `iters` iterations:
       1. linearize_rollout along the current controls: X, A, Bm, status;  J_old = cost.value
@@ -124,7 +160,8 @@ def solve(gm, x0, U0, cost, iters, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5
       4. mu: an environment that accepted: mu <- mu_shrink mu (0.1), set to 0 below mu_min (1e-6); one with fail != 0 or without an accepted a:
          mu <- max(mu_grow mu, mu_min) (x 10) and its controls stay as they were.  mu starts as mu_init (0).
     -> dict: X [H+1,B,n], U [H,B,nu] (the last accepted trajectory of every environment), J [iters+1,B] (J[i]: the cost at the start of iteration i, J[iters]:
-    at the end), a [iters,B] (the accepted step length, 0: none), mu [iters,B] (the regularisation each backward pass ran with), fail [iters,B], dV [iters,B,2]."""
+    at the end), a [iters,B] (the accepted step length, 0: none), mu [iters,B] (the regularisation each backward pass ran with), fail [iters,B], dV [iters,B,2].
+    fused: steps 1 and 3 are one call of dojo_rollout_minimal_dev each (linearize_rollout_fused, forward_pass_fused) instead of H calls driven from here."""
     B, nu = gm.batch, gm.spec.nu; dt = _dtype(gm)
     na = int(nu - act_off if na is None else na)
     dev = x0.device
@@ -135,7 +172,7 @@ def solve(gm, x0, U0, cost, iters, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5
     if int(iters) < 1:
         raise ValueError("iters must be >= 1")
     for _ in range(int(iters)):
-        X, A, Bm, status = linearize_rollout(gm, x0, U)
+        X, A, Bm, status = (linearize_rollout_fused if fused else linearize_rollout)(gm, x0, U)
         J = cost.value(X, U[:, :, act])
         lx, lu, lxx, luu, lux = cost.quadratize(X, U[:, :, act])
         K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na)
@@ -144,7 +181,7 @@ def solve(gm, x0, U0, cost, iters, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5
         a_acc = torch.zeros(B, dtype=dt, device=dev)
         U_new = U.clone()
         for a in alphas:
-            Xa, Ua, sa = forward_pass(gm, X, U, K, kff, float(a), act_off, na)
+            Xa, Ua, sa = (forward_pass_fused if fused else forward_pass)(gm, X, U, K, kff, float(a), act_off, na)
             Ja = cost.value(Xa, Ua[:, :, act])
             now = ~accepted & solved & (sa == 0).all(0) & (Ja <= J + c1 * (a * dV[:, 0] + a * a * dV[:, 1]))
             U_new = torch.where(now[None, :, None], Ua, U_new); a_acc = torch.where(now, torch.full_like(a_acc, a), a_acc)

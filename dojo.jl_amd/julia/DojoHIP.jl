@@ -288,6 +288,34 @@ function riccati(bm::BatchedMechanism{T}, A::Array{T,4}, Bm::Array{T,4}, lx::Arr
     return K, kff, dV, fail, Vx, Vxx
 end
 
+"mirror of `DojoTracking` (include/dojo_hip_trajopt.h): eleven pointers, two Int32"
+struct DojoTracking
+    x0::Ptr{Cvoid}; Ubar::Ptr{Cvoid}; Xbar::Ptr{Cvoid}; K::Ptr{Cvoid}; kff::Ptr{Cvoid}; alpha::Ptr{Cvoid}
+    X::Ptr{Cvoid}; U_out::Ptr{Cvoid}; status::Ptr{Cvoid}; A::Ptr{Cvoid}; Bm::Ptr{Cvoid}
+    act_off::Int32; na::Int32
+end
+
+"""
+simulate! through DojoEnvironments.step! (minimal state in, minimal state out) under the tracking controller u_k = Ubar_k + E (alpha kff_k + K_k (x_k - Xbar_k)),
+evaluated on the device between the steps: dojo_rollout_minimal -- the forward pass of iLQR and, with `jacobians`, its linearization, one call each.  n = 2nu;
+x0[n, B], Ubar[nu, B, H], Xbar[n, B, H + 1], K[n, na, B, H] (K_k', as `riccati` returns it), kff[na, B, H], alpha[B]; each but x0 and Ubar may be `nothing`
+(zeros; alpha: ones).  The controller drives the inputs act_off + 1 : act_off + na.
+-> X[n, B, H + 1], U[nu, B, H], status[B, H] and, with `jacobians`, A[n, n, B, H] (jx' of every step), Bm[nu, n, B, H] (ju'), in the handle's gradient mode.
+"""
+function rollout_minimal(bm::BatchedMechanism{T}, x0::Matrix{T}, Ubar::Array{T,3}; Xbar::Union{Nothing,Array{T,3}}=nothing, K::Union{Nothing,Array{T,4}}=nothing,
+                         kff::Union{Nothing,Array{T,3}}=nothing, alpha::Union{Nothing,Vector{T}}=nothing, act_off::Integer=0, na::Integer=bm.nu - act_off,
+                         jacobians::Bool=false) where T
+    H = size(Ubar, 3); n = 2 * bm.nu
+    X = Array{T}(undef, n, bm.batch, H + 1); U = Array{T}(undef, bm.nu, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    A = jacobians ? Array{T}(undef, n, n, bm.batch, H) : nothing; Bm = jacobians ? Array{T}(undef, bm.nu, n, bm.batch, H) : nothing
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve x0 Ubar Xbar K kff alpha X U status A Bm begin
+        t = Ref(DojoTracking(p(x0), p(Ubar), p(Xbar), p(K), p(kff), p(alpha), p(X), p(U), p(status), p(A), p(Bm), Int32(act_off), Int32(na)))
+        check(@ccall $(fn(:dojo_rollout_minimal))(bm.handle::Ptr{Cvoid}, Int32(H)::Int32, t::Ptr{DojoTracking})::Cint)
+    end
+    return jacobians ? (X, U, status, A, Bm) : (X, U, status)
+end
+
 """
 reverse mode through a closed-loop rollout (no counterpart in Dojo.jl): the rollout of `rollout_policy` (without contact observations) and the
 gradient of a trajectory loss w.r.t. the policy, the feed-forward term and the initial state; the recorded Jacobians stay on the device.

@@ -11,7 +11,10 @@ trajectory, its own regularisation and its own line search, and every stage is o
 The cart's input is the only driven one (act_off = 0, na = 1); the minimal state is [cart position, cart velocity, pole angle, pole angular velocity], the pole is
 upright at angle 0 and hangs at pi.
 
-    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations]          # needs a GPU: libdojo_hip has no CPU fallback
+With --fused the first and the last stage are ONE call of dojo_rollout_minimal_dev each (ilqr.linearize_rollout_fused, ilqr.forward_pass_fused): the steps, the
+feedback law and the Jacobians of the whole horizon on the device, every environment group at its own pace.
+
+    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations] [--fused]          # needs a GPU: libdojo_hip has no CPU fallback
 """
 import os
 import sys
@@ -28,6 +31,7 @@ from dojo_amd import api, ilqr                         # noqa: E402
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
+    fused = "--fused" in argv; argv = [a for a in argv if a != "--fused"]
     B = int(argv[0]) if len(argv) > 0 else 64
     H = int(argv[1]) if len(argv) > 1 else 60
     iters = int(argv[2]) if len(argv) > 2 else 40
@@ -45,7 +49,7 @@ def main(argv=None):
                               x_goal=torch.zeros(4, dtype=dt, device=dev))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = ilqr.solve(gm, x0, U0, cost, iters, act_off=0, na=1)
+    res = ilqr.solve(gm, x0, U0, cost, iters, act_off=0, na=1, fused=fused)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     J = res["J"].cpu().numpy()
@@ -54,7 +58,7 @@ def main(argv=None):
               ("" if i == J.shape[0] - 1 else "   accepted %d / %d, mu max %.1e" % (int((res["a"][i] > 0).sum()), B, float(res["mu"][i].max()))))
     xH = res["X"][-1].cpu().numpy()
     print("final |pole angle|: min %.3f  median %.3f  max %.3f rad (start: %.3f .. %.3f)" % (np.abs(xH[:, 2]).min(), np.median(np.abs(xH[:, 2])), np.abs(xH[:, 2]).max(), 0.5 * np.pi, np.pi))
-    print("%d environments x %d steps x %d iterations in %.2f s" % (B, H, iters, el))
+    print("%d environments x %d steps x %d iterations in %.2f s%s" % (B, H, iters, el, " (fused rollouts)" if fused else ""))
     assert (J[-1] <= J[0]).all()
     gm.close()
     return res

@@ -696,9 +696,9 @@ int  dojo_rollout_mlp_gradients(DojoHandle h, const void* z0, const DojoMlpPolic
  * act_off < 0 or act_off + na > nu.  DOJO_ERR_UNSUPPORTED: a mechanism with a kinematic loop (as dojo_minimal_gradients_dev); a shape the kernel's plan
  * cannot hold -- more than 64 KB of LDS (8 (n (n + 1) / 2 + max(32 (n + na), na n + 2 na^2) + 2 n + 4 na + 8) bytes: Ant (28, 8) 13 KB, Atlas (72, 30) 55 KB),
  * n + na > 110 (the accumulators of the lower triangle of [Qxx Qxu; Qux Quu] live in registers), na > 64 -- with the byte count in the text.
- * Not part of it: the forward pass as one fused call (it needs time-varying gains in the controller kernel: a follow-up; dojo_amd/ilqr.py builds it from
- * dojo_step_minimal_dev), costs shared across the batch or given as diagonals, control limits, second-order dynamics terms (DDP), constraints (augmented
- * Lagrangian), kinematic loops. */
+ * Not part of it: the forward pass and the linearization along it (each is one call of the rollout in minimal coordinates of include/dojo_hip_trajopt.h,
+ * whose controller takes K and kff as they are written here), costs shared across the batch or given as diagonals, control limits, second-order dynamics
+ * terms (DDP), constraints (augmented Lagrangian), kinematic loops. */
 typedef struct DojoRiccati {
     const void* A;      /* [H][B][n][n]   row-major, jx of dojo_minimal_gradients_dev per step */
     const void* Bm;     /* [H][B][n][nu]  row-major, ju ...; columns act_off .. act_off+na-1 are read */
