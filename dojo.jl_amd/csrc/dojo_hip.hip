@@ -19,7 +19,7 @@
 #include "dojo_tangent.hpp"
 #include "dojo_riccati.hpp"
 #include "dojo_tracking.hpp"
-#include "../../include/dojo_hip_trajopt.h"
+#include "../../include/dojo_hip_limits.h"      // (includes dojo_hip_trajopt.h)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -992,23 +992,31 @@ int launch_tangent(const DojoSim* s, int H, int T, const void* DZ, const void* D
     return DOJO_OK;
 }
 
-// dojo_riccati_dev: the Riccati backward pass (dojo_riccati.hpp), one workgroup per environment, one launch; NQ = register accumulators per lane
+// what dojo_riccati_box_dev takes on top of the DojoRiccati record (include/dojo_hip_limits.h); null in its place: the unconstrained pass
+struct RiccatiBox { const DojoControlLimits* lim; const void* U; int64_t* active; int32_t* qp_iters; };
+
+// dojo_riccati_dev, dojo_riccati_box_dev: the Riccati backward pass (dojo_riccati.hpp), one workgroup per environment, one launch; NQ = register accumulators per lane
 template <class TIO, int NQ>
-int launch_riccati(const DojoSim* s, int H, const DojoRiccati& r, hipStream_t st) {
+int launch_riccati(const DojoSim* s, int H, const DojoRiccati& r, const RiccatiBox* box, hipStream_t st) {
     const int nu = (int)s->M.nu, n = 2 * nu;
     const dj::riccati::Args<TIO> A{(const TIO*)r.A, (const TIO*)r.Bm, r.status, (const TIO*)r.lx, (const TIO*)r.lu, (const TIO*)r.lxx, (const TIO*)r.luu, (const TIO*)r.lux, (const TIO*)r.mu,
                                    (TIO*)r.K, (TIO*)r.kff, r.fail, (TIO*)r.dV, (TIO*)r.Vx, (TIO*)r.Vxx, H, s->B, n, nu, r.na, r.act_off};
-    hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::lds_bytes(n, r.na), st, A);
+    if (box) {
+        dj::riccati::BoxArgs<TIO> bx; static_cast<dj::riccati::Args<TIO>&>(bx) = A;
+        bx.lo = (const TIO*)box->lim->lo; bx.hi = (const TIO*)box->lim->hi; bx.U = (const TIO*)box->U; bx.active = (long long*)box->active; bx.iters = box->qp_iters;
+        hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ, dj::riccati::BoxArgs<TIO>>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::box_lds_bytes(n, r.na), st, bx);
+    } else
+        hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::lds_bytes(n, r.na), st, A);
     HIPCHK(hipGetLastError());
     return DOJO_OK;
 }
 template <class TIO>
-int launch_riccati_any(const DojoSim* s, int H, const DojoRiccati& r, hipStream_t st) {
+int launch_riccati_any(const DojoSim* s, int H, const DojoRiccati& r, const RiccatiBox* box, hipStream_t st) {
     switch (dj::riccati::accumulators(2 * (int)s->M.nu, r.na)) {
-        case 3: return launch_riccati<TIO, 3>(s, H, r, st);
-        case 6: return launch_riccati<TIO, 6>(s, H, r, st);
-        case 12: return launch_riccati<TIO, 12>(s, H, r, st);
-        default: return launch_riccati<TIO, 24>(s, H, r, st);
+        case 3: return launch_riccati<TIO, 3>(s, H, r, box, st);
+        case 6: return launch_riccati<TIO, 6>(s, H, r, box, st);
+        case 12: return launch_riccati<TIO, 12>(s, H, r, box, st);
+        default: return launch_riccati<TIO, 24>(s, H, r, box, st);
     }
 }
 
@@ -1033,7 +1041,7 @@ int launch_mlp(const DojoSim* s, const DojoMlpPolicy& p, const dj::mlp::Shape& s
 // (dojo_tracking.hpp), the re-projection by min2max_kernel: the two maps are the kernels of dojo_step_minimal_dev, which index environments from 0 and are given
 // the span's slice of every array.  The observation of the final state (u = null) is the first of the three alone.
 template <class TIO>
-int launch_tracking(const DojoSim* s, const DojoTracking& t, int k, const void* z, const void* uff, void* x, void* u, void* zproj, const Span& sp) {
+int launch_tracking(const DojoSim* s, const DojoTracking& t, const DojoControlLimits* lim, int k, const void* z, const void* uff, void* x, void* u, void* zproj, const Span& sp) {
     const size_t B = s->B, Nb = s->M.Nb, nu = s->M.nu, n = 2 * nu, kB = (size_t)k * B, e0 = sp.env0;
     TIO* const xs = (TIO*)x + e0 * n;
     if (k == 0) HIPCHK(hipMemcpyAsync(xs, (const TIO*)z + e0 * n, (size_t)sp.nenv * n * sizeof(TIO), hipMemcpyDeviceToDevice, sp.stream));
@@ -1042,7 +1050,12 @@ int launch_tracking(const DojoSim* s, const DojoTracking& t, int k, const void* 
     auto row = [&](const void* p, size_t per) { return p ? (const TIO*)p + kB * per : nullptr; };      // step k of an input that is given
     const dj::tracking::Args<TIO> A{(const TIO*)x, (const TIO*)uff, row(t.Xbar, n), row(t.K, (size_t)t.na * n), row(t.kff, (size_t)t.na), (const TIO*)t.alpha, (TIO*)u,
                                     (int)sp.env0, sp.nenv, (int)nu, t.act_off, t.na};
-    hipLaunchKernelGGL((dj::tracking::rollout_tracking_kernel<TIO>), dim3((unsigned)((sp.nenv + dj::policy::ENVS - 1) / dj::policy::ENVS)), dim3(dj::policy::THREADS), 0, sp.stream, A);
+    const dim3 grid((unsigned)((sp.nenv + dj::policy::ENVS - 1) / dj::policy::ENVS));
+    if (lim) {       // (dojo_rollout_minimal_box_dev)
+        dj::tracking::BoxArgs<TIO> bx; static_cast<dj::tracking::Args<TIO>&>(bx) = A; bx.lo = (const TIO*)lim->lo; bx.hi = (const TIO*)lim->hi;
+        hipLaunchKernelGGL((dj::tracking::rollout_tracking_kernel<TIO, dj::tracking::BoxArgs<TIO>>), grid, dim3(dj::policy::THREADS), 0, sp.stream, bx);
+    }
+    else hipLaunchKernelGGL((dj::tracking::rollout_tracking_kernel<TIO>), grid, dim3(dj::policy::THREADS), 0, sp.stream, A);
     HIPCHK(hipGetLastError());
     return launch_items(dj::ckern::min2max_kernel<TIO>, sp.nenv, 64, sp.stream, node_table(s), (const int*)s->d_order, (int)Nb, (int)nu, s->M.dt, sp.nenv, (const TIO*)xs, (TIO*)zproj + e0 * 13 * Nb);
 }
@@ -1053,6 +1066,7 @@ struct Controller {
     const DojoPolicy* affine = nullptr;
     const DojoMlpPolicy* mlp = nullptr;
     const DojoTracking* tracking = nullptr;
+    const DojoControlLimits* limits = nullptr;     // of the tracking controller (dojo_rollout_minimal_box_dev) or null
     dj::mlp::Shape shape{};
     double* ACT = nullptr;              // [H][B][nh] or null
     bool contact_forces() const { return tracking ? false : affine ? affine->contact_forces != 0 : mlp->contact_forces != 0; }
@@ -1060,7 +1074,7 @@ struct Controller {
 };
 // the controls of step k (u != null) or the observation of the final state (u = null, k = H).  zproj: the tracking controller's re-projected state (the others make none)
 int launch_controller(const DojoSim* s, const Controller& c, int k, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp, void* zproj = nullptr) {
-    if (c.tracking) return by_dtype(s, [&](auto t) { return launch_tracking<decltype(t)>(s, *c.tracking, k, z, uff, obs, u, zproj, sp); });
+    if (c.tracking) return by_dtype(s, [&](auto t) { return launch_tracking<decltype(t)>(s, *c.tracking, c.limits, k, z, uff, obs, u, zproj, sp); });
     if (c.affine) return launch_policy_any(s, *c.affine, z, csg, uff, obs, u, sp);
     double* const act = (c.ACT && u) ? c.ACT + (size_t)k * s->B * c.shape.nh : nullptr;
     return by_dtype(s, [&](auto t) { return launch_mlp<decltype(t)>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp); });
@@ -1777,33 +1791,75 @@ static int refuse_riccati(DojoHandle s, int32_t H, const DojoRiccati* r, const c
     return DOJO_OK;
 }
 
-int dojo_riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, void* stream) {
+// ... and what the control-limited entries refuse on top (include/dojo_hip_limits.h)
+static int refuse_riccati_box(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox& box, const char* who) {
+    TRY(refuse_riccati(s, H, r, who));
+    const std::string w_ = std::string(who) + ": ";
+    if (!box.lim || !box.U) { g_err = w_ + "lim and U must not be NULL"; return DOJO_ERR_INVALID; }
+    const int n = 2 * (int)s->M.nu, m = r->na;
+    const size_t lds = dj::riccati::box_lds_bytes(n, m);
+    if (lds > 65536) {
+        g_err = w_ + "n = " + std::to_string(n) + ", na = " + std::to_string(m) + " needs " + std::to_string(lds) + " bytes of LDS per environment with the box QP; the kernel holds at most 65536";
+        return DOJO_ERR_UNSUPPORTED;
+    }
+    return DOJO_OK;
+}
+// the limits of a host entry are read: an empty interval or a NaN is refused (the device entries cannot look: there it is the failure code -(k + 1), or the law's comparison)
+static int refuse_limit_values(DojoHandle s, const DojoControlLimits* lim, size_t count, const char* who) {
+    return by_dtype(s, [&](auto t) {
+        using T = decltype(t);
+        const T* const lo = (const T*)lim->lo; const T* const hi = (const T*)lim->hi;
+        for (size_t i = 0; i < count; ++i) {
+            const double l = lo ? (double)lo[i] : -HUGE_VAL, h = hi ? (double)hi[i] : HUGE_VAL;
+            if (!(l <= h)) { g_err = std::string(who) + ": the limits must satisfy lo <= hi and must not be NaN (element " + std::to_string(i) + " of [B][na])"; return DOJO_ERR_INVALID; }
+        }
+        return DOJO_OK;
+    });
+}
+
+// box = null: dojo_riccati_dev
+static int riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox* box, void* stream, const char* who) {
     Enter enter_(s);
-    TRY(refuse_riccati(s, H, r, "dojo_riccati_dev"));
+    TRY(box ? refuse_riccati_box(s, H, r, *box, who) : refuse_riccati(s, H, r, who));
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: the last dojo_minimal_gradients_dev may be writing the record)
-    return by_dtype(s, [&](auto t) { return launch_riccati_any<decltype(t)>(s, H, *r, st); });
+    return by_dtype(s, [&](auto t) { return launch_riccati_any<decltype(t)>(s, H, *r, box, st); });
+}
+int dojo_riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, void* stream) { return riccati_dev(s, H, r, nullptr, stream, "dojo_riccati_dev"); }
+int dojo_riccati_box_dev(DojoHandle s, int32_t H, const DojoRiccati* r, const DojoControlLimits* lim, const void* U, int64_t* active, int32_t* qp_iters, void* stream) {
+    const RiccatiBox box{lim, U, active, qp_iters};
+    return riccati_dev(s, H, r, &box, stream, "dojo_riccati_box_dev");
 }
 
 // host pointers: upload, one launch, download
-int dojo_riccati(DojoHandle s, int32_t H, const DojoRiccati* r) {
+static int riccati_host(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox* box, const char* who) {
     Enter enter_(s);
-    TRY(refuse_riccati(s, H, r, "dojo_riccati"));
+    TRY(box ? refuse_riccati_box(s, H, r, *box, who) : refuse_riccati(s, H, r, who));
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)r->na, HB = (size_t)H * B;
+    if (box) TRY(refuse_limit_values(s, box->lim, B * m, who));
     Staging st;
     const auto &dA = st.input(HB * n * n * w, r->A), &dB = st.input(HB * n * nu * w, r->Bm), &dS = st.input(HB * sizeof(int32_t), r->status);
     const auto &dlx = st.input((HB + B) * n * w, r->lx), &dlu = st.input(HB * m * w, r->lu), &dlxx = st.input((HB + B) * n * n * w, r->lxx);
     const auto &dluu = st.input(HB * m * m * w, r->luu), &dlux = st.input(HB * m * n * w, r->lux), &dmu = st.input(B * w, r->mu);
+    const auto &dlo = st.input(B * m * w, box ? box->lim->lo : nullptr), &dhi = st.input(B * m * w, box ? box->lim->hi : nullptr), &dU = st.input(HB * nu * w, box ? box->U : nullptr);
     const auto &dK = st.output(HB * m * n * w, r->K), &dk = st.output(HB * m * w, r->kff), &dF = st.output(B * sizeof(int32_t), r->fail);
     const auto &ddV = st.output(B * 2 * w, r->dV), &dVx = st.output(B * n * w, r->Vx), &dVxx = st.output(B * n * n * w, r->Vxx);
+    const auto &dact = st.output(HB * sizeof(int64_t), box ? box->active : nullptr), &dit = st.output(HB * sizeof(int32_t), box ? box->qp_iters : nullptr);
     TRY(st.allocate());
     DojoRiccati d = *r;
     d.A = dA.p; d.Bm = dB.p; d.status = (const int32_t*)dS.p; d.lx = dlx.p; d.lu = dlu.p; d.lxx = dlxx.p; d.luu = dluu.p; d.lux = dlux.p; d.mu = dmu.p;
     d.K = dK.p; d.kff = dk.p; d.fail = (int32_t*)dF.p; d.dV = ddV.p; d.Vx = dVx.p; d.Vxx = dVxx.p;
-    TRY(dojo_riccati_dev(s, H, &d, nullptr));
+    const DojoControlLimits dlim{dlo.p, dhi.p};
+    const RiccatiBox dbox{&dlim, dU.p, (int64_t*)dact.p, (int32_t*)dit.p};
+    TRY(riccati_dev(s, H, &d, box ? &dbox : nullptr, nullptr, who));
     return st.finish();      // (no state: the handle's own is left alone)
+}
+int dojo_riccati(DojoHandle s, int32_t H, const DojoRiccati* r) { return riccati_host(s, H, r, nullptr, "dojo_riccati"); }
+int dojo_riccati_box(DojoHandle s, int32_t H, const DojoRiccati* r, const DojoControlLimits* lim, const void* U, int64_t* active, int32_t* qp_iters) {
+    const RiccatiBox box{lim, U, active, qp_iters};
+    return riccati_host(s, H, r, &box, "dojo_riccati_box");
 }
 
 // ---- rollouts in minimal coordinates with the tracking controller (dojo_tracking.hpp, include/dojo_hip_trajopt.h): iLQR's forward pass and its linearization, one call each ----
@@ -1821,33 +1877,46 @@ static int refuse_tracking(DojoHandle s, int32_t H, const DojoTracking* t, const
     return DOJO_OK;      // (the controller keeps nothing in LDS: there is no shape it cannot hold)
 }
 
-int dojo_rollout_minimal_dev(DojoHandle s, int32_t H, const DojoTracking* t, void* stream) {
+// boxed: the clamped law of include/dojo_hip_limits.h, lim required
+static int rollout_minimal_dev(DojoHandle s, int32_t H, const DojoTracking* t, bool boxed, const DojoControlLimits* lim, void* stream, const char* who) {
     Enter enter_(s);
-    TRY(refuse_tracking(s, H, t, "dojo_rollout_minimal_dev"));
-    const DojoTracking tr = *t;      // (the caller's struct is read during the call only)
-    Controller c; c.tracking = &tr;
+    TRY(refuse_tracking(s, H, t, who));
+    if (boxed && !lim) { g_err = std::string(who) + ": lim must not be NULL"; return DOJO_ERR_INVALID; }
+    const DojoTracking tr = *t;      // (the caller's structs are read during the call only)
+    const DojoControlLimits lm = boxed ? *lim : DojoControlLimits{nullptr, nullptr};
+    Controller c; c.tracking = &tr; c.limits = boxed ? &lm : nullptr;
     RolloutIO io; io.z0 = tr.x0; io.U = tr.Ubar; io.status = tr.status; io.controller = &c; io.OBS = tr.X; io.U_out = tr.U_out; io.A = tr.A; io.Bm = tr.Bm;
     return rollout_core(s, H, io, stream);
 }
+int dojo_rollout_minimal_dev(DojoHandle s, int32_t H, const DojoTracking* t, void* stream) { return rollout_minimal_dev(s, H, t, false, nullptr, stream, "dojo_rollout_minimal_dev"); }
+int dojo_rollout_minimal_box_dev(DojoHandle s, int32_t H, const DojoTracking* t, const DojoControlLimits* lim, void* stream) {
+    return rollout_minimal_dev(s, H, t, true, lim, stream, "dojo_rollout_minimal_box_dev");
+}
 
-// host pointers (the members of *t): upload, roll out on the device, download
-int dojo_rollout_minimal(DojoHandle s, int32_t H, const DojoTracking* t) {
+// host pointers (the members of *t and *lim): upload, roll out on the device, download
+static int rollout_minimal_host(DojoHandle s, int32_t H, const DojoTracking* t, bool boxed, const DojoControlLimits* lim, const char* who) {
     Enter enter_(s);
-    TRY(refuse_tracking(s, H, t, "dojo_rollout_minimal"));
+    TRY(refuse_tracking(s, H, t, who));
+    if (boxed && !lim) { g_err = std::string(who) + ": lim must not be NULL"; return DOJO_ERR_INVALID; }
     HIPCHK(hipSetDevice(s->device));
     const size_t B = s->B, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)t->na, HB = (size_t)H * B;
+    if (boxed) TRY(refuse_limit_values(s, lim, B * m, who));
     Staging st;
     const auto &dx0 = st.input(B * n * w, t->x0), &dUb = st.input(HB * nu * w, t->Ubar), &dXb = st.input((HB + B) * n * w, t->Xbar);
     const auto &dK = st.input(HB * m * n * w, t->K), &dk = st.input(HB * m * w, t->kff), &da = st.input(B * w, t->alpha);
+    const auto &dlo = st.input(B * m * w, boxed ? lim->lo : nullptr), &dhi = st.input(B * m * w, boxed ? lim->hi : nullptr);
     const auto &dX = st.output((HB + B) * n * w, t->X), &dU = st.output(HB * nu * w, t->U_out), &dS = st.output(HB * sizeof(int32_t), t->status);
     const auto &dA = st.output(HB * n * n * w, t->A), &dB = st.output(HB * n * nu * w, t->Bm);
     TRY(st.allocate());
     DojoTracking d = *t;
     d.x0 = dx0.p; d.Ubar = dUb.p; d.Xbar = dXb.p; d.K = dK.p; d.kff = dk.p; d.alpha = da.p;
     d.X = dX.p; d.U_out = dU.p; d.status = (int32_t*)dS.p; d.A = dA.p; d.Bm = dB.p;
-    TRY(dojo_rollout_minimal_dev(s, H, &d, nullptr));
+    const DojoControlLimits dlim{dlo.p, dhi.p};
+    TRY(rollout_minimal_dev(s, H, &d, boxed, &dlim, nullptr, who));
     return st.finish();      // (the handle keeps the last step's states itself)
 }
+int dojo_rollout_minimal(DojoHandle s, int32_t H, const DojoTracking* t) { return rollout_minimal_host(s, H, t, false, nullptr, "dojo_rollout_minimal"); }
+int dojo_rollout_minimal_box(DojoHandle s, int32_t H, const DojoTracking* t, const DojoControlLimits* lim) { return rollout_minimal_host(s, H, t, true, lim, "dojo_rollout_minimal_box"); }
 
 // ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----
 int dojo_observation_jacobian_dev(DojoHandle s, const void* z, int32_t n, double* M, void* stream) {

@@ -43,10 +43,28 @@
 // array pointers of Args and the step's bases).  Ant runs four workgroups per CU, Atlas two (LDS).
 //
 // Not part of it: the forward pass as one fused call (it needs time-varying gains in the controller kernel: a follow-up), costs shared across the batch or given
-// as diagonals, control limits, second-order dynamics terms (DDP), constraints (augmented Lagrangian), kinematic loops.
+// as diagonals, second-order dynamics terms (DDP), constraints other than control limits (augmented Lagrangian), kinematic loops.  Control limits: the variant below.
+//
+// The control-limited variant (dojo_riccati_box_dev, include/dojo_hip_limits.h: the recursion, the solver and the failure codes are documented there) is this
+// kernel over BoxArgs, every difference behind `if constexpr (BOX)`; the instantiations over Args keep the instructions they had before it existed.  Per step:
+//   * in front of the Cholesky lane i of wavefront 0 forms lo'_i = lo_i - U_i and hi'_i (registers); !(lo' <= hi') anywhere: flag -1, code -(k + 1);
+//   * K and kff are solved as above, unchanged -- kf is then the start point of the QP, and a step whose start point is not clipped is finished (its cost over
+//     the unconstrained kernel: a ballot and one barrier);
+//   * otherwise wavefront 0, lane = row, runs the projected Newton (box_qp): g = Qu + Qreg x per lane over column i of the symmetric Quu, the clamped set by
+//     ballot, the masked Cholesky over L (box_factor: the column loop above with identity rows for clamped lanes), the direction by column-oriented substitutions
+//     (box_solve: shuffles, the reciprocal pivots per lane), the trial step in LDS (dl) for the second mat-vec, the two scalar sums of a trial by a fixed
+//     xor-butterfly (wave_add).  wave_sync() between dependent LDS accesses, no workgroup barrier inside.  Details fixed here: the pivots of the direction's
+//     substitutions are multiplied by their reciprocals (the gains' solves divide, as above); f(x+) - f(x) is evaluated as g' dx + 1/2 dx' Qreg dx; a bad pivot
+//     of a masked factor counts as a failed QP; qp_iters counts the factorizations inside the loop;
+//   * a barrier; a failed QP leaves through the failure path (flag -1); a QP that ran: the lanes solve K again from Qux with the masked factor in L, clamped
+//     rows written as zeros.
+// LDS: the plan above + m doubles (dl): Ant 13 296 B, Quadruped 18 736 B, Atlas (72, 30) 55 120 B, Atlas with all 36 inputs 65 152 B (fits).  Resources, NQ = 3 / 6
+// / 12 / 24: fp32 147 / 153 / 171 / 207 VGPRs, fp64 136 / 145 / 163 / 199; no AGPRs, no scratch, no VGPR spills (146 .. 178 SGPRs parked in VGPR lanes).  The Ant's
+// fp32 build is over 128: three workgroups per CU where the unconstrained one runs four (4.06 ms against 3.11 ms with limits that clip nothing).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dojo_math.hpp"
+#include <type_traits>
 
 namespace dj {
 namespace riccati {
@@ -62,6 +80,14 @@ template <class TIO> struct Args {
     int H, B, n, nu, m, act_off;
 };
 
+// the argument record of the control-limited variant (include/dojo_hip_limits.h): riccati_kernel<TIO, NQ, BoxArgs<TIO>>
+template <class TIO> struct BoxArgs : Args<TIO> {
+    const TIO *lo, *hi;     // [B][m]; either may be null
+    const TIO* U;           // [H][B][nu]: the controls the limits are taken relative to
+    long long* active;      // [H][B] or null: bit i = row i clamped
+    int* iters;             // [H][B] or null
+};
+
 constexpr int THREADS = 256, R = 16, RB = 4, MAX_M = 64;        // lanes per workgroup, rows of T per block, rows per lane in a block, rows of the one-wavefront Cholesky
 inline int entries(int n, int m) { return (n + m) * (n + m + 1) / 2; }                                   // lower triangle of Q
 inline int accumulators(int n, int m) {                                                                  // NQ of the instantiation that holds them, 0: none does
@@ -71,6 +97,7 @@ inline int accumulators(int n, int m) {                                         
 }
 inline size_t region1(int n, int m) { const size_t a = 2 * (size_t)R * (n + m), b = (size_t)m * n + 2 * (size_t)m * m; return a > b ? a : b; }
 inline size_t lds_bytes(int n, int m) { return ((size_t)n * (n + 1) / 2 + region1(n, m) + (size_t)n + (n + m) + 3 * (size_t)m + 8) * sizeof(double); }
+inline size_t box_lds_bytes(int n, int m) { return lds_bytes(n, m) + (size_t)m * sizeof(double); }      // + the trial step of the QP
 
 #if defined(__HIPCC__)
 // LDS written by some lanes of a wavefront, read by others of the same wavefront: the hardware keeps a wavefront's LDS operations in order, the fence keeps the compiler from moving them
@@ -80,8 +107,117 @@ __device__ inline void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-template <class TIO, int NQ>
-__global__ void __launch_bounds__(THREADS) riccati_kernel(const Args<TIO> a) {
+// ---- the box QP of a step (the BoxArgs variant): wavefront 0, lane i = row i; the lanes >= m carry zeros and an infinite box ----
+__device__ __forceinline__ double wave_add(double v) {          // every lane gets the same bits: the sum of the 64 in the order of the butterfly
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+// Qreg with the rows and columns of `set` replaced by the identity's = L L^T, as the Cholesky of the sweep; rinv: 1 / L[tid][tid].  false: a pivot is not > 0 or not finite
+__device__ inline bool box_factor(const double* Quu, double* L, int m, double mu, unsigned long long set, int tid, double& rinv) {
+    const bool mine = set >> tid & 1;
+    for (int j = 0; j < m; ++j) {
+        double s = 0.0;
+        if (tid < m && tid >= j) {
+            s = (mine || (set >> j & 1)) ? (tid == j ? 1.0 : 0.0) : Quu[tid * m + j] + (tid == j ? mu : 0.0);
+#pragma unroll 2
+            for (int p = 0; p < j; ++p) s = fma(-L[tid * m + p], L[j * m + p], s);
+        }
+        const double d = __shfl(s, j);
+        if (!(d > 0.0) || !(d < __builtin_huge_val())) return false;
+        const double rd = sqrt(d);
+        if (tid < m && tid >= j) L[tid * m + j] = tid == j ? rd : s / rd;
+        if (tid == j) rinv = 1.0 / rd;
+        wave_sync();
+    }
+    return true;
+}
+// (L L^T)^-1 r, lane i holding r_i and the result's row i: column-oriented substitutions, the finished component crosses the lanes with a shuffle
+__device__ inline double box_solve(const double* L, int m, int tid, double rinv, double s) {
+    for (int p = 0; p < m; ++p) {
+        const double y = __shfl(s * rinv, p);
+        if (tid == p) s = y;
+        if (tid > p && tid < m) s = fma(-L[tid * m + p], y, s);
+    }
+    for (int p = m - 1; p >= 0; --p) {
+        const double x = __shfl(s * rinv, p);
+        if (tid == p) s = x;
+        if (tid < p) s = fma(-L[p * m + tid], x, s);
+    }
+    return s;
+}
+// kf: in, -Qreg^-1 Qu; out, argmin 1/2 x' Qreg x + qu' x over lo <= x <= hi by projected Newton (the header of include/dojo_hip_limits.h).  set: the clamped rows,
+// it: the iterations.  -> 1: the clip changed nothing (L untouched), 2: solved, L holds box_factor(set), -1: failed
+__device__ inline int box_qp(const double* Quu, double* L, double* kf, double* dl, const double* qu_, int m, double mu, double lo, double hi, int tid,
+                             unsigned long long& set, int& it) {
+    const bool valid = tid < m;
+    const auto clip = [&](double v) { return v < lo ? lo : v > hi ? hi : v; };
+    double x = valid ? kf[tid] : 0.0;
+    set = 0; it = 0;
+    { const double xc = clip(x); if (__ballot(valid && xc != x) == 0) return 1; x = xc; }
+    if (valid) kf[tid] = x;
+    wave_sync();
+    const double qu = valid ? qu_[tid] : 0.0;
+    double qm = 0.0;
+    if (valid) for (int j = 0; j < m; ++j) qm = fmax(qm, fabs(Quu[j * m + tid] + (j == tid ? mu : 0.0)));
+    const double qmax = wave_max(qm), qumax = wave_max(fabs(qu));
+    unsigned long long prev = 0, factored = 0; bool have_prev = false, have_factor = false, prev_full = false;
+    double rinv = 1.0;
+    for (;;) {
+        double g = 0.0;                                             // g = qu + Qreg x (Quu is symmetric: column tid is read, consecutive lanes consecutive addresses)
+        if (valid) {
+            double s = mu * x;
+#pragma unroll 2
+            for (int j = 0; j < m; ++j) s = fma(Quu[j * m + tid], kf[j], s);
+            g = qu + s;
+        }
+        set = __ballot(valid && ((x <= lo && g > 0.0) || (x >= hi && g < 0.0)));
+        const bool cl = set >> tid & 1;
+        const int nfree = m - __popcll(set);
+        const double gfree = wave_max(valid && !cl ? fabs(g) : 0.0), xmax = wave_max(fabs(x));
+        if (nfree == 0 || (have_prev && set == prev && prev_full) || gfree <= 64.0 * 0x1p-52 * fmax(qumax, qmax * xmax)) break;
+        if (it == 64) return -1;
+        ++it;
+        if (!box_factor(Quu, L, m, mu, set, tid, rinv)) return -1;
+        factored = set; have_factor = true;
+        const double d = box_solve(L, m, tid, rinv, valid && !cl ? -g : 0.0);
+        double step = 1.0, xt = x, xu = x; bool accepted = false;
+        for (int trial = 0; trial < 40 && !accepted; ++trial) {
+            xu = fma(step, d, x); xt = clip(xu);
+            const double dx = valid ? xt - x : 0.0;
+            if (valid) dl[tid] = dx;
+            wave_sync();
+            double qd = 0.0;
+            if (valid) {
+                qd = mu * dx;
+#pragma unroll 2
+                for (int j = 0; j < m; ++j) qd = fma(Quu[j * m + tid], dl[j], qd);
+            }
+            wave_sync();
+            const double gd = wave_add(g * dx), dqd = wave_add(dx * qd);          // f(x+) - f(x) = g' dx + 1/2 dx' Qreg dx
+            accepted = gd + 0.5 * dqd <= 0.1 * gd;
+            if (!accepted) step *= 0.5;
+        }
+        if (!accepted) return -1;
+        prev = set; have_prev = true;
+        prev_full = step == 1.0 && __ballot(valid && xt != xu) == 0;
+        x = xt;
+        if (valid) kf[tid] = x;
+        wave_sync();
+    }
+    if (!have_factor || factored != set) { if (!box_factor(Quu, L, m, mu, set, tid, rinv)) return -1; }
+    return 2;
+}
+
+// A_ = BoxArgs<TIO>: the control-limited variant (BOX; every difference sits behind `if constexpr (BOX)`: the instantiations over Args<TIO> keep their instructions)
+template <class TIO, int NQ, class A_ = Args<TIO>>
+__global__ void __launch_bounds__(THREADS) riccati_kernel(const A_ a) {
+    constexpr bool BOX = std::is_same<A_, BoxArgs<TIO>>::value;
     extern __shared__ __align__(16) double lds_[];
     const int H = a.H, B = a.B, n = a.n, nu = a.nu, m = a.m, N = n + m, b = (int)blockIdx.x, tid = (int)threadIdx.x;
     const int nV = n * (n + 1) / 2, ne = N * (N + 1) / 2;
@@ -98,6 +234,8 @@ __global__ void __launch_bounds__(THREADS) riccati_kernel(const Args<TIO> a) {
     double* const Vx = r1 + ((2 * R * N > m * n + 2 * m * m) ? 2 * R * N : m * n + 2 * m * m);
     double* const qv = Vx + n; double* const kf = qv + N; double* const g_ = kf + m; double* const t_ = g_ + m;
     int* const flag = reinterpret_cast<int*>(t_ + m);
+    unsigned long long* const clamped = reinterpret_cast<unsigned long long*>(t_ + m + 1);      // (BOX) the clamped set of the step
+    double* const dl = t_ + m + 8;                                                               // (BOX) [m]: the trial step of the QP
     const double mu = a.mu ? (double)DJ_GLOBAL_PTR(const TIO, a.mu)[b] : 0.0;
 
     // the entries of Q this lane owns: (row << 16 | column), row >= column; -1: none.  (Every use below goes through DJ_OPAQUE: what is derived from an entry -- a
@@ -197,9 +335,18 @@ __global__ void __launch_bounds__(THREADS) riccati_kernel(const Args<TIO> a) {
         }
         __syncthreads();
         // Qreg = L L^T: wavefront 0, lane = row
+        double lo_ = -__builtin_huge_val(), hi_ = __builtin_huge_val();     // (BOX) lane i of wavefront 0: the limits of kff_i, lo[b][i] - U[k][b][act_off + i] and hi likewise
         if (tid < 64) {
-            bool ok = true;
-            for (int j = 0; j < m; ++j) {
+            bool ok = true, empty = false;
+            if constexpr (BOX) {
+                if (tid < m) {
+                    const double u = (double)DJ_GLOBAL_PTR(const TIO, a.U)[kb * nu + a.act_off + tid];
+                    if (a.lo) lo_ = (double)DJ_GLOBAL_PTR(const TIO, a.lo)[(size_t)b * m + tid] - u;
+                    if (a.hi) hi_ = (double)DJ_GLOBAL_PTR(const TIO, a.hi)[(size_t)b * m + tid] - u;
+                }
+                empty = __ballot(!(lo_ <= hi_)) != 0; ok = !empty;                               // (an empty or NaN box: the code is -(k + 1), nothing is factored)
+            }
+            for (int j = 0; j < (BOX && !ok ? 0 : m); ++j) {
                 double s = 0.0;
                 if (tid < m && tid >= j) {
                     s = Quu[tid * m + j] + (tid == j ? mu : 0.0);
@@ -212,20 +359,22 @@ __global__ void __launch_bounds__(THREADS) riccati_kernel(const Args<TIO> a) {
                 if (tid < m && tid >= j) L[tid * m + j] = tid == j ? rd : s / rd;
                 wave_sync();
             }
-            if (tid == 0) *flag = ok ? 1 : 0;
+            if (tid == 0) *flag = ok ? 1 : (BOX && empty) ? -1 : 0;
         }
         __syncthreads();
-        if (*flag == 0) {
+        if (BOX ? *flag <= 0 : *flag == 0) {
+        failed:     // (BOX: a failed QP comes here from below; the code is the flag's)
             // steps <= k and the value function: zeros; the steps above keep what was computed
             for (int kz = 0; kz <= k; ++kz) {
                 const size_t kzb = (size_t)kz * B + b;
                 for (int e = tid; e < m * n; e += THREADS) Kg[kzb * m * n + e] = (TIO)0;
                 for (int i = tid; i < m; i += THREADS) kffg[kzb * m + i] = (TIO)0;
+                if constexpr (BOX) if (tid == 0) { if (a.active) a.active[kzb] = 0; if (a.iters) a.iters[kzb] = 0; }
             }
             if (a.dV && tid < 2) a.dV[(size_t)b * 2 + tid] = (TIO)0;
             if (a.Vx) for (int i = tid; i < n; i += THREADS) a.Vx[(size_t)b * n + i] = (TIO)0;
             if (a.Vxx) for (int e = tid; e < n * n; e += THREADS) a.Vxx[(size_t)b * n * n + e] = (TIO)0;
-            if (tid == 0) a.fail[b] = k + 1;
+            if (tid == 0) a.fail[b] = (BOX && *flag < 0) ? -(k + 1) : k + 1;
             return;
         }
         // K = -Qreg^-1 Qux, kff = -Qreg^-1 Qu: one lane per right-hand side, in place (K over the dead Vxx)
@@ -246,6 +395,40 @@ __global__ void __launch_bounds__(THREADS) riccati_kernel(const Args<TIO> a) {
             for (int i = 0; i < m; ++i) x[i * ld] = -x[i * ld];
         }
         __syncthreads();
+        if constexpr (BOX) {
+            // kf holds -Qreg^-1 Qu and K_ the unconstrained gains, both exactly riccati_kernel's.  Wavefront 0 clips kf; where that changes nothing the step is
+            // done (no iteration, nothing clamped), otherwise it solves the QP, leaves the factor masked by the clamped set in L, and the gains are solved again
+            if (tid < 64) {
+                unsigned long long set = 0; int it = 0;
+                const int code = box_qp(Quu, L, kf, dl, qv + n, m, mu, lo_, hi_, tid, set, it);       // -1: failed, 1: nothing clipped, 2: solved, L is the masked factor
+                if (tid == 0) {
+                    *flag = code; *clamped = set;
+                    if (code > 0) { if (a.active) a.active[kb] = (long long)set; if (a.iters) a.iters[kb] = it; }
+                }
+            }
+            __syncthreads();
+            if (*flag < 0) goto failed;
+            if (*flag == 2) {
+                const unsigned long long set = *clamped;
+                for (int c = tid; c < n; c += THREADS) {
+                    double* const x = K_ + c;
+                    for (int i = 0; i < m; ++i) {
+                        double s = (set >> i & 1) ? 0.0 : Y[i * n + c];
+#pragma unroll 2
+                        for (int p = 0; p < i; ++p) s = fma(-L[i * m + p], x[p * n], s);
+                        x[i * n] = s / L[i * m + i];
+                    }
+                    for (int i = m - 1; i >= 0; --i) {
+                        double s = x[i * n];
+#pragma unroll 2
+                        for (int p = i + 1; p < m; ++p) s = fma(-L[p * m + i], x[p * n], s);
+                        x[i * n] = s / L[i * m + i];
+                    }
+                    for (int i = 0; i < m; ++i) x[i * n] = (set >> i & 1) ? 0.0 : -x[i * n];
+                }
+                __syncthreads();
+            }
+        }
         // t = Quu kff, g = t / 2 + Qu, Y = Quu K / 2 + Qux; the gains leave
         for (int i = tid; i < m; i += THREADS) {
             double s = 0.0;

@@ -22,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dojo_policy.hpp"
+#include <type_traits>
 
 namespace dj {
 namespace tracking {
@@ -35,9 +36,16 @@ template <class TIO> struct Args {
     int nu, act_off, na;
 };
 
+// the argument record of the clamped law (dojo_rollout_minimal_box_dev, include/dojo_hip_limits.h): rollout_tracking_kernel<TIO, BoxArgs<TIO>>
+template <class TIO> struct BoxArgs : Args<TIO> {
+    const TIO *lo, *hi;                 // [B][na] (batch-level); either may be null
+};
+
 #if defined(__HIPCC__)
-template <class TIO>
-__global__ void __launch_bounds__(policy::THREADS) rollout_tracking_kernel(const Args<TIO> A) {
+// A_ = BoxArgs<TIO>: the clamped law (BOX; every difference sits behind `if constexpr (BOX)`: the instantiations over Args<TIO> keep their instructions)
+template <class TIO, class A_ = Args<TIO>>
+__global__ void __launch_bounds__(policy::THREADS) rollout_tracking_kernel(const A_ A) {
+    constexpr bool BOX = std::is_same<A_, BoxArgs<TIO>>::value;
     using policy::WAVE;
     const int tid = (int)threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
     const int e = (int)blockIdx.x * policy::ENVS + wave;
@@ -63,7 +71,16 @@ __global__ void __launch_bounds__(policy::THREADS) rollout_tracking_kernel(const
         }
         const double a = fma(alpha, kff ? (double)kff[i] : 0.0, s);
         const int c = A.act_off + i;
-        if (lane == c % WAVE) u[c] = (TIO)((ubar ? (double)ubar[c] : 0.0) + a);
+        if constexpr (BOX) {
+            // min(max(Ubar + a, lo), hi) in fp64, rounded once.  The limits are values of the ABI type and rounding is monotone: clamping in front of the rounding
+            // gives the bits of clamping behind it, and a driven input is inside [lo, hi] exactly
+            double v = (ubar ? (double)ubar[c] : 0.0) + a;
+            if (A.lo) { const double l = (double)DJ_GLOBAL_PTR(const TIO, A.lo)[env * A.na + i]; v = v < l ? l : v; }
+            if (A.hi) { const double h = (double)DJ_GLOBAL_PTR(const TIO, A.hi)[env * A.na + i]; v = v > h ? h : v; }
+            if (lane == c % WAVE) u[c] = (TIO)v;
+        } else {
+            if (lane == c % WAVE) u[c] = (TIO)((ubar ? (double)ubar[c] : 0.0) + a);
+        }
     }
 }
 #endif

@@ -59,6 +59,10 @@ EXPORTED_SYMBOLS = list(_SIGNATURES)
 # include/dojo_hip_trajopt.h, the second public header, in the same notation
 _TRAJOPT_SIGNATURES = {"dojo_rollout_minimal_dev": (C.c_int, "pipp"), "dojo_rollout_minimal": (C.c_int, "pip")}
 TRAJOPT_SYMBOLS = list(_TRAJOPT_SIGNATURES)
+# include/dojo_hip_limits.h, the third: control-limited iLQR
+_LIMITS_SIGNATURES = {"dojo_riccati_box_dev": (C.c_int, "pipppppp"), "dojo_riccati_box": (C.c_int, "pippppp"),
+                      "dojo_rollout_minimal_box_dev": (C.c_int, "pippp"), "dojo_rollout_minimal_box": (C.c_int, "pipp")}
+LIMITS_SYMBOLS = list(_LIMITS_SIGNATURES)
 
 
 def lib():
@@ -67,7 +71,7 @@ def lib():
         if not os.path.exists(_LIB_PATH):
             raise DojoError("libdojo_hip.so not built (run __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(_LIB_PATH)
-        for name, (restype, args) in {**_SIGNATURES, **_TRAJOPT_SIGNATURES}.items():
+        for name, (restype, args) in {**_SIGNATURES, **_TRAJOPT_SIGNATURES, **_LIMITS_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, [_KINDS[k] for k in args]
         _lib = L
@@ -118,6 +122,12 @@ class DojoTracking(C.Structure):
     and -- both or neither -- the Jacobians A, Bm) of a rollout in minimal coordinates; device pointers for dojo_rollout_minimal_dev, host pointers for dojo_rollout_minimal"""
     _fields_ = [("x0", C.c_void_p), ("Ubar", C.c_void_p), ("Xbar", C.c_void_p), ("K", C.c_void_p), ("kff", C.c_void_p), ("alpha", C.c_void_p),
                 ("X", C.c_void_p), ("U_out", C.c_void_p), ("status", C.c_void_p), ("A", C.c_void_p), ("Bm", C.c_void_p), ("act_off", C.c_int32), ("na", C.c_int32)]
+
+
+class DojoControlLimits(C.Structure):
+    """include/dojo_hip_limits.h `DojoControlLimits`: the limits lo, hi [B][na] of the driven inputs (either may be NULL: none on that side); device pointers
+    for the _dev entries, host pointers for dojo_riccati_box and dojo_rollout_minimal_box"""
+    _fields_ = [("lo", C.c_void_p), ("hi", C.c_void_p)]
 
 
 MLP_MAX_LAYERS = 4      # DOJO_MLP_MAX_LAYERS
@@ -526,6 +536,50 @@ class BatchedMechanism:
         A = np.empty((H, B, n, n), self.np_dtype) if jacobians else None; Bm = np.empty((H, B, n, nu), self.np_dtype) if jacobians else None
         t = DojoTracking(*map(addr, ins + (X, U, st, A, Bm)), int(act_off), na)
         _chk(lib().dojo_rollout_minimal(self.h, H, C.byref(t)))
+        return (X, U, st, A, Bm) if jacobians else (X, U, st)
+
+    def _limits(self, lo, hi, na):
+        """lo, hi: None, a scalar, [na] or [B, na] -> the two [B, na] arrays (None stays None) and the DojoControlLimits over them"""
+        arrs = [None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=self.np_dtype), (self.batch, na))) for a in (lo, hi)]
+        return arrs, DojoControlLimits(addr(arrs[0]), addr(arrs[1]))
+
+    def riccati_box(self, A, Bm, lx, lu, lxx, luu, U, lo=None, hi=None, lux=None, mu=None, status=None, act_off=0, na=None, value=True):
+        """dojo_riccati_box (host arrays): `riccati` under the control limits lo <= U[k][act] + kff[k] <= hi (control-limited DDP: a box QP per step, the gain
+        rows of clamped inputs are zero).  U [H,B,nu]: the controls the pass is taken around; lo, hi: None, a scalar, [na] or [B,na], +-inf allowed.
+        -> K, kff, dV, fail (0; 1 + k: the Cholesky of step k failed; -(1 + k): the QP of step k failed or its box is empty), active [H,B] int64 (bit i: input
+        act_off + i clamped), qp_iters [H,B] and, with value, Vx, Vxx."""
+        B, nu = self.batch, self.spec.nu; n = 2 * nu
+        H = int(np.shape(A)[0]); na = int(nu - act_off if na is None else na)
+        A = self._arr(A, (H, B, n, n)); Bm = self._arr(Bm, (H, B, n, nu)); U = self._arr(U, (H, B, nu))
+        lx = self._arr(lx, (H + 1, B, n)); lu = self._arr(lu, (H, B, na)); lxx = self._arr(lxx, (H + 1, B, n, n)); luu = self._arr(luu, (H, B, na, na))
+        lux = None if lux is None else self._arr(lux, (H, B, na, n)); mu = None if mu is None else self._arr(mu, (B,))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        K = np.empty((H, B, na, n), self.np_dtype); kff = np.empty((H, B, na), self.np_dtype); fail = np.empty(B, np.int32); dV = np.empty((B, 2), self.np_dtype)
+        Vx = np.empty((B, n), self.np_dtype) if value else None; Vxx = np.empty((B, n, n), self.np_dtype) if value else None
+        active = np.empty((H, B), np.int64); qp_iters = np.empty((H, B), np.int32)
+        keep, lim = self._limits(lo, hi, na)
+        r = DojoRiccati(*map(addr, (A, Bm, status, lx, lu, lxx, luu, lux, mu, K, kff, fail, dV, Vx, Vxx)), int(act_off), na)
+        _chk(lib().dojo_riccati_box(self.h, H, C.byref(r), C.byref(lim), addr(U), addr(active), addr(qp_iters)))
+        return (K, kff, dV, fail, active, qp_iters, Vx, Vxx) if value else (K, kff, dV, fail, active, qp_iters)
+
+    def rollout_minimal_box(self, x0, lo=None, hi=None, steps=None, Ubar=None, Xbar=None, K=None, kff=None, alpha=None, act_off=0, na=None, jacobians=False):
+        """dojo_rollout_minimal_box (host arrays): `rollout_minimal` with the driven inputs clamped into [lo, hi] (None, a scalar, [na] or [B,na]) before they are
+        rounded and stepped -> what `rollout_minimal` returns."""
+        B, nu = self.batch, self.spec.nu; n = 2 * nu
+        na = int(nu - act_off if na is None else na)
+        Hs = [np.shape(a)[0] for a in (Ubar, K, kff) if a is not None] + ([int(steps)] if steps is not None else [])
+        if not Hs:
+            raise ValueError("rollout_minimal_box needs the horizon: Ubar, K, kff or steps")
+        H = int(Hs[0])
+        if any(int(h) != H for h in Hs):
+            raise ValueError("Ubar, K, kff and steps disagree about the horizon: %s" % Hs)
+        opt = lambda a, shape: None if a is None else self._arr(a, shape)
+        ins = (self._arr(x0, (B, n)), opt(Ubar, (H, B, nu)), opt(Xbar, (H + 1, B, n)), opt(K, (H, B, na, n)), opt(kff, (H, B, na)), opt(alpha, (B,)))
+        X = np.empty((H + 1, B, n), self.np_dtype); U = np.empty((H, B, nu), self.np_dtype); st = np.empty((H, B), np.int32)
+        A = np.empty((H, B, n, n), self.np_dtype) if jacobians else None; Bm = np.empty((H, B, n, nu), self.np_dtype) if jacobians else None
+        keep, lim = self._limits(lo, hi, na)
+        t = DojoTracking(*map(addr, ins + (X, U, st, A, Bm)), int(act_off), na)
+        _chk(lib().dojo_rollout_minimal_box(self.h, H, C.byref(t), C.byref(lim)))
         return (X, U, st, A, Bm) if jacobians else (X, U, st)
 
     def rollout_policy(self, z0, W, steps, bias=None, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):

@@ -7,10 +7,13 @@ the same loop for B environments at once -- one trajectory, one regularisation a
     X, U, status = forward_pass_fused(gm, Xbar, Ubar, K, kff, a, ..)  # the closed-loop rollout around (Xbar, Ubar) for the step lengths a [B], ONE call
     K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu)           # ONE launch of dojo_riccati_dev for all H steps
     res = solve(gm, x0, U0, QuadraticCost(Q, R, Qf, x_goal), iters=10)
+    K, kff, dV, fail, active, qp_iters = riccati_box(gm, A, Bm, lx, lu, lxx, luu, U, lo, hi)   # ONE launch of dojo_riccati_box_dev: a box QP per step
+    X, U, status = rollout_minimal_box(gm, x0, Ubar, lo, hi, Xbar, K, kff, a)                  # dojo_rollout_minimal_box_dev: the clamped tracking law
+    res = solve_limited(gm, x0, U0, cost, 10, lo, hi)                                          # control-limited iLQR, lo <= u[act] <= hi
 
 Everything is enqueued on torch's current stream.  The driver reads one flag per trial step length (have all environments accepted?) and nothing else.
-Not here (include/dojo_hip.h, "Batched iLQR"; include/dojo_hip_trajopt.h): costs shared across the batch, control limits, second-order dynamics terms, constraints,
-running the step lengths of a line search side by side, kinematic loops."""
+Not here (include/dojo_hip.h, "Batched iLQR"; include/dojo_hip_trajopt.h): costs shared across the batch, second-order dynamics terms, constraints other than
+control limits (those: include/dojo_hip_limits.h, solve_limited), running the step lengths of a line search side by side, kinematic loops."""
 import ctypes as C
 
 import torch
@@ -51,6 +54,11 @@ def linearize_rollout(gm, x0, U):
 def riccati(gm, A, Bm, lx, lu, lxx, luu, lux=None, mu=None, status=None, act_off=0, na=None, value=False):
     """dojo_riccati_dev on device tensors: A [H,B,n,n], Bm [H,B,n,nu], lx [H+1,B,n], lu [H,B,na], lxx [H+1,B,n,n], luu [H,B,na,na], lux [H,B,na,n] or None,
     mu [B] or None, status [H,B] int32 or None -> K [H,B,na,n], kff [H,B,na], dV [B,2], fail [B] int32 (and Vx [B,n], Vxx [B,n,n] with value).  One launch."""
+    return _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, None)
+
+
+def _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, _box):
+    """riccati (_box None) and riccati_box (_box = (U, lo, hi)): the checks and the outputs they share"""
     B, nu = gm.batch, gm.spec.nu; n, dt = 2 * nu, _dtype(gm)
     H = int(A.shape[0]); na = int(nu - act_off if na is None else na)
     A = _want(A, "A", dt, (H, B, n, n)); Bm = _want(Bm, "Bm", dt, (H, B, n, nu))
@@ -62,8 +70,28 @@ def riccati(gm, A, Bm, lx, lu, lxx, luu, lux=None, mu=None, status=None, act_off
     dV = torch.empty((B, 2), dtype=dt, device=dev); fail = torch.empty(B, dtype=torch.int32, device=dev)
     Vx = torch.empty((B, n), dtype=dt, device=dev) if value else None; Vxx = torch.empty((B, n, n), dtype=dt, device=dev) if value else None
     r = api.DojoRiccati(*map(api.addr, (A, Bm, status, lx, lu, lxx, luu, lux, mu, K, kff, fail, dV, Vx, Vxx)), int(act_off), na)
-    api._chk(api.lib().dojo_riccati_dev(gm.h, H, C.byref(r), api.torch_stream(dev)))
-    return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
+    if _box is None:
+        api._chk(api.lib().dojo_riccati_dev(gm.h, H, C.byref(r), api.torch_stream(dev)))
+        return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
+    U, lo, hi = _box
+    U = _want(U, "U", dt, (H, B, nu)); lo, hi = _limits(gm, lo, hi, na, dev)
+    active = torch.empty((H, B), dtype=torch.int64, device=dev); qp_iters = torch.empty((H, B), dtype=torch.int32, device=dev)
+    lim = api.DojoControlLimits(api.addr(lo), api.addr(hi))
+    api._chk(api.lib().dojo_riccati_box_dev(gm.h, H, C.byref(r), C.byref(lim), api.addr(U), api.addr(active), api.addr(qp_iters), api.torch_stream(dev)))
+    return (K, kff, dV, fail, active, qp_iters, Vx, Vxx) if value else (K, kff, dV, fail, active, qp_iters)
+
+
+def _limits(gm, lo, hi, na, dev):
+    """lo, hi: a number, [na] or [B,na] (None: no limit on that side) -> two contiguous [B,na] device tensors in the handle dtype"""
+    one = lambda v, none: torch.as_tensor(none if v is None else v, dtype=_dtype(gm), device=dev).expand(gm.batch, na).contiguous()
+    return one(lo, float("-inf")), one(hi, float("inf"))
+
+
+def riccati_box(gm, A, Bm, lx, lu, lxx, luu, U, lo, hi, lux=None, mu=None, status=None, act_off=0, na=None, value=False):
+    """dojo_riccati_box_dev on device tensors: `riccati` under lo <= U[k][act] + kff[k] <= hi (a box QP per step, the gain rows of clamped inputs zero).  U [H,B,nu]:
+    the controls the pass is taken around; lo, hi: [na] or [B,na] (a number or None also pass) -> K, kff, dV, fail (-(1 + k): the QP of step k failed or its box is
+    empty), active [H,B] int64 (bit i: input act_off + i clamped), qp_iters [H,B] int32 (and Vx, Vxx with value).  One launch."""
+    return _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, (U, lo, hi))
 
 
 class QuadraticCost:
@@ -119,6 +147,11 @@ def rollout_minimal(gm, x0, Ubar, Xbar=None, K=None, kff=None, alpha=None, act_o
     environment group at its own pace.  Ubar [H,B,nu], Xbar [H+1,B,n], K [H,B,na,n], kff [H,B,na] (riccati's outputs), alpha [B]; each of the last four may be None
     (zeros; alpha: ones).  -> X [H+1,B,n], U [H,B,nu], status [H,B] int32 and, with jacobians, A [H,B,n,n], Bm [H,B,n,nu]: what H calls of
     dojo_step_minimal_dev / dojo_minimal_gradients_dev at (X[k], U[k]) give, bit for bit."""
+    return _rollout_minimal(gm, x0, Ubar, Xbar, K, kff, alpha, act_off, na, jacobians, None)
+
+
+def _rollout_minimal(gm, x0, Ubar, Xbar, K, kff, alpha, act_off, na, jacobians, _box):
+    """rollout_minimal (_box None) and rollout_minimal_box (_box = (lo, hi)): the checks and the outputs they share"""
     B, nu = gm.batch, gm.spec.nu; n, dt = 2 * nu, _dtype(gm)
     if Ubar.dim() != 3:
         raise ValueError("Ubar must be [H, B, nu]")
@@ -130,8 +163,42 @@ def rollout_minimal(gm, x0, Ubar, Xbar=None, K=None, kff=None, alpha=None, act_o
     status = torch.empty((H, B), dtype=torch.int32, device=dev)
     A = torch.empty((H, B, n, n), dtype=dt, device=dev) if jacobians else None; Bm = torch.empty((H, B, n, nu), dtype=dt, device=dev) if jacobians else None
     t = api.DojoTracking(*map(api.addr, (x0, Ubar, Xbar, K, kff, alpha, X, U, status, A, Bm)), int(act_off), na)
-    api._chk(api.lib().dojo_rollout_minimal_dev(gm.h, H, C.byref(t), api.torch_stream(dev)))
+    if _box is None:
+        api._chk(api.lib().dojo_rollout_minimal_dev(gm.h, H, C.byref(t), api.torch_stream(dev)))
+    else:
+        lo, hi = _limits(gm, _box[0], _box[1], na, dev)
+        lim = api.DojoControlLimits(api.addr(lo), api.addr(hi))
+        api._chk(api.lib().dojo_rollout_minimal_box_dev(gm.h, H, C.byref(t), C.byref(lim), api.torch_stream(dev)))
     return (X, U, status, A, Bm) if jacobians else (X, U, status)
+
+
+def rollout_minimal_box(gm, x0, Ubar, lo, hi, Xbar=None, K=None, kff=None, alpha=None, act_off=0, na=None, jacobians=False):
+    """dojo_rollout_minimal_box_dev on device tensors: `rollout_minimal` with the driven inputs clamped into [lo, hi] ([na] or [B,na]; a number or None also pass)
+    in fp64 before they are rounded and stepped.  With infinite limits: rollout_minimal's outputs, bit for bit."""
+    return _rollout_minimal(gm, x0, Ubar, Xbar, K, kff, alpha, act_off, na, jacobians, (lo, hi))
+
+
+def forward_pass_box(gm, Xbar, Ubar, K, kff, a, act_off, na, lo, hi):
+    """forward_pass with the driven inputs clamped into [lo, hi] (torch.clamp) -> X [H+1,B,n], U [H,B,nu], status [H,B]"""
+    H, B = Ubar.shape[:2]
+    dev = Xbar.device
+    lo, hi = _limits(gm, lo, hi, na, dev)
+    X = torch.empty_like(Xbar); X[0] = Xbar[0]
+    U = Ubar.clone()
+    status = torch.empty((H, B), dtype=torch.int32, device=dev); iters = torch.empty(B, dtype=torch.int32, device=dev)
+    L, st = api.lib(), api.torch_stream(dev)
+    for k in range(H):
+        U[k, :, act_off:act_off + na] += a * kff[k] + torch.einsum("bij,bj->bi", K[k], X[k] - Xbar[k])
+        U[k, :, act_off:act_off + na] = torch.clamp(U[k, :, act_off:act_off + na], lo, hi)
+        api._chk(L.dojo_step_minimal_dev(gm.h, api.addr(X[k]), api.addr(U[k]), api.addr(X[k + 1]), api.addr(status[k]), api.addr(iters), st))
+    return X, U, status
+
+
+def forward_pass_fused_box(gm, Xbar, Ubar, K, kff, alpha, act_off, na, lo, hi):
+    """forward_pass_box as one call of dojo_rollout_minimal_box_dev, the law and the clamp evaluated on the device in fp64"""
+    if not torch.is_tensor(alpha):
+        alpha = torch.full((gm.batch,), float(alpha), dtype=_dtype(gm), device=Xbar.device)
+    return rollout_minimal_box(gm, Xbar[0].contiguous(), Ubar, lo, hi, Xbar, K, kff, alpha, act_off, na)
 
 
 def linearize_rollout_fused(gm, x0, U):
@@ -162,6 +229,20 @@ def solve(gm, x0, U0, cost, iters, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5
     -> dict: X [H+1,B,n], U [H,B,nu] (the last accepted trajectory of every environment), J [iters+1,B] (J[i]: the cost at the start of iteration i, J[iters]:
     at the end), a [iters,B] (the accepted step length, 0: none), mu [iters,B] (the regularisation each backward pass ran with), fail [iters,B], dV [iters,B,2].
     fused: steps 1 and 3 are one call of dojo_rollout_minimal_dev each (linearize_rollout_fused, forward_pass_fused) instead of H calls driven from here."""
+    return _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu_grow, mu_shrink, fused, None)
+
+
+def solve_limited(gm, x0, U0, cost, iters, lo, hi, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625, 0.0078125),
+                  mu_init=0.0, mu_min=1e-6, mu_grow=10.0, mu_shrink=0.1, fused=False):
+    """control-limited iLQR (Tassa, Mansard, Todorov, ICRA 2014): `solve` under lo <= u[act] <= hi at every step, lo and hi [na] or [B,na] (+-inf allowed).
+    U0[:, :, act] is clamped into the limits first; the backward pass is riccati_box (a box QP per step around the current controls, the gain rows of clamped
+    inputs zero), the forward pass clamps (forward_pass_box; fused: one call of dojo_rollout_minimal_box_dev).  Everything else, the acceptance test included, is
+    `solve`'s.  -> solve's dict and active [iters,H,B] int64 (bit i: input act_off + i clamped in that backward pass).  With infinite limits: solve's bits."""
+    return _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu_grow, mu_shrink, fused, (lo, hi))
+
+
+def _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu_grow, mu_shrink, fused, limits):
+    """the loop of solve (limits None) and solve_limited (limits = (lo, hi))"""
     B, nu = gm.batch, gm.spec.nu; dt = _dtype(gm)
     na = int(nu - act_off if na is None else na)
     dev = x0.device
@@ -169,19 +250,30 @@ def solve(gm, x0, U0, cost, iters, act_off=0, na=None, c1=1e-4, alphas=(1.0, 0.5
     mu = torch.full((B,), float(mu_init), dtype=dt, device=dev)
     hist = {"J": [], "a": [], "mu": [], "fail": [], "dV": []}
     act = slice(act_off, act_off + na)
+    if limits is not None:
+        lo, hi = _limits(gm, limits[0], limits[1], na, dev)
+        U[:, :, act] = torch.clamp(U[:, :, act], lo, hi)
+        hist["active"] = []
     if int(iters) < 1:
         raise ValueError("iters must be >= 1")
     for _ in range(int(iters)):
         X, A, Bm, status = (linearize_rollout_fused if fused else linearize_rollout)(gm, x0, U)
         J = cost.value(X, U[:, :, act])
         lx, lu, lxx, luu, lux = cost.quadratize(X, U[:, :, act])
-        K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na)
+        if limits is None:
+            K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na)
+        else:
+            K, kff, dV, fail, active, _ = riccati_box(gm, A, Bm, lx, lu, lxx, luu, U, lo, hi, lux, mu, status, act_off, na)
+            hist["active"].append(active)
         solved = (status == 0).all(0) & (fail == 0)
         accepted = torch.zeros(B, dtype=torch.bool, device=dev)
         a_acc = torch.zeros(B, dtype=dt, device=dev)
         U_new = U.clone()
         for a in alphas:
-            Xa, Ua, sa = (forward_pass_fused if fused else forward_pass)(gm, X, U, K, kff, float(a), act_off, na)
+            if limits is None:
+                Xa, Ua, sa = (forward_pass_fused if fused else forward_pass)(gm, X, U, K, kff, float(a), act_off, na)
+            else:
+                Xa, Ua, sa = (forward_pass_fused_box if fused else forward_pass_box)(gm, X, U, K, kff, float(a), act_off, na, lo, hi)
             Ja = cost.value(Xa, Ua[:, :, act])
             now = ~accepted & solved & (sa == 0).all(0) & (Ja <= J + c1 * (a * dV[:, 0] + a * a * dV[:, 1]))
             U_new = torch.where(now[None, :, None], Ua, U_new); a_acc = torch.where(now, torch.full_like(a_acc, a), a_acc)

@@ -316,6 +316,54 @@ function rollout_minimal(bm::BatchedMechanism{T}, x0::Matrix{T}, Ubar::Array{T,3
     return jacobians ? (X, U, status, A, Bm) : (X, U, status)
 end
 
+"mirror of `DojoControlLimits` (include/dojo_hip_limits.h): the limits lo, hi [na, B] of the driven inputs; either may be NULL"
+struct DojoControlLimits
+    lo::Ptr{Cvoid}; hi::Ptr{Cvoid}
+end
+
+"""
+`riccati` under control limits (control-limited DDP, include/dojo_hip_limits.h): dojo_riccati_box.  U[nu, B, H] are the controls the pass is taken around,
+lo[na, B] and hi[na, B] the limits of the driven inputs (+-Inf allowed, either may be `nothing`): lo <= U[act, b, k] + kff[:, b, k] <= hi, the rows of K_k of
+clamped inputs are zero.  Other arguments and array conventions as in `riccati`.
+-> K, kff, dV, fail[B] (0; 1 + k: the Cholesky of step k failed; -(1 + k): the QP of step k failed or its box is empty), active[B, H] (Int64, bit i: input
+act_off + i + 1 clamped), qp_iters[B, H], Vx, Vxx.
+"""
+function riccati_box(bm::BatchedMechanism{T}, A::Array{T,4}, Bm::Array{T,4}, lx::Array{T,3}, lu::Array{T,3}, lxx::Array{T,4}, luu::Array{T,4}, U::Array{T,3};
+                     lo::Union{Nothing,Matrix{T}}=nothing, hi::Union{Nothing,Matrix{T}}=nothing, lux::Union{Nothing,Array{T,4}}=nothing,
+                     mu::Union{Nothing,Vector{T}}=nothing, status::Union{Nothing,Matrix{Int32}}=nothing, act_off::Integer=0) where T
+    H = size(A, 4); n = 2 * bm.nu; na = size(lu, 1)
+    K = Array{T}(undef, n, na, bm.batch, H); kff = Array{T}(undef, na, bm.batch, H); fail = Vector{Int32}(undef, bm.batch)
+    dV = Matrix{T}(undef, 2, bm.batch); Vx = Matrix{T}(undef, n, bm.batch); Vxx = Array{T}(undef, n, n, bm.batch)
+    active = Matrix{Int64}(undef, bm.batch, H); qp_iters = Matrix{Int32}(undef, bm.batch, H)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve A Bm status lx lu lxx luu lux mu K kff fail dV Vx Vxx U lo hi active qp_iters begin
+        r = Ref(DojoRiccati(p(A), p(Bm), p(status), p(lx), p(lu), p(lxx), p(luu), p(lux), p(mu), p(K), p(kff), p(fail), p(dV), p(Vx), p(Vxx), Int32(act_off), Int32(na)))
+        lim = Ref(DojoControlLimits(p(lo), p(hi)))
+        check(@ccall $(fn(:dojo_riccati_box))(bm.handle::Ptr{Cvoid}, Int32(H)::Int32, r::Ptr{DojoRiccati}, lim::Ptr{DojoControlLimits}, U::Ptr{T}, active::Ptr{Int64},
+                                              qp_iters::Ptr{Int32})::Cint)
+    end
+    return K, kff, dV, fail, active, qp_iters, Vx, Vxx
+end
+
+"""
+`rollout_minimal` with the driven inputs clamped into [lo, hi] (lo[na, B], hi[na, B]; either may be `nothing`) before they are rounded and stepped:
+dojo_rollout_minimal_box, the forward pass of control-limited iLQR.  Everything else as in `rollout_minimal`.
+"""
+function rollout_minimal_box(bm::BatchedMechanism{T}, x0::Matrix{T}, Ubar::Array{T,3}; lo::Union{Nothing,Matrix{T}}=nothing, hi::Union{Nothing,Matrix{T}}=nothing,
+                             Xbar::Union{Nothing,Array{T,3}}=nothing, K::Union{Nothing,Array{T,4}}=nothing, kff::Union{Nothing,Array{T,3}}=nothing,
+                             alpha::Union{Nothing,Vector{T}}=nothing, act_off::Integer=0, na::Integer=bm.nu - act_off, jacobians::Bool=false) where T
+    H = size(Ubar, 3); n = 2 * bm.nu
+    X = Array{T}(undef, n, bm.batch, H + 1); U = Array{T}(undef, bm.nu, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    A = jacobians ? Array{T}(undef, n, n, bm.batch, H) : nothing; Bm = jacobians ? Array{T}(undef, bm.nu, n, bm.batch, H) : nothing
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve x0 Ubar Xbar K kff alpha X U status A Bm lo hi begin
+        t = Ref(DojoTracking(p(x0), p(Ubar), p(Xbar), p(K), p(kff), p(alpha), p(X), p(U), p(status), p(A), p(Bm), Int32(act_off), Int32(na)))
+        lim = Ref(DojoControlLimits(p(lo), p(hi)))
+        check(@ccall $(fn(:dojo_rollout_minimal_box))(bm.handle::Ptr{Cvoid}, Int32(H)::Int32, t::Ptr{DojoTracking}, lim::Ptr{DojoControlLimits})::Cint)
+    end
+    return jacobians ? (X, U, status, A, Bm) : (X, U, status)
+end
+
 """
 reverse mode through a closed-loop rollout (no counterpart in Dojo.jl): the rollout of `rollout_policy` (without contact observations) and the
 gradient of a trajectory loss w.r.t. the policy, the feed-forward term and the initial state; the recorded Jacobians stay on the device.

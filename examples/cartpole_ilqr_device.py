@@ -14,7 +14,11 @@ upright at angle 0 and hangs at pi.
 With --fused the first and the last stage are ONE call of dojo_rollout_minimal_dev each (ilqr.linearize_rollout_fused, ilqr.forward_pass_fused): the steps, the
 feedback law and the Jacobians of the whole horizon on the device, every environment group at its own pace.
 
-    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations] [--fused]          # needs a GPU: libdojo_hip has no CPU fallback
+With --limit F the swing-up runs under |u| <= F (ilqr.solve_limited, control-limited DDP: include/dojo_hip_limits.h): the backward pass is ONE launch of
+dojo_riccati_box_dev (a box QP per step, the gain rows of clamped inputs zero), the forward pass clamps; the largest |u| and the share of steps at the bound are
+printed.
+
+    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations] [--fused] [--limit F]          # needs a GPU: libdojo_hip has no CPU fallback
 """
 import os
 import sys
@@ -32,6 +36,9 @@ from dojo_amd import api, ilqr                         # noqa: E402
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     fused = "--fused" in argv; argv = [a for a in argv if a != "--fused"]
+    limit = None
+    if "--limit" in argv:
+        i = argv.index("--limit"); limit = float(argv[i + 1]); del argv[i:i + 2]
     B = int(argv[0]) if len(argv) > 0 else 64
     H = int(argv[1]) if len(argv) > 1 else 60
     iters = int(argv[2]) if len(argv) > 2 else 40
@@ -49,7 +56,10 @@ def main(argv=None):
                               x_goal=torch.zeros(4, dtype=dt, device=dev))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = ilqr.solve(gm, x0, U0, cost, iters, act_off=0, na=1, fused=fused)
+    if limit is None:
+        res = ilqr.solve(gm, x0, U0, cost, iters, act_off=0, na=1, fused=fused)
+    else:
+        res = ilqr.solve_limited(gm, x0, U0, cost, iters, -limit, limit, act_off=0, na=1, fused=fused)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     J = res["J"].cpu().numpy()
@@ -58,6 +68,10 @@ def main(argv=None):
               ("" if i == J.shape[0] - 1 else "   accepted %d / %d, mu max %.1e" % (int((res["a"][i] > 0).sum()), B, float(res["mu"][i].max()))))
     xH = res["X"][-1].cpu().numpy()
     print("final |pole angle|: min %.3f  median %.3f  max %.3f rad (start: %.3f .. %.3f)" % (np.abs(xH[:, 2]).min(), np.median(np.abs(xH[:, 2])), np.abs(xH[:, 2]).max(), 0.5 * np.pi, np.pi))
+    if limit is not None:
+        u = res["U"][:, :, 0].abs()
+        print("|u| <= %g: largest |u| %.6g, %.1f %% of the %d environment-steps at the bound" % (limit, float(u.max()), 100.0 * float((u == limit).double().mean()), u.numel()))
+        assert float(u.max()) <= limit
     print("%d environments x %d steps x %d iterations in %.2f s%s" % (B, H, iters, el, " (fused rollouts)" if fused else ""))
     assert (J[-1] <= J[0]).all()
     gm.close()
