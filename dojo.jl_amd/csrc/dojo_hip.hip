@@ -19,7 +19,7 @@
 #include "dojo_tangent.hpp"
 #include "dojo_riccati.hpp"
 #include "dojo_tracking.hpp"
-#include "../../include/dojo_hip_limits.h"      // (includes dojo_hip_trajopt.h)
+#include "../../include/dojo_hip_constraints.h"      // (includes dojo_hip_limits.h, which includes dojo_hip_trajopt.h)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -994,29 +994,36 @@ int launch_tangent(const DojoSim* s, int H, int T, const void* DZ, const void* D
 
 // what dojo_riccati_box_dev takes on top of the DojoRiccati record (include/dojo_hip_limits.h); null in its place: the unconstrained pass
 struct RiccatiBox { const DojoControlLimits* lim; const void* U; int64_t* active; int32_t* qp_iters; };
+// ... and what dojo_riccati_al_dev takes on top of that (include/dojo_hip_constraints.h); with it lim and U of the box may be null
+using RiccatiCon = DojoStageConstraints;
 
-// dojo_riccati_dev, dojo_riccati_box_dev: the Riccati backward pass (dojo_riccati.hpp), one workgroup per environment, one launch; NQ = register accumulators per lane
+// dojo_riccati_dev, dojo_riccati_box_dev, dojo_riccati_al_dev: the Riccati backward pass (dojo_riccati.hpp), one workgroup per environment, one launch; NQ = register accumulators per lane
 template <class TIO, int NQ>
-int launch_riccati(const DojoSim* s, int H, const DojoRiccati& r, const RiccatiBox* box, hipStream_t st) {
+int launch_riccati(const DojoSim* s, int H, const DojoRiccati& r, const RiccatiBox* box, const RiccatiCon* con, hipStream_t st) {
     const int nu = (int)s->M.nu, n = 2 * nu;
     const dj::riccati::Args<TIO> A{(const TIO*)r.A, (const TIO*)r.Bm, r.status, (const TIO*)r.lx, (const TIO*)r.lu, (const TIO*)r.lxx, (const TIO*)r.luu, (const TIO*)r.lux, (const TIO*)r.mu,
                                    (TIO*)r.K, (TIO*)r.kff, r.fail, (TIO*)r.dV, (TIO*)r.Vx, (TIO*)r.Vxx, H, s->B, n, nu, r.na, r.act_off};
     if (box) {
-        dj::riccati::BoxArgs<TIO> bx; static_cast<dj::riccati::Args<TIO>&>(bx) = A;
-        bx.lo = (const TIO*)box->lim->lo; bx.hi = (const TIO*)box->lim->hi; bx.U = (const TIO*)box->U; bx.active = (long long*)box->active; bx.iters = box->qp_iters;
-        hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ, dj::riccati::BoxArgs<TIO>>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::box_lds_bytes(n, r.na), st, bx);
+        dj::riccati::AlArgs<TIO> al{}; dj::riccati::BoxArgs<TIO>& bx = al; static_cast<dj::riccati::Args<TIO>&>(bx) = A;
+        bx.lo = (const TIO*)(box->lim ? box->lim->lo : nullptr); bx.hi = (const TIO*)(box->lim ? box->lim->hi : nullptr); bx.U = (const TIO*)box->U;
+        bx.active = (long long*)box->active; bx.iters = box->qp_iters;
+        if (con && (con->nc > 0 || !box->U)) {       // (no rows: the control-limited kernel is the constrained one's bits and has fewer registers; it needs U, though)
+            al.Cx = (const TIO*)con->Cx; al.Cu = (const TIO*)con->Cu; al.w = (const TIO*)con->w; al.y = (const TIO*)con->y; al.nc = con->nc; al.shared = con->shared;
+            hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ, dj::riccati::AlArgs<TIO>>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::al_lds_bytes(n, r.na), st, al);
+        } else
+            hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ, dj::riccati::BoxArgs<TIO>>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::box_lds_bytes(n, r.na), st, bx);
     } else
         hipLaunchKernelGGL((dj::riccati::riccati_kernel<TIO, NQ>), dim3((unsigned)s->B), dim3(dj::riccati::THREADS), dj::riccati::lds_bytes(n, r.na), st, A);
     HIPCHK(hipGetLastError());
     return DOJO_OK;
 }
 template <class TIO>
-int launch_riccati_any(const DojoSim* s, int H, const DojoRiccati& r, const RiccatiBox* box, hipStream_t st) {
+int launch_riccati_any(const DojoSim* s, int H, const DojoRiccati& r, const RiccatiBox* box, const RiccatiCon* con, hipStream_t st) {
     switch (dj::riccati::accumulators(2 * (int)s->M.nu, r.na)) {
-        case 3: return launch_riccati<TIO, 3>(s, H, r, box, st);
-        case 6: return launch_riccati<TIO, 6>(s, H, r, box, st);
-        case 12: return launch_riccati<TIO, 12>(s, H, r, box, st);
-        default: return launch_riccati<TIO, 24>(s, H, r, box, st);
+        case 3: return launch_riccati<TIO, 3>(s, H, r, box, con, st);
+        case 6: return launch_riccati<TIO, 6>(s, H, r, box, con, st);
+        case 12: return launch_riccati<TIO, 12>(s, H, r, box, con, st);
+        default: return launch_riccati<TIO, 24>(s, H, r, box, con, st);
     }
 }
 
@@ -1817,33 +1824,72 @@ static int refuse_limit_values(DojoHandle s, const DojoControlLimits* lim, size_
     });
 }
 
-// box = null: dojo_riccati_dev
-static int riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox* box, void* stream, const char* who) {
+// ... and what the constrained entries refuse (include/dojo_hip_constraints.h): the limits are optional there, the constraints record is not
+static int refuse_riccati_al(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox& box, const RiccatiCon* con, const char* who) {
+    TRY(refuse_riccati(s, H, r, who));
+    const std::string w_ = std::string(who) + ": ";
+    if (!con) { g_err = w_ + "con must not be NULL"; return DOJO_ERR_INVALID; }
+    if (con->nc < 0) { g_err = w_ + "nc must be >= 0"; return DOJO_ERR_INVALID; }
+    if (con->nc > 0 && (!con->Cx || !con->w || !con->y)) { g_err = w_ + "Cx, w and y must not be NULL with nc > 0"; return DOJO_ERR_INVALID; }
+    if (box.lim && !box.U) { g_err = w_ + "U must not be NULL with limits"; return DOJO_ERR_INVALID; }
+    const int n = 2 * (int)s->M.nu, m = r->na;
+    const size_t lds = dj::riccati::al_lds_bytes(n, m);
+    if (lds > 65536) {
+        g_err = w_ + "n = " + std::to_string(n) + ", na = " + std::to_string(m) + " needs " + std::to_string(lds) + " bytes of LDS per environment with the box QP; the kernel holds at most 65536";
+        return DOJO_ERR_UNSUPPORTED;
+    }
+    return DOJO_OK;
+}
+// the weights and multipliers of a host entry are read: w < 0 and NaN are refused (the device entry cannot look)
+static int refuse_constraint_values(DojoHandle s, const RiccatiCon* con, size_t count, const char* who) {
+    return by_dtype(s, [&](auto t) {
+        using T = decltype(t);
+        const T* const w = (const T*)con->w; const T* const y = (const T*)con->y;
+        for (size_t i = 0; i < count; ++i)
+            if (!((double)w[i] >= 0.0) || (double)y[i] != (double)y[i]) {
+                g_err = std::string(who) + ": w must be >= 0 and w, y must not be NaN (element " + std::to_string(i) + " of [H+1][B][nc])"; return DOJO_ERR_INVALID;
+            }
+        return DOJO_OK;
+    });
+}
+
+// box = null: dojo_riccati_dev; con != null (with a box whose lim and U may be null): dojo_riccati_al_dev
+static int riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox* box, const RiccatiCon* con, bool al, void* stream, const char* who) {
     Enter enter_(s);
-    TRY(box ? refuse_riccati_box(s, H, r, *box, who) : refuse_riccati(s, H, r, who));
+    TRY(al ? refuse_riccati_al(s, H, r, *box, con, who) : box ? refuse_riccati_box(s, H, r, *box, who) : refuse_riccati(s, H, r, who));
     HIPCHK(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     TRY(join_groups(s, st));                  // (asynchronous steps still in flight: the last dojo_minimal_gradients_dev may be writing the record)
-    return by_dtype(s, [&](auto t) { return launch_riccati_any<decltype(t)>(s, H, *r, box, st); });
+    const RiccatiCon c = al ? *con : RiccatiCon{};      // (the caller's struct is read during the call only)
+    return by_dtype(s, [&](auto t) { return launch_riccati_any<decltype(t)>(s, H, *r, box, al ? &c : nullptr, st); });
 }
-int dojo_riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, void* stream) { return riccati_dev(s, H, r, nullptr, stream, "dojo_riccati_dev"); }
+int dojo_riccati_dev(DojoHandle s, int32_t H, const DojoRiccati* r, void* stream) { return riccati_dev(s, H, r, nullptr, nullptr, false, stream, "dojo_riccati_dev"); }
 int dojo_riccati_box_dev(DojoHandle s, int32_t H, const DojoRiccati* r, const DojoControlLimits* lim, const void* U, int64_t* active, int32_t* qp_iters, void* stream) {
     const RiccatiBox box{lim, U, active, qp_iters};
-    return riccati_dev(s, H, r, &box, stream, "dojo_riccati_box_dev");
+    return riccati_dev(s, H, r, &box, nullptr, false, stream, "dojo_riccati_box_dev");
+}
+int dojo_riccati_al_dev(DojoHandle s, int32_t H, const DojoRiccati* r, const DojoControlLimits* lim, const void* U, const DojoStageConstraints* con, int64_t* active, int32_t* qp_iters,
+                        void* stream) {
+    const RiccatiBox box{lim, U, active, qp_iters};
+    return riccati_dev(s, H, r, &box, con, true, stream, "dojo_riccati_al_dev");
 }
 
 // host pointers: upload, one launch, download
-static int riccati_host(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox* box, const char* who) {
+static int riccati_host(DojoHandle s, int32_t H, const DojoRiccati* r, const RiccatiBox* box, const RiccatiCon* con, bool al, const char* who) {
     Enter enter_(s);
-    TRY(box ? refuse_riccati_box(s, H, r, *box, who) : refuse_riccati(s, H, r, who));
+    TRY(al ? refuse_riccati_al(s, H, r, *box, con, who) : box ? refuse_riccati_box(s, H, r, *box, who) : refuse_riccati(s, H, r, who));
     HIPCHK(hipSetDevice(s->device));
-    const size_t B = s->B, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)r->na, HB = (size_t)H * B;
-    if (box) TRY(refuse_limit_values(s, box->lim, B * m, who));
+    const size_t B = s->B, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)r->na, HB = (size_t)H * B, nc = al ? (size_t)con->nc : 0;
+    if (box && box->lim) TRY(refuse_limit_values(s, box->lim, B * m, who));
+    if (nc) TRY(refuse_constraint_values(s, con, (HB + B) * nc, who));
     Staging st;
     const auto &dA = st.input(HB * n * n * w, r->A), &dB = st.input(HB * n * nu * w, r->Bm), &dS = st.input(HB * sizeof(int32_t), r->status);
     const auto &dlx = st.input((HB + B) * n * w, r->lx), &dlu = st.input(HB * m * w, r->lu), &dlxx = st.input((HB + B) * n * n * w, r->lxx);
     const auto &dluu = st.input(HB * m * m * w, r->luu), &dlux = st.input(HB * m * n * w, r->lux), &dmu = st.input(B * w, r->mu);
-    const auto &dlo = st.input(B * m * w, box ? box->lim->lo : nullptr), &dhi = st.input(B * m * w, box ? box->lim->hi : nullptr), &dU = st.input(HB * nu * w, box ? box->U : nullptr);
+    const auto &dlo = st.input(B * m * w, box && box->lim ? box->lim->lo : nullptr), &dhi = st.input(B * m * w, box && box->lim ? box->lim->hi : nullptr), &dU = st.input(HB * nu * w, box ? box->U : nullptr);
+    const bool sh = nc && con->shared;
+    const auto &dCx = st.input((sh ? 1 : HB + B) * nc * n * w, nc ? con->Cx : nullptr), &dCu = st.input((sh ? 1 : HB) * nc * m * w, nc ? con->Cu : nullptr);
+    const auto &dw = st.input((HB + B) * nc * w, nc ? con->w : nullptr), &dy = st.input((HB + B) * nc * w, nc ? con->y : nullptr);
     const auto &dK = st.output(HB * m * n * w, r->K), &dk = st.output(HB * m * w, r->kff), &dF = st.output(B * sizeof(int32_t), r->fail);
     const auto &ddV = st.output(B * 2 * w, r->dV), &dVx = st.output(B * n * w, r->Vx), &dVxx = st.output(B * n * n * w, r->Vxx);
     const auto &dact = st.output(HB * sizeof(int64_t), box ? box->active : nullptr), &dit = st.output(HB * sizeof(int32_t), box ? box->qp_iters : nullptr);
@@ -1852,14 +1898,19 @@ static int riccati_host(DojoHandle s, int32_t H, const DojoRiccati* r, const Ric
     d.A = dA.p; d.Bm = dB.p; d.status = (const int32_t*)dS.p; d.lx = dlx.p; d.lu = dlu.p; d.lxx = dlxx.p; d.luu = dluu.p; d.lux = dlux.p; d.mu = dmu.p;
     d.K = dK.p; d.kff = dk.p; d.fail = (int32_t*)dF.p; d.dV = ddV.p; d.Vx = dVx.p; d.Vxx = dVxx.p;
     const DojoControlLimits dlim{dlo.p, dhi.p};
-    const RiccatiBox dbox{&dlim, dU.p, (int64_t*)dact.p, (int32_t*)dit.p};
-    TRY(riccati_dev(s, H, &d, box ? &dbox : nullptr, nullptr, who));
+    const RiccatiBox dbox{box && box->lim ? &dlim : nullptr, dU.p, (int64_t*)dact.p, (int32_t*)dit.p};
+    const RiccatiCon dcon{dCx.p, dCu.p, dw.p, dy.p, (int32_t)nc, al ? con->shared : 0};
+    TRY(riccati_dev(s, H, &d, box ? &dbox : nullptr, al ? &dcon : nullptr, al, nullptr, who));
     return st.finish();      // (no state: the handle's own is left alone)
 }
-int dojo_riccati(DojoHandle s, int32_t H, const DojoRiccati* r) { return riccati_host(s, H, r, nullptr, "dojo_riccati"); }
+int dojo_riccati(DojoHandle s, int32_t H, const DojoRiccati* r) { return riccati_host(s, H, r, nullptr, nullptr, false, "dojo_riccati"); }
 int dojo_riccati_box(DojoHandle s, int32_t H, const DojoRiccati* r, const DojoControlLimits* lim, const void* U, int64_t* active, int32_t* qp_iters) {
     const RiccatiBox box{lim, U, active, qp_iters};
-    return riccati_host(s, H, r, &box, "dojo_riccati_box");
+    return riccati_host(s, H, r, &box, nullptr, false, "dojo_riccati_box");
+}
+int dojo_riccati_al(DojoHandle s, int32_t H, const DojoRiccati* r, const DojoControlLimits* lim, const void* U, const DojoStageConstraints* con, int64_t* active, int32_t* qp_iters) {
+    const RiccatiBox box{lim, U, active, qp_iters};
+    return riccati_host(s, H, r, &box, con, true, "dojo_riccati_al");
 }
 
 // ---- rollouts in minimal coordinates with the tracking controller (dojo_tracking.hpp, include/dojo_hip_trajopt.h): iLQR's forward pass and its linearization, one call each ----

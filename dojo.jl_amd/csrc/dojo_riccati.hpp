@@ -43,7 +43,7 @@
 // array pointers of Args and the step's bases).  Ant runs four workgroups per CU, Atlas two (LDS).
 //
 // Not part of it: the forward pass as one fused call (it needs time-varying gains in the controller kernel: a follow-up), costs shared across the batch or given
-// as diagonals, second-order dynamics terms (DDP), constraints other than control limits (augmented Lagrangian), kinematic loops.  Control limits: the variant below.
+// as diagonals, second-order dynamics terms (DDP), second-order constraint terms, kinematic loops.  Control limits and other constraints: the variants below.
 //
 // The control-limited variant (dojo_riccati_box_dev, include/dojo_hip_limits.h: the recursion, the solver and the failure codes are documented there) is this
 // kernel over BoxArgs, every difference behind `if constexpr (BOX)`; the instantiations over Args keep the instructions they had before it existed.  Per step:
@@ -61,6 +61,17 @@
 // LDS: the plan above + m doubles (dl): Ant 13 296 B, Quadruped 18 736 B, Atlas (72, 30) 55 120 B, Atlas with all 36 inputs 65 152 B (fits).  Resources, NQ = 3 / 6
 // / 12 / 24: fp32 147 / 153 / 171 / 207 VGPRs, fp64 136 / 145 / 163 / 199; no AGPRs, no scratch, no VGPR spills (146 .. 178 SGPRs parked in VGPR lanes).  The Ant's
 // fp32 build is over 128: three workgroups per CU where the unconstrained one runs four (4.06 ms against 3.11 ms with limits that clip nothing).
+//
+// The constrained variant (dojo_riccati_al_dev, include/dojo_hip_constraints.h: the recursion and the refusals are documented there) is the control-limited kernel
+// over AlArgs (BOX holds for it too), every further difference behind `if constexpr (AL)`; the sixteen instantiations over Args and BoxArgs keep their instructions.
+// The augmented-Lagrangian terms of nc constraint rows per stage, G' diag(w) G and G' y with G = [Cx Cu], never exist in memory (al_rows):
+//   * behind the dynamics blocks of a step -- also of a failed one -- the rows go R = 16 at a time through the same row buffers, Fb = G, Tb = diag(w) G, and the same
+//     accumulator loop; q += G' y is taken by lane j over the block's rows; two barriers per block;
+//   * a row with w = y = 0 is not loaded, a block of 16 such rows is skipped with its barriers.  Lane l of every wavefront reads w, y of row l and a ballot gives
+//     every wavefront the same mask: one load per 64 rows, issued a step ahead (w_next, y_next) so that its latency is hidden behind the step in between;
+//   * the terminal stage: the owners of the packed Vxx entries load them into accumulators, run the same blocks over Cx_H alone and write them back;
+//   * lim = NULL is lo = hi = NULL (U is then not read).  The host launches the control-limited kernel when nc = 0 and U is given: the same bits, fewer registers.
+// LDS: box_lds_bytes, nothing on top (al_lds_bytes), whatever nc.  Resources, NQ = 3 / 6 / 12 / 24: see DESIGN.md 5k.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dojo_math.hpp"
@@ -88,6 +99,12 @@ template <class TIO> struct BoxArgs : Args<TIO> {
     int* iters;             // [H][B] or null
 };
 
+// the argument record of the constrained variant (include/dojo_hip_constraints.h): riccati_kernel<TIO, NQ, AlArgs<TIO>>.  lo, hi and U may all be null: no limits
+template <class TIO> struct AlArgs : BoxArgs<TIO> {
+    const TIO *Cx, *Cu, *w, *y;     // [H+1][B][nc][n] ([nc][n] when shared), [H][B][nc][m] ([nc][m] when shared) or null: zeros, [H+1][B][nc], [H+1][B][nc]
+    int nc, shared;
+};
+
 constexpr int THREADS = 256, R = 16, RB = 4, MAX_M = 64;        // lanes per workgroup, rows of T per block, rows per lane in a block, rows of the one-wavefront Cholesky
 inline int entries(int n, int m) { return (n + m) * (n + m + 1) / 2; }                                   // lower triangle of Q
 inline int accumulators(int n, int m) {                                                                  // NQ of the instantiation that holds them, 0: none does
@@ -98,6 +115,7 @@ inline int accumulators(int n, int m) {                                         
 inline size_t region1(int n, int m) { const size_t a = 2 * (size_t)R * (n + m), b = (size_t)m * n + 2 * (size_t)m * m; return a > b ? a : b; }
 inline size_t lds_bytes(int n, int m) { return ((size_t)n * (n + 1) / 2 + region1(n, m) + (size_t)n + (n + m) + 3 * (size_t)m + 8) * sizeof(double); }
 inline size_t box_lds_bytes(int n, int m) { return lds_bytes(n, m) + (size_t)m * sizeof(double); }      // + the trial step of the QP
+inline size_t al_lds_bytes(int n, int m) { return box_lds_bytes(n, m); }                                // the constraint rows go through Fb, Tb: nothing on top, whatever nc
 
 #if defined(__HIPCC__)
 // LDS written by some lanes of a wavefront, read by others of the same wavefront: the hardware keeps a wavefront's LDS operations in order, the fence keeps the compiler from moving them
@@ -214,10 +232,61 @@ __device__ inline int box_qp(const double* Quu, double* L, double* kf, double* d
     return 2;
 }
 
+// ---- the constraint rows of a stage (the AlArgs variant): acc += G' diag(w) G over the entries rc, q += G' y, G = [Cx Cu] (nc x N; columns >= cols count as zero:
+// the terminal stage has cols = n), R rows at a time through the row buffers: Fb = G, Tb = diag(w) G, the accumulator loop of the sweep; q[j] is lane j's.  A row
+// with w = y = 0 is not loaded; a block without a live row is skipped with its barriers.  That decision is the workgroup's: lane l of EVERY wavefront reads w, y of
+// row i0 + l and the ballot gives each wavefront the same mask (one load per 64 rows, not one per row).  w0, y0: lane l's w, y of row l (rows < 64) when the caller
+// has them already (have0: the sweep loads them a step ahead, so that their latency is not the step's).  Ends behind a barrier whenever it wrote to Fb, Tb ----
+template <class TIO, int NQ>
+__device__ __forceinline__ void al_rows(const TIO* Cx, const TIO* Cu, const TIO* wg, const TIO* yg, int nc, int n, int m, int cols, const int (&rc)[NQ], double (&acc)[NQ],
+                                        double* Fb, double* Tb, double* q, int tid, bool have0, double w0, double y0) {
+    const int N = n + m;
+    for (int c0 = 0; c0 < nc; c0 += 64) {
+        const int il = c0 + (tid & 63);
+        double wl = w0, yl = y0;
+        if (!(have0 && c0 == 0)) { wl = (double)wg[il < nc ? il : 0]; yl = (double)yg[il < nc ? il : 0]; }
+        const unsigned long long live64 = __ballot(il < nc && !(wl == 0.0 && yl == 0.0));
+        for (int i0 = c0; i0 < nc && i0 < c0 + 64; i0 += R) {
+            const unsigned live = (unsigned)(live64 >> (i0 - c0)) & 0xffffu;
+            if (live == 0) continue;
+            for (int o = tid; o < R * N; o += THREADS) {
+                const int kk = o / N, j = o - kk * N, i = i0 + kk;
+                double g = 0.0, wi = 0.0;
+                if ((live >> kk & 1) && j < cols) {
+                    wi = (double)wg[i];
+                    g = j < n ? (double)Cx[(size_t)i * n + j] : Cu ? (double)Cu[(size_t)i * m + (j - n)] : 0.0;
+                }
+                Fb[o] = g; Tb[o] = wi * g;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int qq = 0; qq < NQ; ++qq) {
+                int w = rc[qq]; DJ_OPAQUE(w);
+                if (w >= 0) {
+                    const double* const fr = Fb + (w >> 16); const double* const tc = Tb + (w & 0xffff);
+                    double s = acc[qq];
+#pragma unroll 4
+                    for (int kk = 0; kk < R; ++kk) s = fma(fr[kk * N], tc[kk * N], s);
+                    acc[qq] = s;
+                }
+            }
+            for (int j = tid; j < cols; j += THREADS) {
+                double s = q[j];
+#pragma unroll 4
+                for (int kk = 0; kk < R; ++kk) if (live >> kk & 1) s = fma((double)yg[i0 + kk], Fb[kk * N + j], s);
+                q[j] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // A_ = BoxArgs<TIO>: the control-limited variant (BOX; every difference sits behind `if constexpr (BOX)`: the instantiations over Args<TIO> keep their instructions)
+// A_ = AlArgs<TIO>: the constrained variant (AL, with BOX; every difference behind `if constexpr (AL)`: the instantiations over Args and BoxArgs keep theirs)
 template <class TIO, int NQ, class A_ = Args<TIO>>
 __global__ void __launch_bounds__(THREADS) riccati_kernel(const A_ a) {
-    constexpr bool BOX = std::is_same<A_, BoxArgs<TIO>>::value;
+    constexpr bool AL = std::is_same<A_, AlArgs<TIO>>::value;
+    constexpr bool BOX = AL || std::is_same<A_, BoxArgs<TIO>>::value;
     extern __shared__ __align__(16) double lds_[];
     const int H = a.H, B = a.B, n = a.n, nu = a.nu, m = a.m, N = n + m, b = (int)blockIdx.x, tid = (int)threadIdx.x;
     const int nV = n * (n + 1) / 2, ne = N * (N + 1) / 2;
@@ -261,7 +330,29 @@ __global__ void __launch_bounds__(THREADS) riccati_kernel(const A_ a) {
     }
     double dV0 = 0.0, dV1 = 0.0;          // (lane 0's)
     __syncthreads();
+    if constexpr (AL) {
+        // the terminal rows: Vxx += sum_i w_i Cx_H[i]' Cx_H[i], Vx += sum_i y_i Cx_H[i] over the live rows, i ascending; the owner of a packed entry takes its own sum
+        if (a.nc > 0) {
+            const size_t kb = (size_t)H * B + b;
+            double acc[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) { int w = rc[q]; DJ_OPAQUE(w); acc[q] = (w >= 0 && (w >> 16) < n) ? Vp[tid + q * THREADS] : 0.0; }
+            al_rows<TIO, NQ>(DJ_GLOBAL_PTR(const TIO, a.Cx) + (a.shared ? (size_t)0 : kb * a.nc * n), nullptr, DJ_GLOBAL_PTR(const TIO, a.w) + kb * a.nc,
+                             DJ_GLOBAL_PTR(const TIO, a.y) + kb * a.nc, a.nc, n, m, n, rc, acc, r1, r1 + R * N, Vx, tid, false, 0.0, 0.0);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) { int w = rc[q]; DJ_OPAQUE(w); if (w >= 0 && (w >> 16) < n) Vp[tid + q * THREADS] = acc[q]; }
+            __syncthreads();
+        }
+    }
 
+    TIO w_next = (TIO)0, y_next = (TIO)0;      // (AL) lane l of every wavefront: w, y of row l (rows < 64) of the step to come, loaded a step ahead
+    (void)w_next; (void)y_next;
+    if constexpr (AL) {
+        if (a.nc > 0) {
+            const size_t o = ((size_t)(H - 1) * B + b) * a.nc + ((tid & 63) < a.nc ? (tid & 63) : 0);
+            w_next = DJ_GLOBAL_PTR(const TIO, a.w)[o]; y_next = DJ_GLOBAL_PTR(const TIO, a.y)[o];
+        }
+    }
     for (int k = H - 1; k >= 0; --k) {
         const size_t kb = (size_t)k * B + b;
         const bool failed = status != nullptr && status[kb] != 0;
@@ -323,6 +414,19 @@ __global__ void __launch_bounds__(THREADS) riccati_kernel(const A_ a) {
                 __syncthreads();
             }
         }
+        if constexpr (AL) {
+            // Q += G' diag(w) G, q += G' y over the live rows of the step (al_rows) -- also at a failed step: its cost terms stand
+            if (a.nc > 0) {
+                const double w_now = (double)w_next, y_now = (double)y_next;
+                if (k > 0) {
+                    const size_t o = (kb - B) * a.nc + ((tid & 63) < a.nc ? (tid & 63) : 0);
+                    w_next = DJ_GLOBAL_PTR(const TIO, a.w)[o]; y_next = DJ_GLOBAL_PTR(const TIO, a.y)[o];
+                }
+                al_rows<TIO, NQ>(DJ_GLOBAL_PTR(const TIO, a.Cx) + (a.shared ? (size_t)0 : kb * a.nc * n),
+                                 a.Cu ? DJ_GLOBAL_PTR(const TIO, a.Cu) + (a.shared ? (size_t)0 : kb * a.nc * m) : nullptr,
+                                 DJ_GLOBAL_PTR(const TIO, a.w) + kb * a.nc, DJ_GLOBAL_PTR(const TIO, a.y) + kb * a.nc, a.nc, n, m, N, rc, acc, Fb, Tb, qv, tid, true, w_now, y_now);
+            }
+        }
         // Qux, Quu leave the registers
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -340,7 +444,9 @@ __global__ void __launch_bounds__(THREADS) riccati_kernel(const A_ a) {
             bool ok = true, empty = false;
             if constexpr (BOX) {
                 if (tid < m) {
-                    const double u = (double)DJ_GLOBAL_PTR(const TIO, a.U)[kb * nu + a.act_off + tid];
+                    double u;
+                    if constexpr (AL) u = a.U ? (double)DJ_GLOBAL_PTR(const TIO, a.U)[kb * nu + a.act_off + tid] : 0.0;      // (null only without limits)
+                    else u = (double)DJ_GLOBAL_PTR(const TIO, a.U)[kb * nu + a.act_off + tid];
                     if (a.lo) lo_ = (double)DJ_GLOBAL_PTR(const TIO, a.lo)[(size_t)b * m + tid] - u;
                     if (a.hi) hi_ = (double)DJ_GLOBAL_PTR(const TIO, a.hi)[(size_t)b * m + tid] - u;
                 }

@@ -63,6 +63,9 @@ TRAJOPT_SYMBOLS = list(_TRAJOPT_SIGNATURES)
 _LIMITS_SIGNATURES = {"dojo_riccati_box_dev": (C.c_int, "pipppppp"), "dojo_riccati_box": (C.c_int, "pippppp"),
                       "dojo_rollout_minimal_box_dev": (C.c_int, "pippp"), "dojo_rollout_minimal_box": (C.c_int, "pipp")}
 LIMITS_SYMBOLS = list(_LIMITS_SIGNATURES)
+# include/dojo_hip_constraints.h, the fourth: the augmented-Lagrangian terms of stage constraints in the backward pass
+_CONSTRAINT_SIGNATURES = {"dojo_riccati_al_dev": (C.c_int, "pippppppp"), "dojo_riccati_al": (C.c_int, "pipppppp")}
+CONSTRAINT_SYMBOLS = list(_CONSTRAINT_SIGNATURES)
 
 
 def lib():
@@ -71,7 +74,7 @@ def lib():
         if not os.path.exists(_LIB_PATH):
             raise DojoError("libdojo_hip.so not built (run __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(_LIB_PATH)
-        for name, (restype, args) in {**_SIGNATURES, **_TRAJOPT_SIGNATURES, **_LIMITS_SIGNATURES}.items():
+        for name, (restype, args) in {**_SIGNATURES, **_TRAJOPT_SIGNATURES, **_LIMITS_SIGNATURES, **_CONSTRAINT_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, [_KINDS[k] for k in args]
         _lib = L
@@ -128,6 +131,13 @@ class DojoControlLimits(C.Structure):
     """include/dojo_hip_limits.h `DojoControlLimits`: the limits lo, hi [B][na] of the driven inputs (either may be NULL: none on that side); device pointers
     for the _dev entries, host pointers for dojo_riccati_box and dojo_rollout_minimal_box"""
     _fields_ = [("lo", C.c_void_p), ("hi", C.c_void_p)]
+
+
+class DojoStageConstraints(C.Structure):
+    """include/dojo_hip_constraints.h `DojoStageConstraints`: the linearized constraints of every stage -- Cx [H+1][B][nc][n] and Cu [H][B][nc][na] ([nc][n] and
+    [nc][na] when shared; Cu may be NULL: zeros), the row weights w and the multiplier estimates y, [H+1][B][nc] each; device pointers for dojo_riccati_al_dev,
+    host pointers for dojo_riccati_al"""
+    _fields_ = [("Cx", C.c_void_p), ("Cu", C.c_void_p), ("w", C.c_void_p), ("y", C.c_void_p), ("nc", C.c_int32), ("shared", C.c_int32)]
 
 
 MLP_MAX_LAYERS = 4      # DOJO_MLP_MAX_LAYERS
@@ -560,6 +570,31 @@ class BatchedMechanism:
         keep, lim = self._limits(lo, hi, na)
         r = DojoRiccati(*map(addr, (A, Bm, status, lx, lu, lxx, luu, lux, mu, K, kff, fail, dV, Vx, Vxx)), int(act_off), na)
         _chk(lib().dojo_riccati_box(self.h, H, C.byref(r), C.byref(lim), addr(U), addr(active), addr(qp_iters)))
+        return (K, kff, dV, fail, active, qp_iters, Vx, Vxx) if value else (K, kff, dV, fail, active, qp_iters)
+
+    def riccati_al(self, A, Bm, lx, lu, lxx, luu, Cx, w, y, Cu=None, shared=False, U=None, lo=None, hi=None, lux=None, mu=None, status=None, act_off=0, na=None,
+                   value=True):
+        """dojo_riccati_al (host arrays): `riccati_box` with the augmented-Lagrangian terms of nc linearized constraint rows per stage added to the step's
+        model inside the kernel: G' diag(w) G to the Hessian and G' y to the gradient, G = [Cx Cu].  Cx [H+1,B,nc,n], Cu [H,B,nc,na] or None (zeros) -- [nc,n]
+        and [nc,na] with shared --, w, y [H+1,B,nc] (a row with w = y = 0 is not read).  lo, hi as in riccati_box; both None: no limits, and U may be None.
+        nc = 0: Cx, w, y may be None.  -> what riccati_box returns."""
+        B, nu = self.batch, self.spec.nu; n = 2 * nu
+        H = int(np.shape(A)[0]); na = int(nu - act_off if na is None else na)
+        nc = 0 if w is None else int(np.shape(w)[-1])
+        A = self._arr(A, (H, B, n, n)); Bm = self._arr(Bm, (H, B, n, nu)); U = None if U is None else self._arr(U, (H, B, nu))
+        lx = self._arr(lx, (H + 1, B, n)); lu = self._arr(lu, (H, B, na)); lxx = self._arr(lxx, (H + 1, B, n, n)); luu = self._arr(luu, (H, B, na, na))
+        lux = None if lux is None else self._arr(lux, (H, B, na, n)); mu = None if mu is None else self._arr(mu, (B,))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32)
+        opt = lambda a, shape: None if a is None else self._arr(a, shape)
+        Cx = opt(Cx, (nc, n) if shared else (H + 1, B, nc, n)); Cu = opt(Cu, (nc, na) if shared else (H, B, nc, na))
+        w = opt(w, (H + 1, B, nc)); y = opt(y, (H + 1, B, nc))
+        K = np.empty((H, B, na, n), self.np_dtype); kff = np.empty((H, B, na), self.np_dtype); fail = np.empty(B, np.int32); dV = np.empty((B, 2), self.np_dtype)
+        Vx = np.empty((B, n), self.np_dtype) if value else None; Vxx = np.empty((B, n, n), self.np_dtype) if value else None
+        active = np.empty((H, B), np.int64); qp_iters = np.empty((H, B), np.int32)
+        keep, lim = self._limits(lo, hi, na)
+        con = DojoStageConstraints(addr(Cx), addr(Cu), addr(w), addr(y), nc, int(bool(shared)))
+        r = DojoRiccati(*map(addr, (A, Bm, status, lx, lu, lxx, luu, lux, mu, K, kff, fail, dV, Vx, Vxx)), int(act_off), na)
+        _chk(lib().dojo_riccati_al(self.h, H, C.byref(r), None if lo is None and hi is None else C.byref(lim), addr(U), C.byref(con), addr(active), addr(qp_iters)))
         return (K, kff, dV, fail, active, qp_iters, Vx, Vxx) if value else (K, kff, dV, fail, active, qp_iters)
 
     def rollout_minimal_box(self, x0, lo=None, hi=None, steps=None, Ubar=None, Xbar=None, K=None, kff=None, alpha=None, act_off=0, na=None, jacobians=False):

@@ -10,10 +10,13 @@ the same loop for B environments at once -- one trajectory, one regularisation a
     K, kff, dV, fail, active, qp_iters = riccati_box(gm, A, Bm, lx, lu, lxx, luu, U, lo, hi)   # ONE launch of dojo_riccati_box_dev: a box QP per step
     X, U, status = rollout_minimal_box(gm, x0, Ubar, lo, hi, Xbar, K, kff, a)                  # dojo_rollout_minimal_box_dev: the clamped tracking law
     res = solve_limited(gm, x0, U0, cost, 10, lo, hi)                                          # control-limited iLQR, lo <= u[act] <= hi
+    K, kff, dV, fail, active, qp_iters = riccati_al(gm, A, Bm, lx, lu, lxx, luu, Cx, w, y)     # ONE launch of dojo_riccati_al_dev: the AL terms of constraint rows added in the kernel
+    res = solve_constrained(gm, x0, U0, cost, GoalConstraint(x_goal), iters=4, outer=5)        # the augmented-Lagrangian loop: a terminal goal, state bounds
 
 Everything is enqueued on torch's current stream.  The driver reads one flag per trial step length (have all environments accepted?) and nothing else.
-Not here (include/dojo_hip.h, "Batched iLQR"; include/dojo_hip_trajopt.h): costs shared across the batch, second-order dynamics terms, constraints other than
-control limits (those: include/dojo_hip_limits.h, solve_limited), running the step lengths of a line search side by side, kinematic loops."""
+Not here (include/dojo_hip.h, "Batched iLQR"; include/dojo_hip_trajopt.h): costs shared across the batch, second-order dynamics terms, second-order constraint
+terms and constraints evaluated on the device (control limits: include/dojo_hip_limits.h, solve_limited; other constraints: include/dojo_hip_constraints.h,
+solve_constrained), running the step lengths of a line search side by side, kinematic loops."""
 import ctypes as C
 
 import torch
@@ -57,8 +60,8 @@ def riccati(gm, A, Bm, lx, lu, lxx, luu, lux=None, mu=None, status=None, act_off
     return _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, None)
 
 
-def _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, _box):
-    """riccati (_box None) and riccati_box (_box = (U, lo, hi)): the checks and the outputs they share"""
+def _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, _box, _con=None):
+    """riccati (_box None), riccati_box (_box = (U, lo, hi)) and riccati_al (_con = (Cx, Cu, w, y, shared) on top): the checks and the outputs they share"""
     B, nu = gm.batch, gm.spec.nu; n, dt = 2 * nu, _dtype(gm)
     H = int(A.shape[0]); na = int(nu - act_off if na is None else na)
     A = _want(A, "A", dt, (H, B, n, n)); Bm = _want(Bm, "Bm", dt, (H, B, n, nu))
@@ -74,8 +77,22 @@ def _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, _
         api._chk(api.lib().dojo_riccati_dev(gm.h, H, C.byref(r), api.torch_stream(dev)))
         return (K, kff, dV, fail, Vx, Vxx) if value else (K, kff, dV, fail)
     U, lo, hi = _box
-    U = _want(U, "U", dt, (H, B, nu)); lo, hi = _limits(gm, lo, hi, na, dev)
     active = torch.empty((H, B), dtype=torch.int64, device=dev); qp_iters = torch.empty((H, B), dtype=torch.int32, device=dev)
+    if _con is not None:
+        Cx, Cu, w, y, shared = _con
+        nc = 0 if w is None else int(w.shape[-1])
+        Cx = _want(Cx, "Cx", dt, (nc, n) if shared else (H + 1, B, nc, n)); Cu = _want(Cu, "Cu", dt, (nc, na) if shared else (H, B, nc, na))
+        w = _want(w, "w", dt, (H + 1, B, nc)); y = _want(y, "y", dt, (H + 1, B, nc))
+        limited = lo is not None or hi is not None
+        U = _want(U, "U", dt, (H, B, nu))
+        if limited:
+            lo, hi = _limits(gm, lo, hi, na, dev)
+        lim = api.DojoControlLimits(api.addr(lo), api.addr(hi))
+        con = api.DojoStageConstraints(api.addr(Cx), api.addr(Cu), api.addr(w), api.addr(y), nc, int(bool(shared)))
+        api._chk(api.lib().dojo_riccati_al_dev(gm.h, H, C.byref(r), C.byref(lim) if limited else None, api.addr(U), C.byref(con), api.addr(active), api.addr(qp_iters),
+                                               api.torch_stream(dev)))
+        return (K, kff, dV, fail, active, qp_iters, Vx, Vxx) if value else (K, kff, dV, fail, active, qp_iters)
+    U = _want(U, "U", dt, (H, B, nu)); lo, hi = _limits(gm, lo, hi, na, dev)
     lim = api.DojoControlLimits(api.addr(lo), api.addr(hi))
     api._chk(api.lib().dojo_riccati_box_dev(gm.h, H, C.byref(r), C.byref(lim), api.addr(U), api.addr(active), api.addr(qp_iters), api.torch_stream(dev)))
     return (K, kff, dV, fail, active, qp_iters, Vx, Vxx) if value else (K, kff, dV, fail, active, qp_iters)
@@ -92,6 +109,15 @@ def riccati_box(gm, A, Bm, lx, lu, lxx, luu, U, lo, hi, lux=None, mu=None, statu
     the controls the pass is taken around; lo, hi: [na] or [B,na] (a number or None also pass) -> K, kff, dV, fail (-(1 + k): the QP of step k failed or its box is
     empty), active [H,B] int64 (bit i: input act_off + i clamped), qp_iters [H,B] int32 (and Vx, Vxx with value).  One launch."""
     return _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, (U, lo, hi))
+
+
+def riccati_al(gm, A, Bm, lx, lu, lxx, luu, Cx, w, y, Cu=None, shared=False, U=None, lo=None, hi=None, lux=None, mu=None, status=None, act_off=0, na=None,
+               value=False):
+    """dojo_riccati_al_dev on device tensors: `riccati_box` with the augmented-Lagrangian terms of nc linearized constraint rows per stage added inside the
+    kernel -- G' diag(w) G to the step's Hessian, G' y to its gradient, G = [Cx Cu]; they never exist in memory.  Cx [H+1,B,nc,n], Cu [H,B,nc,na] or None
+    (zeros), [nc,n] and [nc,na] with shared; w, y [H+1,B,nc]: the weight of a row (0: inactive or absent) and its multiplier estimate lambda + w c.  A row with
+    w = y = 0 is not read.  lo, hi None: no control limits (U may then be None).  -> K, kff, dV, fail, active, qp_iters (and Vx, Vxx with value).  One launch."""
+    return _riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na, value, (U, lo, hi), (Cx, Cu, w, y, shared))
 
 
 class QuadraticCost:
@@ -241,8 +267,10 @@ def solve_limited(gm, x0, U0, cost, iters, lo, hi, act_off=0, na=None, c1=1e-4, 
     return _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu_grow, mu_shrink, fused, (lo, hi))
 
 
-def _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu_grow, mu_shrink, fused, limits):
-    """the loop of solve (limits None) and solve_limited (limits = (lo, hi))"""
+def _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu_grow, mu_shrink, fused, limits, al=None):
+    """the loop of solve (limits None) and solve_limited (limits = (lo, hi)).  al (solve_constrained's _AugmentedLagrangian, None for the two others, whose
+    statements are then exactly what they were): the backward pass is riccati_al over al.terms, and the merit M = J + al.penalty takes J's place in the
+    acceptance test; the regularisation starts from al.mu and is left there"""
     B, nu = gm.batch, gm.spec.nu; dt = _dtype(gm)
     na = int(nu - act_off if na is None else na)
     dev = x0.device
@@ -254,13 +282,24 @@ def _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu
         lo, hi = _limits(gm, limits[0], limits[1], na, dev)
         U[:, :, act] = torch.clamp(U[:, :, act], lo, hi)
         hist["active"] = []
+    if al is not None:
+        hist["M"] = []
+        if al.mu is not None:
+            mu = al.mu
     if int(iters) < 1:
         raise ValueError("iters must be >= 1")
     for _ in range(int(iters)):
         X, A, Bm, status = (linearize_rollout_fused if fused else linearize_rollout)(gm, x0, U)
         J = cost.value(X, U[:, :, act])
         lx, lu, lxx, luu, lux = cost.quadratize(X, U[:, :, act])
-        if limits is None:
+        if al is not None:
+            Cx, Cu, shared, w, y, pen = al.terms(X, U[:, :, act])
+            M = M_acc = J + pen
+            K, kff, dV, fail, active, _ = riccati_al(gm, A, Bm, lx, lu, lxx, luu, Cx, w, y, Cu, shared, U if limits is not None else None,
+                                                     lo if limits is not None else None, hi if limits is not None else None, lux, mu, status, act_off, na)
+            if limits is not None:
+                hist["active"].append(active)
+        elif limits is None:
             K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na)
         else:
             K, kff, dV, fail, active, _ = riccati_box(gm, A, Bm, lx, lu, lxx, luu, U, lo, hi, lux, mu, status, act_off, na)
@@ -275,7 +314,12 @@ def _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu
             else:
                 Xa, Ua, sa = (forward_pass_fused_box if fused else forward_pass_box)(gm, X, U, K, kff, float(a), act_off, na, lo, hi)
             Ja = cost.value(Xa, Ua[:, :, act])
-            now = ~accepted & solved & (sa == 0).all(0) & (Ja <= J + c1 * (a * dV[:, 0] + a * a * dV[:, 1]))
+            if al is None:
+                now = ~accepted & solved & (sa == 0).all(0) & (Ja <= J + c1 * (a * dV[:, 0] + a * a * dV[:, 1]))
+            else:
+                Ma = Ja + al.penalty(Xa, Ua[:, :, act])
+                now = ~accepted & solved & (sa == 0).all(0) & (Ma <= M + c1 * (a * dV[:, 0] + a * a * dV[:, 1]))
+                M_acc = torch.where(now, Ma, M_acc)
             U_new = torch.where(now[None, :, None], Ua, U_new); a_acc = torch.where(now, torch.full_like(a_acc, a), a_acc)
             accepted |= now
             if bool((accepted | ~solved).all()):
@@ -284,6 +328,160 @@ def _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu
         shrunk = mu * mu_shrink
         mu = torch.where(accepted, torch.where(shrunk < mu_min, torch.zeros_like(mu), shrunk), torch.clamp(mu * mu_grow, min=mu_min))
         U = U_new
+        if al is not None:
+            hist["M"].append(torch.stack([M, M_acc]))
+    if al is not None:
+        al.mu = mu
     X = replay(gm, x0, U)
     hist["J"].append(cost.value(X, U[:, :, act]))
     return {"X": X, "U": U, **{k: torch.stack(v) for k, v in hist.items()}}
+
+
+# ---- constraints other than control limits: the augmented-Lagrangian loop of IterativeLQR around the iLQR above (include/dojo_hip_constraints.h) ----
+class GoalConstraint:
+    """the terminal equality x_H[rows] = x_goal[rows] (rows: indices into the n state coordinates, default all): c = x_H[rows] - x_goal[rows] at stage H, absent at
+    the stages before.  x_goal [n] or [B,n], a device tensor in the handle's dtype.  The Jacobian is shared by the stages and the batch."""
+
+    def __init__(self, x_goal, rows=None):
+        n = int(x_goal.shape[-1])
+        self.rows = torch.arange(n, device=x_goal.device) if rows is None else torch.as_tensor(rows, dtype=torch.long, device=x_goal.device)
+        self.goal, self.n, self.nc = x_goal, n, int(self.rows.numel())
+        self.ineq = torch.zeros(self.nc, dtype=torch.bool, device=x_goal.device)
+        self._Cx = torch.zeros((self.nc, n), dtype=x_goal.dtype, device=x_goal.device)
+        self._Cx[torch.arange(self.nc, device=x_goal.device), self.rows] = 1.0
+
+    def present(self, H):
+        p = torch.zeros((H + 1, self.nc), dtype=torch.bool, device=self.goal.device); p[H] = True
+        return p
+
+    def evaluate(self, X, U_act):
+        return (X - self.goal)[..., self.rows]
+
+    def jacobians(self, X, U_act):
+        return self._Cx, None, True
+
+
+class StateBounds:
+    """lo <= x_k[rows] <= hi at the stages k = 1 .. H as 2 len(rows) inequalities c <= 0: c = [x[rows] - hi; lo - x[rows]] (rows: indices into the n state
+    coordinates, default all).  lo, hi: numbers or [len(rows)] (+-inf: no bound on that side; its row is absent).  The Jacobian is shared by the stages and the batch."""
+
+    def __init__(self, lo, hi, rows=None):
+        self._lo, self._hi, self._rows, self._built = lo, hi, rows, None
+        r = len(rows) if rows is not None else max(int(torch.as_tensor(v).numel()) for v in (lo, hi))
+        if rows is None and r == 1:
+            raise ValueError("StateBounds: with scalar bounds give the rows they apply to")
+        self.nc = 2 * r
+
+    def _build(self, X):
+        """the tensors, on X's device in X's dtype, at the first use"""
+        if self._built is None or self._built != (X.dtype, X.device):
+            dt, dev, r, n = X.dtype, X.device, self.nc // 2, int(X.shape[-1])
+            self.rows = torch.arange(n, device=dev) if self._rows is None else torch.as_tensor(self._rows, dtype=torch.long, device=dev)
+            self.lo = torch.as_tensor(self._lo, dtype=dt, device=dev).expand(r).contiguous(); self.hi = torch.as_tensor(self._hi, dtype=dt, device=dev).expand(r).contiguous()
+            self.Cx = torch.zeros((self.nc, n), dtype=dt, device=dev)
+            i = torch.arange(r, device=dev)
+            self.Cx[i, self.rows] = 1.0; self.Cx[r + i, self.rows] = -1.0
+            self._built = (dt, dev)
+
+    @property
+    def ineq(self):
+        return torch.ones(self.nc, dtype=torch.bool)
+
+    def present(self, H):
+        finite = torch.isfinite(torch.cat([torch.as_tensor(self._hi, dtype=torch.float64).expand(self.nc // 2), torch.as_tensor(self._lo, dtype=torch.float64).expand(self.nc // 2)]).cpu())
+        p = finite[None].repeat(H + 1, 1); p[0] = False
+        return p
+
+    def evaluate(self, X, U_act):
+        self._build(X)
+        x = X[..., self.rows]
+        c = torch.cat([x - self.hi, self.lo - x], -1)
+        return torch.where(torch.isfinite(c), c, torch.full_like(c, -1.0))         # (an infinite bound: its row is absent, any finite value does)
+
+    def jacobians(self, X, U_act):
+        self._build(X)
+        return self.Cx, None, True
+
+
+class _AugmentedLagrangian:
+    """what _solve needs of the outer loop's state: the multipliers lam [H+1,B,nc], the penalty rho [B], the regularisation carried across the outer iterations"""
+
+    def __init__(self, con, H, B, rho0, dt, dev):
+        present = con.present(H) if callable(con.present) else con.present           # [H+1,nc] bool: a tensor, or a function of the horizon
+        self.con, self.present, self.ineq = con, torch.as_tensor(present, device=dev)[:, None, :], torch.as_tensor(con.ineq, device=dev)[None, None, :]
+        self.lam = torch.zeros((H + 1, B, con.nc), dtype=dt, device=dev); self.rho = torch.full((B,), float(rho0), dtype=dt, device=dev)
+        self.mu = None
+
+    def weights(self, c):
+        """a = present & (~ineq | c >= 0 | lam > 0), w = rho a, y = lam + w c"""
+        a = self.present & (~self.ineq | (c >= 0) | (self.lam > 0))
+        w = self.rho[None, :, None] * a
+        return w, self.lam + w * c
+
+    def penalty(self, X, U_act):
+        """sum lam c + 1/2 sum w c^2 -> [B]"""
+        c = self.con.evaluate(X, U_act) * self.present
+        w, _ = self.weights(c)
+        return (self.lam * c).sum((0, 2)) + 0.5 * (w * c * c).sum((0, 2))
+
+    def terms(self, X, U_act):
+        c = self.con.evaluate(X, U_act) * self.present
+        w, y = self.weights(c)
+        Cx, Cu, shared = self.con.jacobians(X, U_act)
+        return Cx, Cu, shared, w.contiguous(), y.contiguous(), (self.lam * c).sum((0, 2)) + 0.5 * (w * c * c).sum((0, 2))
+
+    def violation(self, X, U_act):
+        c = self.con.evaluate(X, U_act)
+        v = torch.where(self.ineq, torch.clamp(c, min=0.0), c.abs()) * self.present
+        return v.amax((0, 2)), c
+
+    def update(self, c, rho_scale, rho_max):
+        """lam <- lam + rho c (equalities), max(0, lam + rho c) (inequalities) on the present rows; rho <- min(rho_scale rho, rho_max)"""
+        new = self.lam + self.rho[None, :, None] * c
+        self.lam = torch.where(self.present, torch.where(self.ineq, torch.clamp(new, min=0.0), new), self.lam)
+        self.rho = torch.clamp(self.rho * rho_scale, max=rho_max)
+
+
+def solve_constrained(gm, x0, U0, cost, constraints, iters, outer, lo=None, hi=None, rho0=1.0, rho_scale=10.0, rho_max=1e8, act_off=0, na=None, c1=1e-4,
+                      alphas=(1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625, 0.0078125), mu_init=0.0, mu_min=1e-6, mu_grow=10.0, mu_shrink=0.1, fused=False):
+    """iLQR under constraints c(x, u) = 0 / <= 0 by IterativeLQR's augmented-Lagrangian loop.  `constraints`: an object with nc, ineq [nc] bool (the convention is
+    c <= 0), present [H+1,nc] bool (or a function of H that gives it), evaluate(X, U_act) -> c [H+1,B,nc] and jacobians(X, U_act) -> (Cx, Cu or None, shared) in riccati_al's layouts
+    (GoalConstraint, StateBounds).  lo, hi: control limits as in solve_limited -- they go to the box QP of the backward pass and the clamp of the forward pass, not
+    into the augmented Lagrangian.  With lam = 0 and rho [B] = rho0 at the start, each of the `outer` iterations runs
+      * `iters` iterations of `solve` with the merit  M = J + sum lam c + 1/2 sum w c^2  in J's place in the acceptance test and riccati_al as the backward pass,
+        where, from the current c, before every backward pass and every evaluation of M:  a = present & (~ineq | c >= 0 | lam > 0),  w = rho a,  y = lam + w c
+        (the kernel's dV is the model of exactly this M);
+      * then, on the present rows:  lam <- lam + rho c  (equalities),  lam <- max(0, lam + rho c)  (inequalities);  rho <- min(rho_scale rho, rho_max).
+    The regularisation mu carries over from one outer iteration to the next.
+    -> solve's dict over all outer x iters iterations (J [outer iters + 1,B] is the cost alone; M [outer iters,2,B]: the merit at the start of an iteration and behind
+    its accepted step), viol [outer+1,B] (the largest |c| of an equality, max(c, 0) of an inequality over the present rows, before the first and behind every outer
+    iteration), lam [H+1,B,nc], rho [B]."""
+    B, nu = gm.batch, gm.spec.nu; dt = _dtype(gm)
+    na = int(nu - act_off if na is None else na)
+    H, dev = int(U0.shape[0]), x0.device
+    act = slice(act_off, act_off + na)
+    if int(outer) < 1:
+        raise ValueError("outer must be >= 1")
+    limits = None if lo is None and hi is None else (lo, hi)
+    al = _AugmentedLagrangian(constraints, H, B, rho0, dt, dev)
+    U = U0.clone()
+    if limits is not None:
+        l, h = _limits(gm, lo, hi, na, dev)
+        U[:, :, act] = torch.clamp(U[:, :, act], l, h)
+    viol = [al.violation(replay(gm, x0, U), U[:, :, act])[0]]
+    parts = []
+    for _ in range(int(outer)):
+        res = _solve(gm, x0, U, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu_grow, mu_shrink, fused, limits, al)
+        U = res["U"]
+        v, c = al.violation(res["X"], U[:, :, act])
+        viol.append(v)
+        al.update(c * al.present, rho_scale, rho_max)
+        parts.append(res)
+    out = {"X": parts[-1]["X"], "U": U}
+    for k in parts[0]:
+        if k == "J":
+            out[k] = torch.cat([p[k][:-1] for p in parts] + [parts[-1][k][-1:]])
+        elif k not in ("X", "U"):
+            out[k] = torch.cat([p[k] for p in parts])
+    out.update(viol=torch.stack(viol), lam=al.lam, rho=al.rho)
+    return out

@@ -345,6 +345,42 @@ function riccati_box(bm::BatchedMechanism{T}, A::Array{T,4}, Bm::Array{T,4}, lx:
     return K, kff, dV, fail, active, qp_iters, Vx, Vxx
 end
 
+"mirror of `DojoStageConstraints` (include/dojo_hip_constraints.h): four pointers, two Int32"
+struct DojoStageConstraints
+    Cx::Ptr{Cvoid}; Cu::Ptr{Cvoid}; w::Ptr{Cvoid}; y::Ptr{Cvoid}
+    nc::Int32; shared::Int32
+end
+
+"""
+`riccati_box` with the augmented-Lagrangian terms of nc linearized constraint rows per stage added to the step's model inside the kernel
+(include/dojo_hip_constraints.h): dojo_riccati_al.  With G = [Cx Cu] the stage gains G' diag(w) G in its Hessian and G' y in its gradient.
+Cx[n, nc, B, H + 1] and Cu[na, nc, B, H] (row i of the Jacobian is column i: the C layout [H][B][nc][n] read column-major), or Cx[n, nc], Cu[na, nc] with
+`shared`; Cu may be `nothing` (zeros).  w[nc, B, H + 1]: the weight of a row (0: inactive or absent), y[nc, B, H + 1]: its multiplier estimate lambda + w c.
+A row with w = y = 0 is not read.  lo, hi `nothing`: no control limits, and U may be `nothing` too.  Other arguments and outputs as in `riccati_box`.
+"""
+function riccati_al(bm::BatchedMechanism{T}, A::Array{T,4}, Bm::Array{T,4}, lx::Array{T,3}, lu::Array{T,3}, lxx::Array{T,4}, luu::Array{T,4},
+                    Cx::Array{T}, w::Array{T,3}, y::Array{T,3}; Cu::Union{Nothing,Array{T}}=nothing, shared::Bool=false, U::Union{Nothing,Array{T,3}}=nothing,
+                    lo::Union{Nothing,Matrix{T}}=nothing, hi::Union{Nothing,Matrix{T}}=nothing, lux::Union{Nothing,Array{T,4}}=nothing,
+                    mu::Union{Nothing,Vector{T}}=nothing, status::Union{Nothing,Matrix{Int32}}=nothing, act_off::Integer=0) where T
+    H = size(A, 4); n = 2 * bm.nu; na = size(lu, 1); nc = size(w, 1)
+    K = Array{T}(undef, n, na, bm.batch, H); kff = Array{T}(undef, na, bm.batch, H); fail = Vector{Int32}(undef, bm.batch)
+    dV = Matrix{T}(undef, 2, bm.batch); Vx = Matrix{T}(undef, n, bm.batch); Vxx = Array{T}(undef, n, n, bm.batch)
+    active = Matrix{Int64}(undef, bm.batch, H); qp_iters = Matrix{Int32}(undef, bm.batch, H)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    limited = lo !== nothing || hi !== nothing
+    GC.@preserve A Bm status lx lu lxx luu lux mu K kff fail dV Vx Vxx U lo hi active qp_iters Cx Cu w y begin
+        r = Ref(DojoRiccati(p(A), p(Bm), p(status), p(lx), p(lu), p(lxx), p(luu), p(lux), p(mu), p(K), p(kff), p(fail), p(dV), p(Vx), p(Vxx), Int32(act_off), Int32(na)))
+        lim = Ref(DojoControlLimits(p(lo), p(hi)))
+        con = Ref(DojoStageConstraints(p(Cx), p(Cu), p(w), p(y), Int32(nc), Int32(shared)))
+        GC.@preserve lim begin
+            limp = limited ? Base.unsafe_convert(Ptr{DojoControlLimits}, lim) : Ptr{DojoControlLimits}(C_NULL)
+            check(@ccall $(fn(:dojo_riccati_al))(bm.handle::Ptr{Cvoid}, Int32(H)::Int32, r::Ptr{DojoRiccati}, limp::Ptr{DojoControlLimits},
+                                                 p(U)::Ptr{Cvoid}, con::Ptr{DojoStageConstraints}, active::Ptr{Int64}, qp_iters::Ptr{Int32})::Cint)
+        end
+    end
+    return K, kff, dV, fail, active, qp_iters, Vx, Vxx
+end
+
 """
 `rollout_minimal` with the driven inputs clamped into [lo, hi] (lo[na, B], hi[na, B]; either may be `nothing`) before they are rounded and stepped:
 dojo_rollout_minimal_box, the forward pass of control-limited iLQR.  Everything else as in `rollout_minimal`.

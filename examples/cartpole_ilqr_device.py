@@ -18,7 +18,12 @@ With --limit F the swing-up runs under |u| <= F (ilqr.solve_limited, control-lim
 dojo_riccati_box_dev (a box QP per step, the gain rows of clamped inputs zero), the forward pass clamps; the largest |u| and the share of steps at the bound are
 printed.
 
-    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations] [--fused] [--limit F]          # needs a GPU: libdojo_hip has no CPU fallback
+With --goal the swing-up ends AT the upright state instead of near it (ilqr.solve_constrained, IterativeLQR's augmented-Lagrangian loop:
+include/dojo_hip_constraints.h): a terminal goal constraint x_H = 0 with a modest terminal cost (Qf = Q) in place of the large one, 4 outer iterations of
+[iterations] / 4 inner ones each; the backward pass is ONE launch of dojo_riccati_al_dev, which adds the constraint's terms to the step's model inside the kernel.
+The terminal violation max |x_H| is printed per outer iteration next to that of `solve` under the same cost and as many iterations.  --limit F combines with it.
+
+    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations] [--fused] [--limit F] [--goal]     # needs a GPU: libdojo_hip has no CPU fallback
 """
 import os
 import sys
@@ -36,6 +41,7 @@ from dojo_amd import api, ilqr                         # noqa: E402
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     fused = "--fused" in argv; argv = [a for a in argv if a != "--fused"]
+    goal = "--goal" in argv; argv = [a for a in argv if a != "--goal"]
     limit = None
     if "--limit" in argv:
         i = argv.index("--limit"); limit = float(argv[i + 1]); del argv[i:i + 2]
@@ -52,11 +58,15 @@ def main(argv=None):
     U0 = torch.zeros((H, B, spec.nu), dtype=dt, device=dev)
     cost = ilqr.QuadraticCost(Q=torch.diag(torch.tensor([1.0, 0.1, 1.0, 0.1], dtype=dt, device=dev)) * spec.timestep,
                               R=torch.eye(1, dtype=dt, device=dev) * 0.01 * spec.timestep,
-                              Qf=torch.diag(torch.tensor([100.0, 10.0, 100.0, 10.0], dtype=dt, device=dev)),
+                              Qf=torch.diag(torch.tensor([1.0, 0.1, 1.0, 0.1] if goal else [100.0, 10.0, 100.0, 10.0], dtype=dt, device=dev)),
                               x_goal=torch.zeros(4, dtype=dt, device=dev))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    if limit is None:
+    if goal:
+        outer = 4; inner = max(1, iters // outer)
+        lim = {} if limit is None else {"lo": -limit, "hi": limit}
+        res = ilqr.solve_constrained(gm, x0, U0, cost, ilqr.GoalConstraint(torch.zeros(4, dtype=dt, device=dev)), inner, outer, act_off=0, na=1, fused=fused, **lim)
+    elif limit is None:
         res = ilqr.solve(gm, x0, U0, cost, iters, act_off=0, na=1, fused=fused)
     else:
         res = ilqr.solve_limited(gm, x0, U0, cost, iters, -limit, limit, act_off=0, na=1, fused=fused)
@@ -72,8 +82,17 @@ def main(argv=None):
         u = res["U"][:, :, 0].abs()
         print("|u| <= %g: largest |u| %.6g, %.1f %% of the %d environment-steps at the bound" % (limit, float(u.max()), 100.0 * float((u == limit).double().mean()), u.numel()))
         assert float(u.max()) <= limit
+    if goal:
+        free = (ilqr.solve(gm, x0, U0, cost, inner * outer, act_off=0, na=1, fused=fused) if limit is None else
+                ilqr.solve_limited(gm, x0, U0, cost, inner * outer, -limit, limit, act_off=0, na=1, fused=fused))
+        dist = free["X"][-1].abs().amax(1).cpu().numpy()
+        viol = res["viol"].cpu().numpy()
+        for o in range(viol.shape[0]):
+            print("outer %d: terminal violation max |x_H - goal|  min %.3e  median %.3e  max %.3e%s" % (o, viol[o].min(), np.median(viol[o]), viol[o].max(), "   (the start)" if o == 0 else ""))
+        print("without the constraint, same cost, %d iterations:    min %.3e  median %.3e  max %.3e" % (inner * outer, dist.min(), np.median(dist), dist.max()))
+        print("rho %.1e, largest |lambda| %.3e" % (float(res["rho"].max()), float(res["lam"].abs().max())))
     print("%d environments x %d steps x %d iterations in %.2f s%s" % (B, H, iters, el, " (fused rollouts)" if fused else ""))
-    assert (J[-1] <= J[0]).all()
+    assert goal or (J[-1] <= J[0]).all()                # (under a goal constraint the cost alone may rise: the merit is what falls)
     gm.close()
     return res
 
