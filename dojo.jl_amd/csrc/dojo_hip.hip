@@ -19,7 +19,9 @@
 #include "dojo_tangent.hpp"
 #include "dojo_riccati.hpp"
 #include "dojo_tracking.hpp"
+#include "dojo_linesearch.hpp"
 #include "../../include/dojo_hip_constraints.h"      // (includes dojo_hip_limits.h, which includes dojo_hip_trajopt.h)
+#include "../../include/dojo_hip_linesearch.h"       // (the fifth: the fan rollout and the selection kernel of a side-by-side line search)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -1048,17 +1050,32 @@ int launch_mlp(const DojoSim* s, const DojoMlpPolicy& p, const dj::mlp::Shape& s
 // (dojo_tracking.hpp), the re-projection by min2max_kernel: the two maps are the kernels of dojo_step_minimal_dev, which index environments from 0 and are given
 // the span's slice of every array.  The observation of the final state (u = null) is the first of the three alone.
 template <class TIO>
-int launch_tracking(const DojoSim* s, const DojoTracking& t, const DojoControlLimits* lim, int k, const void* z, const void* uff, void* x, void* u, void* zproj, const Span& sp) {
-    const size_t B = s->B, Nb = s->M.Nb, nu = s->M.nu, n = 2 * nu, kB = (size_t)k * B, e0 = sp.env0;
+int launch_tracking(const DojoSim* s, const DojoTracking& t, const DojoControlLimits* lim, int fan_P, int k, const void* z, const void* uff, void* x, void* u, void* zproj, const Span& sp) {
+    // fan_P > 0 (dojo_rollout_minimal_fan_dev): the reference members hold P = fan_P rows per step, not B, and x0 is [P][n]
+    const size_t B = s->B, Nb = s->M.Nb, nu = s->M.nu, n = 2 * nu, kB = (size_t)k * (fan_P ? (size_t)fan_P : B), e0 = sp.env0;
     TIO* const xs = (TIO*)x + e0 * n;
-    if (k == 0) HIPCHK(hipMemcpyAsync(xs, (const TIO*)z + e0 * n, (size_t)sp.nenv * n * sizeof(TIO), hipMemcpyDeviceToDevice, sp.stream));
+    if (k == 0 && fan_P) {
+        // X[0][tr P + p] = x0[p]: the span's environments piece by piece, a piece ending where a trial ends (a span may begin and end inside a trial)
+        for (size_t e = e0, end = e0 + (size_t)sp.nenv; e < end;) {
+            const size_t p = e % (size_t)fan_P, cnt = std::min(end - e, (size_t)fan_P - p);
+            HIPCHK(hipMemcpyAsync((TIO*)x + e * n, (const TIO*)z + p * n, cnt * n * sizeof(TIO), hipMemcpyDeviceToDevice, sp.stream));
+            e += cnt;
+        }
+    }
+    else if (k == 0) HIPCHK(hipMemcpyAsync(xs, (const TIO*)z + e0 * n, (size_t)sp.nenv * n * sizeof(TIO), hipMemcpyDeviceToDevice, sp.stream));
     else TRY(launch_items(dj::ckern::max2min_kernel<TIO>, (long long)sp.nenv * Nb, 256, sp.stream, node_table(s), (int)Nb, (int)nu, s->M.dt, sp.nenv, (const TIO*)z + e0 * 13 * Nb, xs, (int)n));
     if (!u) return DOJO_OK;
     auto row = [&](const void* p, size_t per) { return p ? (const TIO*)p + kB * per : nullptr; };      // step k of an input that is given
-    const dj::tracking::Args<TIO> A{(const TIO*)x, (const TIO*)uff, row(t.Xbar, n), row(t.K, (size_t)t.na * n), row(t.kff, (size_t)t.na), (const TIO*)t.alpha, (TIO*)u,
+    // (the fan's Ubar has P rows per step as well: rollout_core, which strides by B, is not given it -- uff is null then)
+    const dj::tracking::Args<TIO> A{(const TIO*)x, fan_P ? row(t.Ubar, nu) : (const TIO*)uff, row(t.Xbar, n), row(t.K, (size_t)t.na * n), row(t.kff, (size_t)t.na), (const TIO*)t.alpha, (TIO*)u,
                                     (int)sp.env0, sp.nenv, (int)nu, t.act_off, t.na};
     const dim3 grid((unsigned)((sp.nenv + dj::policy::ENVS - 1) / dj::policy::ENVS));
-    if (lim) {       // (dojo_rollout_minimal_box_dev)
+    if (fan_P) {     // (dojo_rollout_minimal_fan_dev; lim null: no limits)
+        dj::tracking::FanArgs<TIO> fa; static_cast<dj::tracking::Args<TIO>&>(fa) = A;
+        fa.lo = lim ? (const TIO*)lim->lo : nullptr; fa.hi = lim ? (const TIO*)lim->hi : nullptr; fa.P = fan_P;
+        hipLaunchKernelGGL((dj::tracking::rollout_tracking_kernel<TIO, dj::tracking::FanArgs<TIO>>), grid, dim3(dj::policy::THREADS), 0, sp.stream, fa);
+    }
+    else if (lim) {  // (dojo_rollout_minimal_box_dev)
         dj::tracking::BoxArgs<TIO> bx; static_cast<dj::tracking::Args<TIO>&>(bx) = A; bx.lo = (const TIO*)lim->lo; bx.hi = (const TIO*)lim->hi;
         hipLaunchKernelGGL((dj::tracking::rollout_tracking_kernel<TIO, dj::tracking::BoxArgs<TIO>>), grid, dim3(dj::policy::THREADS), 0, sp.stream, bx);
     }
@@ -1074,6 +1091,7 @@ struct Controller {
     const DojoMlpPolicy* mlp = nullptr;
     const DojoTracking* tracking = nullptr;
     const DojoControlLimits* limits = nullptr;     // of the tracking controller (dojo_rollout_minimal_box_dev) or null
+    int fan_P = 0;                                 // of the tracking controller: > 0 = the fan of dojo_rollout_minimal_fan_dev over P problems (include/dojo_hip_linesearch.h)
     dj::mlp::Shape shape{};
     double* ACT = nullptr;              // [H][B][nh] or null
     bool contact_forces() const { return tracking ? false : affine ? affine->contact_forces != 0 : mlp->contact_forces != 0; }
@@ -1081,7 +1099,7 @@ struct Controller {
 };
 // the controls of step k (u != null) or the observation of the final state (u = null, k = H).  zproj: the tracking controller's re-projected state (the others make none)
 int launch_controller(const DojoSim* s, const Controller& c, int k, const void* z, const void* csg, const void* uff, void* obs, void* u, const Span& sp, void* zproj = nullptr) {
-    if (c.tracking) return by_dtype(s, [&](auto t) { return launch_tracking<decltype(t)>(s, *c.tracking, c.limits, k, z, uff, obs, u, zproj, sp); });
+    if (c.tracking) return by_dtype(s, [&](auto t) { return launch_tracking<decltype(t)>(s, *c.tracking, c.limits, c.fan_P, k, z, uff, obs, u, zproj, sp); });
     if (c.affine) return launch_policy_any(s, *c.affine, z, csg, uff, obs, u, sp);
     double* const act = (c.ACT && u) ? c.ACT + (size_t)k * s->B * c.shape.nh : nullptr;
     return by_dtype(s, [&](auto t) { return launch_mlp<decltype(t)>(s, *c.mlp, c.shape, z, csg, uff, obs, u, act, sp); });
@@ -1097,6 +1115,20 @@ int launch_mlp_adjoint(const DojoSim* s, const DojoMlpPolicy& p, const dj::mlp::
     HIPCHK(hipGetLastError());
     // at n_layers = 1 theta is [W | bias], the order of the affine sweep's accumulators: every entry goes to the one output
     return (!p.per_env && a.gtheta) ? launch_policy_reduce<TIO>(s, ws, (int)sh.P, (int)sh.P, a.gtheta, nullptr, st) : DOJO_OK;
+}
+
+// dojo_linesearch_select_dev: one workgroup per problem (dojo_linesearch.hpp)
+template <class TIO>
+int launch_select(const DojoSim* s, int H, int T, const DojoQuadraticCost* cost, const DojoLineSearch& l, hipStream_t st) {
+    dj::linesearch::Args<TIO> A{};
+    A.X = (const TIO*)l.X; A.U = (const TIO*)l.U; A.status = l.status; A.alpha = (const TIO*)l.alpha; A.dV = (const TIO*)l.dV; A.ok = l.ok;
+    A.Xcur = (const TIO*)l.Xcur; A.Ucur = (const TIO*)l.Ucur; A.J0 = l.J0; A.J_trial = l.J_trial; A.J_cur = l.J_cur; A.J_acc = l.J_acc;
+    A.choice = l.choice; A.alpha_acc = (TIO*)l.alpha_acc; A.X_new = (TIO*)l.X_new; A.U_new = (TIO*)l.U_new;
+    if (cost) { A.Q = (const TIO*)cost->Q; A.R = (const TIO*)cost->R; A.Qf = (const TIO*)cost->Qf; A.goal = (const TIO*)cost->goal; A.goal_per_problem = cost->goal_per_problem ? 1 : 0; }
+    A.c1 = l.c1; A.H = H; A.T = T; A.P = (int)(s->B / (size_t)T); A.nu = (int)s->M.nu; A.act_off = l.act_off; A.na = l.na;
+    hipLaunchKernelGGL((dj::linesearch::linesearch_select_kernel<TIO>), dim3((unsigned)A.P), dim3(dj::linesearch::THREADS), 0, st, A);
+    HIPCHK(hipGetLastError());
+    return DOJO_OK;
 }
 
 } // namespace
@@ -1968,6 +2000,97 @@ static int rollout_minimal_host(DojoHandle s, int32_t H, const DojoTracking* t, 
 }
 int dojo_rollout_minimal(DojoHandle s, int32_t H, const DojoTracking* t) { return rollout_minimal_host(s, H, t, false, nullptr, "dojo_rollout_minimal"); }
 int dojo_rollout_minimal_box(DojoHandle s, int32_t H, const DojoTracking* t, const DojoControlLimits* lim) { return rollout_minimal_host(s, H, t, true, lim, "dojo_rollout_minimal_box"); }
+
+// ---- the line search side by side (include/dojo_hip_linesearch.h): T trials of P problems in one rollout, and the selection kernel (dojo_linesearch.hpp) ----
+// what the fan refuses on top of refuse_tracking; *P: the problems
+static int refuse_fan(DojoHandle s, int32_t H, int32_t T, const DojoTracking* t, const char* who) {
+    TRY(refuse_tracking(s, H, t, who));
+    const std::string w_ = std::string(who) + ": ";
+    if (T < 1) { g_err = w_ + "T must be >= 1"; return DOJO_ERR_INVALID; }
+    if (s->B % (size_t)T != 0) { g_err = w_ + "the batch (" + std::to_string(s->B) + ") must be T (" + std::to_string(T) + ") trials of P problems: B mod T != 0"; return DOJO_ERR_INVALID; }
+    if (t->A || t->Bm) { g_err = w_ + "A and Bm must be NULL (the fan does not record Jacobians)"; return DOJO_ERR_INVALID; }
+    return DOJO_OK;
+}
+int dojo_rollout_minimal_fan_dev(DojoHandle s, int32_t H, int32_t T, const DojoTracking* t, const DojoControlLimits* lim, void* stream) {
+    Enter enter_(s);
+    TRY(refuse_fan(s, H, T, t, "dojo_rollout_minimal_fan_dev"));
+    const DojoTracking tr = *t;      // (the caller's structs are read during the call only)
+    const DojoControlLimits lm = lim ? *lim : DojoControlLimits{nullptr, nullptr};
+    Controller c; c.tracking = &tr; c.limits = lim ? &lm : nullptr; c.fan_P = (int)(s->B / (size_t)T);
+    // (no io.U: rollout_core strides the feed-forward controls by B, the fan's Ubar has P rows per step -- launch_tracking takes them from the record)
+    RolloutIO io; io.z0 = tr.x0; io.status = tr.status; io.controller = &c; io.OBS = tr.X; io.U_out = tr.U_out;
+    return rollout_core(s, H, io, stream);
+}
+int dojo_rollout_minimal_fan(DojoHandle s, int32_t H, int32_t T, const DojoTracking* t, const DojoControlLimits* lim) {
+    Enter enter_(s);
+    const char* who = "dojo_rollout_minimal_fan";
+    TRY(refuse_fan(s, H, T, t, who));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, P = B / (size_t)T, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)t->na, HB = (size_t)H * B, HP = (size_t)H * P;
+    if (lim) TRY(refuse_limit_values(s, lim, P * m, who));
+    Staging st;
+    const auto &dx0 = st.input(P * n * w, t->x0), &dUb = st.input(HP * nu * w, t->Ubar), &dXb = st.input((HP + P) * n * w, t->Xbar);
+    const auto &dK = st.input(HP * m * n * w, t->K), &dk = st.input(HP * m * w, t->kff), &da = st.input(B * w, t->alpha);
+    const auto &dlo = st.input(P * m * w, lim ? lim->lo : nullptr), &dhi = st.input(P * m * w, lim ? lim->hi : nullptr);
+    const auto &dX = st.output((HB + B) * n * w, t->X), &dU = st.output(HB * nu * w, t->U_out), &dS = st.output(HB * sizeof(int32_t), t->status);
+    TRY(st.allocate());
+    DojoTracking d = *t;
+    d.x0 = dx0.p; d.Ubar = dUb.p; d.Xbar = dXb.p; d.K = dK.p; d.kff = dk.p; d.alpha = da.p; d.X = dX.p; d.U_out = dU.p; d.status = (int32_t*)dS.p;
+    const DojoControlLimits dlim{dlo.p, dhi.p};
+    TRY(dojo_rollout_minimal_fan_dev(s, H, T, &d, lim ? &dlim : nullptr, nullptr));
+    return st.finish();      // (the handle keeps the last step's states itself)
+}
+
+// what both selection entries refuse, before anything is allocated or launched
+static int refuse_select(DojoHandle s, int32_t H, int32_t T, const DojoQuadraticCost* cost, const DojoLineSearch* ls, const char* who) {
+    const std::string w_ = std::string(who) + ": ";
+    if (!s || !ls) { g_err = w_ + "bad argument (the handle and the DojoLineSearch record are required)"; return DOJO_ERR_INVALID; }
+    if (H < 1) { g_err = w_ + "H must be >= 1"; return DOJO_ERR_INVALID; }
+    if (T < 1 || T > dj::linesearch::MAX_T) { g_err = w_ + "T must be 1 .. " + std::to_string(dj::linesearch::MAX_T) + " (the kernel keeps the trials' costs in LDS)"; return DOJO_ERR_INVALID; }
+    if (s->B % (size_t)T != 0) { g_err = w_ + "the batch (" + std::to_string(s->B) + ") must be T (" + std::to_string(T) + ") trials of P problems: B mod T != 0"; return DOJO_ERR_INVALID; }
+    if (!ls->X || !ls->U || !ls->alpha || !ls->dV || !ls->Xcur || !ls->Ucur || !ls->choice || !ls->alpha_acc || !ls->J_acc) {
+        g_err = w_ + "X, U, alpha, dV, Xcur, Ucur, choice, alpha_acc and J_acc must not be NULL"; return DOJO_ERR_INVALID;
+    }
+    if (!ls->J_trial) { g_err = w_ + "J_trial must not be NULL (an output with a cost, an input without)"; return DOJO_ERR_INVALID; }
+    if (!cost && !ls->J0) { g_err = w_ + "J0 must not be NULL without a cost"; return DOJO_ERR_INVALID; }
+    if (cost && (!cost->Q || !cost->R || !cost->Qf || !cost->goal)) { g_err = w_ + "Q, R, Qf and goal of the cost must not be NULL"; return DOJO_ERR_INVALID; }
+    if (s->M.nu == 0) { g_err = w_ + "the mechanism has no inputs"; return DOJO_ERR_INVALID; }
+    if (ls->na < 1 || ls->act_off < 0 || (long long)ls->act_off + ls->na > (long long)s->M.nu) { g_err = w_ + "the cost must cover inputs act_off .. act_off + na - 1 inside 0 .. nu - 1, na >= 1"; return DOJO_ERR_INVALID; }
+    if (!std::isfinite(ls->c1)) { g_err = w_ + "c1 must be finite"; return DOJO_ERR_INVALID; }
+    return DOJO_OK;
+}
+int dojo_linesearch_select_dev(DojoHandle s, int32_t H, int32_t T, const DojoQuadraticCost* cost, const DojoLineSearch* ls, void* stream) {
+    Enter enter_(s);
+    TRY(refuse_select(s, H, T, cost, ls, "dojo_linesearch_select_dev"));
+    HIPCHK(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    TRY(join_groups(s, st));                  // (asynchronous steps still in flight may be writing the trials)
+    return by_dtype(s, [&](auto t) { return launch_select<decltype(t)>(s, H, T, cost, *ls, st); });
+}
+int dojo_linesearch_select(DojoHandle s, int32_t H, int32_t T, const DojoQuadraticCost* cost, const DojoLineSearch* ls) {
+    Enter enter_(s);
+    TRY(refuse_select(s, H, T, cost, ls, "dojo_linesearch_select"));
+    HIPCHK(hipSetDevice(s->device));
+    const size_t B = s->B, P = B / (size_t)T, w = s->w, nu = s->M.nu, n = 2 * nu, m = (size_t)ls->na, HB = (size_t)H * B, HP = (size_t)H * P;
+    Staging st;
+    const auto &dX = st.input((HB + B) * n * w, ls->X), &dU = st.input(HB * nu * w, ls->U), &dS = st.input(HB * sizeof(int32_t), ls->status);
+    const auto &da = st.input(B * w, ls->alpha), &ddV = st.input(P * 2 * w, ls->dV), &dok = st.input(P * sizeof(int32_t), ls->ok);
+    const auto &dXc = st.input((HP + P) * n * w, ls->Xcur), &dUc = st.input(HP * nu * w, ls->Ucur), &dJ0 = st.input(P * sizeof(double), ls->J0);
+    const auto &dQ = st.input(n * n * w, cost ? cost->Q : nullptr), &dR = st.input(m * m * w, cost ? cost->R : nullptr), &dQf = st.input(n * n * w, cost ? cost->Qf : nullptr);
+    const auto &dg = st.input((cost && cost->goal_per_problem ? P : 1) * n * w, cost ? cost->goal : nullptr);
+    const auto &dJt = cost ? st.output(B * sizeof(double), ls->J_trial) : st.input(B * sizeof(double), ls->J_trial);
+    const auto &dJc = st.output(P * sizeof(double), ls->J_cur), &dJa = st.output(P * sizeof(double), ls->J_acc);
+    const auto &dch = st.output(P * sizeof(int32_t), ls->choice), &daa = st.output(P * w, ls->alpha_acc);
+    const auto &dXn = st.output((HP + P) * n * w, ls->X_new), &dUn = st.output(HP * nu * w, ls->U_new);
+    TRY(st.allocate());
+    DojoLineSearch d = *ls;
+    d.X = dX.p; d.U = dU.p; d.status = (const int32_t*)dS.p; d.alpha = da.p; d.dV = ddV.p; d.ok = (const int32_t*)dok.p; d.Xcur = dXc.p; d.Ucur = dUc.p;
+    d.J0 = (const double*)dJ0.p; d.J_trial = (double*)dJt.p; d.J_cur = (double*)dJc.p; d.J_acc = (double*)dJa.p; d.choice = (int32_t*)dch.p; d.alpha_acc = daa.p;
+    d.X_new = dXn.p; d.U_new = dUn.p;
+    const DojoQuadraticCost dc{dQ.p, dR.p, dQf.p, dg.p, cost ? cost->goal_per_problem : 0};
+    TRY(dojo_linesearch_select_dev(s, H, T, cost ? &dc : nullptr, &d, nullptr));
+    return st.finish();      // (no state: the handle's own is left alone)
+}
 
 // ---- reverse mode through closed-loop rollouts (dojo_policy_adjoint.hpp) ----
 int dojo_observation_jacobian_dev(DojoHandle s, const void* z, int32_t n, double* M, void* stream) {

@@ -41,22 +41,32 @@ template <class TIO> struct BoxArgs : Args<TIO> {
     const TIO *lo, *hi;                 // [B][na] (batch-level); either may be null
 };
 
+// the argument record of the fan (dojo_rollout_minimal_fan_dev, include/dojo_hip_linesearch.h): rollout_tracking_kernel<TIO, FanArgs<TIO>>.  The batch is T trials
+// of P problems, environment e = tr P + p: the reference members ubar, xbar, K, kff, lo, hi are [P][..] (the step's rows, P per step) and are read at p = e mod P;
+// X, alpha and u stay per environment.  The law is the clamped one; with lo = hi = null it rounds the same fp64 sum as the plain one.
+template <class TIO> struct FanArgs : BoxArgs<TIO> {
+    int P;
+};
+
 #if defined(__HIPCC__)
 // A_ = BoxArgs<TIO>: the clamped law (BOX; every difference sits behind `if constexpr (BOX)`: the instantiations over Args<TIO> keep their instructions)
+// A_ = FanArgs<TIO>: the clamped law with the reference members read at e mod P (FAN; behind `if constexpr (FAN)`: the four other instantiations keep theirs)
 template <class TIO, class A_ = Args<TIO>>
 __global__ void __launch_bounds__(policy::THREADS) rollout_tracking_kernel(const A_ A) {
-    constexpr bool BOX = std::is_same<A_, BoxArgs<TIO>>::value;
+    constexpr bool FAN = std::is_same<A_, FanArgs<TIO>>::value, BOX = FAN || std::is_same<A_, BoxArgs<TIO>>::value;
     using policy::WAVE;
     const int tid = (int)threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
     const int e = (int)blockIdx.x * policy::ENVS + wave;
     if (e >= A.nenv) return;                                                // (uniform over the wavefront: the DPP sums below see all 64 lanes)
     const size_t env = (size_t)A.env0 + e;
+    size_t ref = env;                                                       // where the reference members are read
+    if constexpr (FAN) ref = (unsigned)(A.env0 + e) % (unsigned)A.P;                // (env0 + e < B fits an int: a 32-bit remainder, not the 64-bit software one)
     const int nu = A.nu, n = 2 * nu;
     const TIO* const x = DJ_GLOBAL_PTR(const TIO, A.X) + env * n;
-    const TIO* const ubar = A.ubar ? DJ_GLOBAL_PTR(const TIO, A.ubar) + env * nu : nullptr;
-    const TIO* const xbar = (A.xbar && A.K) ? DJ_GLOBAL_PTR(const TIO, A.xbar) + env * n : nullptr;
-    const TIO* const K = A.K ? DJ_GLOBAL_PTR(const TIO, A.K) + env * A.na * n : nullptr;
-    const TIO* const kff = A.kff ? DJ_GLOBAL_PTR(const TIO, A.kff) + env * A.na : nullptr;
+    const TIO* const ubar = A.ubar ? DJ_GLOBAL_PTR(const TIO, A.ubar) + ref * nu : nullptr;
+    const TIO* const xbar = (A.xbar && A.K) ? DJ_GLOBAL_PTR(const TIO, A.xbar) + ref * n : nullptr;
+    const TIO* const K = A.K ? DJ_GLOBAL_PTR(const TIO, A.K) + ref * A.na * n : nullptr;
+    const TIO* const kff = A.kff ? DJ_GLOBAL_PTR(const TIO, A.kff) + ref * A.na : nullptr;
     const double alpha = A.alpha ? (double)DJ_GLOBAL_PTR(const TIO, A.alpha)[env] : 1.0;
     TIO* const u = DJ_GLOBAL_PTR(TIO, A.u) + env * nu;
     for (int c = lane; c < nu; c += WAVE)
@@ -75,8 +85,8 @@ __global__ void __launch_bounds__(policy::THREADS) rollout_tracking_kernel(const
             // min(max(Ubar + a, lo), hi) in fp64, rounded once.  The limits are values of the ABI type and rounding is monotone: clamping in front of the rounding
             // gives the bits of clamping behind it, and a driven input is inside [lo, hi] exactly
             double v = (ubar ? (double)ubar[c] : 0.0) + a;
-            if (A.lo) { const double l = (double)DJ_GLOBAL_PTR(const TIO, A.lo)[env * A.na + i]; v = v < l ? l : v; }
-            if (A.hi) { const double h = (double)DJ_GLOBAL_PTR(const TIO, A.hi)[env * A.na + i]; v = v > h ? h : v; }
+            if (A.lo) { const double l = (double)DJ_GLOBAL_PTR(const TIO, A.lo)[ref * A.na + i]; v = v < l ? l : v; }
+            if (A.hi) { const double h = (double)DJ_GLOBAL_PTR(const TIO, A.hi)[ref * A.na + i]; v = v > h ? h : v; }
             if (lane == c % WAVE) u[c] = (TIO)v;
         } else {
             if (lane == c % WAVE) u[c] = (TIO)((ubar ? (double)ubar[c] : 0.0) + a);

@@ -66,6 +66,10 @@ LIMITS_SYMBOLS = list(_LIMITS_SIGNATURES)
 # include/dojo_hip_constraints.h, the fourth: the augmented-Lagrangian terms of stage constraints in the backward pass
 _CONSTRAINT_SIGNATURES = {"dojo_riccati_al_dev": (C.c_int, "pippppppp"), "dojo_riccati_al": (C.c_int, "pipppppp")}
 CONSTRAINT_SYMBOLS = list(_CONSTRAINT_SIGNATURES)
+# include/dojo_hip_linesearch.h, the fifth: the step lengths of a line search side by side -- the fan rollout and the selection kernel
+_LINESEARCH_SIGNATURES = {"dojo_rollout_minimal_fan_dev": (C.c_int, "piippp"), "dojo_rollout_minimal_fan": (C.c_int, "piipp"),
+                          "dojo_linesearch_select_dev": (C.c_int, "piippp"), "dojo_linesearch_select": (C.c_int, "piipp")}
+LINESEARCH_SYMBOLS = list(_LINESEARCH_SIGNATURES)
 
 
 def lib():
@@ -74,7 +78,7 @@ def lib():
         if not os.path.exists(_LIB_PATH):
             raise DojoError("libdojo_hip.so not built (run __graft_entry__.build()); there is no CPU fallback")
         L = C.CDLL(_LIB_PATH)
-        for name, (restype, args) in {**_SIGNATURES, **_TRAJOPT_SIGNATURES, **_LIMITS_SIGNATURES, **_CONSTRAINT_SIGNATURES}.items():
+        for name, (restype, args) in {**_SIGNATURES, **_TRAJOPT_SIGNATURES, **_LIMITS_SIGNATURES, **_CONSTRAINT_SIGNATURES, **_LINESEARCH_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, [_KINDS[k] for k in args]
         _lib = L
@@ -138,6 +142,22 @@ class DojoStageConstraints(C.Structure):
     [nc][na] when shared; Cu may be NULL: zeros), the row weights w and the multiplier estimates y, [H+1][B][nc] each; device pointers for dojo_riccati_al_dev,
     host pointers for dojo_riccati_al"""
     _fields_ = [("Cx", C.c_void_p), ("Cu", C.c_void_p), ("w", C.c_void_p), ("y", C.c_void_p), ("nc", C.c_int32), ("shared", C.c_int32)]
+
+
+class DojoQuadraticCost(C.Structure):
+    """include/dojo_hip_linesearch.h `DojoQuadraticCost`: Q [n][n], R [na][na], Qf [n][n], goal [n] ([P][n] with goal_per_problem) in the handle dtype; device
+    pointers for dojo_linesearch_select_dev, host pointers for dojo_linesearch_select"""
+    _fields_ = [("Q", C.c_void_p), ("R", C.c_void_p), ("Qf", C.c_void_p), ("goal", C.c_void_p), ("goal_per_problem", C.c_int32)]
+
+
+class DojoLineSearch(C.Structure):
+    """include/dojo_hip_linesearch.h `DojoLineSearch`: the T trials of P problems (X, U, status, alpha), the model dV, the flags ok, the trajectory the pass was
+    taken around (Xcur, Ucur, its cost J0), the costs (J_trial: an output with a cost, an input without; J_cur, J_acc) and the selection (choice, alpha_acc,
+    X_new, U_new); device pointers for dojo_linesearch_select_dev, host pointers for dojo_linesearch_select"""
+    _fields_ = [("X", C.c_void_p), ("U", C.c_void_p), ("status", C.c_void_p), ("alpha", C.c_void_p), ("dV", C.c_void_p), ("ok", C.c_void_p),
+                ("Xcur", C.c_void_p), ("Ucur", C.c_void_p), ("J0", C.c_void_p), ("J_trial", C.c_void_p), ("J_cur", C.c_void_p), ("J_acc", C.c_void_p),
+                ("choice", C.c_void_p), ("alpha_acc", C.c_void_p), ("X_new", C.c_void_p), ("U_new", C.c_void_p), ("c1", C.c_double),
+                ("act_off", C.c_int32), ("na", C.c_int32)]
 
 
 MLP_MAX_LAYERS = 4      # DOJO_MLP_MAX_LAYERS
@@ -616,6 +636,58 @@ class BatchedMechanism:
         t = DojoTracking(*map(addr, ins + (X, U, st, A, Bm)), int(act_off), na)
         _chk(lib().dojo_rollout_minimal_box(self.h, H, C.byref(t), C.byref(lim)))
         return (X, U, st, A, Bm) if jacobians else (X, U, st)
+
+    def rollout_minimal_fan(self, T, x0, lo=None, hi=None, steps=None, Ubar=None, Xbar=None, K=None, kff=None, alpha=None, act_off=0, na=None):
+        """dojo_rollout_minimal_fan (host arrays): T trials of P = batch / T problems in one rollout.  x0 [P,n], Ubar [H,P,nu], Xbar [H+1,P,n], K [H,P,na,n],
+        kff [H,P,na], lo / hi (None, a scalar, [na] or [P,na]) are per problem; alpha [T,P] is per environment (e = tr P + p).  lo and hi both None: no limits.
+        -> X [H+1,T P,n], U [H,T P,nu], status [H,T P]: what `rollout_minimal_box` (`rollout_minimal` without limits) gives with the inputs repeated T times."""
+        B, nu, T = self.batch, self.spec.nu, int(T); n = 2 * nu
+        P = B // T if T >= 1 and B % T == 0 else B          # (a T the library refuses: the arrays' shapes are then not looked at here)
+        na = int(nu - act_off if na is None else na)
+        Hs = [np.shape(a)[0] for a in (Ubar, K, kff) if a is not None] + ([int(steps)] if steps is not None else [])
+        if not Hs:
+            raise ValueError("rollout_minimal_fan needs the horizon: Ubar, K, kff or steps")
+        H = int(Hs[0])
+        if any(int(h) != H for h in Hs):
+            raise ValueError("Ubar, K, kff and steps disagree about the horizon: %s" % Hs)
+        opt = lambda a, shape: None if a is None else self._arr(a, shape)
+        ins = (self._arr(x0, (P, n)), opt(Ubar, (H, P, nu)), opt(Xbar, (H + 1, P, n)), opt(K, (H, P, na, n)), opt(kff, (H, P, na)), opt(alpha, (B // P, P)))
+        X = np.empty((H + 1, B, n), self.np_dtype); U = np.empty((H, B, nu), self.np_dtype); st = np.empty((H, B), np.int32)
+        lims = [None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=self.np_dtype), (P, na))) for a in (lo, hi)]
+        lim = DojoControlLimits(addr(lims[0]), addr(lims[1]))
+        t = DojoTracking(*map(addr, ins + (X, U, st, None, None)), int(act_off), na)
+        _chk(lib().dojo_rollout_minimal_fan(self.h, H, T, C.byref(t), None if lo is None and hi is None else C.byref(lim)))
+        return X, U, st
+
+    def linesearch_select(self, T, X, U, alpha, dV, Xcur, Ucur, cost=None, status=None, ok=None, J0=None, J_trial=None, c1=1e-4, act_off=0, na=None, gather=True):
+        """dojo_linesearch_select (host arrays) on the T trials X [H+1,T P,n], U [H,T P,nu], status [H,T P] of a fan: the first trial tr of every problem with
+        ok != 0, no failed step and J_tr <= J0 + c1 (a dV[0] + a^2 dV[1]), a = alpha[tr, p].  cost = (Q, R, Qf, goal) (goal [n] or [P,n]): the costs are computed on
+        the device in fp64 (J0 from Xcur, Ucur unless given); cost None: J_trial [T,P] and J0 [P] are the caller's.
+        -> dict: choice [P] int32 (-1: none), alpha [P], J_trial [T,P], J_cur [P], J_acc [P] (float64) and, with gather, X [H+1,P,n], U [H,P,nu]: the accepted
+        trial's columns, or Xcur / Ucur."""
+        B, nu, T = self.batch, self.spec.nu, int(T); n = 2 * nu
+        P = B // T if T >= 1 and B % T == 0 else B
+        na = int(nu - act_off if na is None else na)
+        H = int(np.shape(U)[0])
+        X = self._arr(X, (H + 1, B, n)); U = self._arr(U, (H, B, nu)); alpha = self._arr(alpha, (B // P, P)); dV = self._arr(dV, (P, 2))
+        Xcur = self._arr(Xcur, (H + 1, P, n)); Ucur = self._arr(Ucur, (H, P, nu))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32); ok = None if ok is None else np.ascontiguousarray(ok, dtype=np.int32)
+        J0 = None if J0 is None else np.ascontiguousarray(J0, dtype=np.float64)
+        J_trial = np.empty((B // P, P), np.float64) if cost is not None else None if J_trial is None else np.array(J_trial, dtype=np.float64, order="C")
+        J_cur = np.empty(P, np.float64); J_acc = np.empty(P, np.float64); choice = np.empty(P, np.int32); a_acc = np.empty(P, self.np_dtype)
+        Xn = np.empty((H + 1, P, n), self.np_dtype) if gather else None; Un = np.empty((H, P, nu), self.np_dtype) if gather else None
+        qc = None
+        if cost is not None:
+            Q, R, Qf, goal = cost
+            per = np.ndim(goal) == 2
+            keep = (self._arr(Q, (n, n)), self._arr(R, (na, na)), self._arr(Qf, (n, n)), self._arr(goal, (P, n) if per else (n,)))
+            qc = DojoQuadraticCost(*map(addr, keep), int(per))
+        ls = DojoLineSearch(*map(addr, (X, U, status, alpha, dV, ok, Xcur, Ucur, J0, J_trial, J_cur, J_acc, choice, a_acc, Xn, Un)), float(c1), int(act_off), na)
+        _chk(lib().dojo_linesearch_select(self.h, H, T, None if qc is None else C.byref(qc), C.byref(ls)))
+        out = {"choice": choice, "alpha": a_acc, "J_trial": J_trial, "J_cur": J_cur, "J_acc": J_acc}
+        if gather:
+            out.update(X=Xn, U=Un)
+        return out
 
     def rollout_policy(self, z0, W, steps, bias=None, mean=None, scale=None, U_ff=None, act_off=0, contact_forces=False, contact_init=0):
         """Closed-loop rollout (dojo_rollout_policy): simulate! with the affine feedback policy u_k = U_ff[k] + E (bias + W ((o_k - mean) .* scale))

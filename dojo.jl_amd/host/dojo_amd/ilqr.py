@@ -12,11 +12,15 @@ the same loop for B environments at once -- one trajectory, one regularisation a
     res = solve_limited(gm, x0, U0, cost, 10, lo, hi)                                          # control-limited iLQR, lo <= u[act] <= hi
     K, kff, dV, fail, active, qp_iters = riccati_al(gm, A, Bm, lx, lu, lxx, luu, Cx, w, y)     # ONE launch of dojo_riccati_al_dev: the AL terms of constraint rows added in the kernel
     res = solve_constrained(gm, x0, U0, cost, GoalConstraint(x_goal), iters=4, outer=5)        # the augmented-Lagrangian loop: a terminal goal, state bounds
+    Xt, Ut, st = rollout_minimal_fan(gm_trials, T, x0, Ubar, Xbar, K, kff, alpha, lo, hi)      # ONE call of dojo_rollout_minimal_fan_dev: T step lengths of P problems as T P environments
+    sel = linesearch_select(gm_trials, T, Xt, Ut, st, alpha, dV, Xcur, Ucur, cost)             # ONE launch of dojo_linesearch_select_dev: costs, Armijo test, first accepted trial, gather
+    res = solve_side_by_side(gm, gm_trials, x0, U0, cost, 10, lo, hi)                          # solve / solve_limited with the line search side by side, no read-back
 
-Everything is enqueued on torch's current stream.  The driver reads one flag per trial step length (have all environments accepted?) and nothing else.
+Everything is enqueued on torch's current stream.  The drivers solve, solve_limited and solve_constrained read one flag per trial step length (have all
+environments accepted?) and nothing else; solve_side_by_side reads nothing (include/dojo_hip_linesearch.h: it pays when an iteration needs two or more step lengths: DESIGN.md 5l has the measurements).
 Not here (include/dojo_hip.h, "Batched iLQR"; include/dojo_hip_trajopt.h): costs shared across the batch, second-order dynamics terms, second-order constraint
 terms and constraints evaluated on the device (control limits: include/dojo_hip_limits.h, solve_limited; other constraints: include/dojo_hip_constraints.h,
-solve_constrained), running the step lengths of a line search side by side, kinematic loops."""
+solve_constrained), constraints in the side-by-side driver, kinematic loops."""
 import ctypes as C
 
 import torch
@@ -334,6 +338,126 @@ def _solve(gm, x0, U0, cost, iters, act_off, na, c1, alphas, mu_init, mu_min, mu
         al.mu = mu
     X = replay(gm, x0, U)
     hist["J"].append(cost.value(X, U[:, :, act]))
+    return {"X": X, "U": U, **{k: torch.stack(v) for k, v in hist.items()}}
+
+
+# ---- the line search side by side (include/dojo_hip_linesearch.h): T step lengths of P problems as ONE rollout of T P environments, ONE selection kernel ----
+def rollout_minimal_fan(gm_trials, T, x0, Ubar, Xbar, K, kff, alpha, lo=None, hi=None, act_off=0, na=None):
+    """dojo_rollout_minimal_fan_dev on device tensors.  gm_trials: a handle of batch T P; environment tr P + p is trial tr of problem p.  x0 [P,n], Ubar [H,P,nu],
+    Xbar [H+1,P,n], K [H,P,na,n], kff [H,P,na] (Xbar, K, kff may be None) and lo, hi ([na] or [P,na], a number or None; both None: no limits) are per problem and
+    are read at e mod P; alpha [T,P] is per environment.  -> X [H+1,T P,n], U [H,T P,nu], status [H,T P] int32: rollout_minimal_box's (rollout_minimal's without
+    limits) on the inputs repeated T times, bit for bit."""
+    B, nu, T = gm_trials.batch, gm_trials.spec.nu, int(T); n, dt = 2 * nu, _dtype(gm_trials)
+    if T < 1 or B % T:
+        raise ValueError("the batch of gm_trials (%d) must be T (%d) trials of P problems" % (B, T))
+    if Ubar.dim() != 3:
+        raise ValueError("Ubar must be [H, P, nu]")
+    P, H = B // T, int(Ubar.shape[0]); na = int(nu - act_off if na is None else na)
+    x0 = _want(x0, "x0", dt, (P, n)); Ubar = _want(Ubar, "Ubar", dt, (H, P, nu)); Xbar = _want(Xbar, "Xbar", dt, (H + 1, P, n))
+    K = _want(K, "K", dt, (H, P, na, n)); kff = _want(kff, "kff", dt, (H, P, na)); alpha = _want(alpha, "alpha", dt, (T, P))
+    dev = x0.device
+    X = torch.empty((H + 1, B, n), dtype=dt, device=dev); U = torch.empty((H, B, nu), dtype=dt, device=dev)
+    status = torch.empty((H, B), dtype=torch.int32, device=dev)
+    t = api.DojoTracking(*map(api.addr, (x0, Ubar, Xbar, K, kff, alpha, X, U, status, None, None)), int(act_off), na)
+    limited = lo is not None or hi is not None
+    if limited:
+        one = lambda v, none: torch.as_tensor(none if v is None else v, dtype=dt, device=dev).expand(P, na).contiguous()
+        lo, hi = one(lo, float("-inf")), one(hi, float("inf"))
+    lim = api.DojoControlLimits(api.addr(lo), api.addr(hi))
+    api._chk(api.lib().dojo_rollout_minimal_fan_dev(gm_trials.h, H, T, C.byref(t), C.byref(lim) if limited else None, api.torch_stream(dev)))
+    return X, U, status
+
+
+def linesearch_select(gm_trials, T, X, U, status, alpha, dV, Xcur, Ucur, cost=None, ok=None, J0=None, J_trial=None, c1=1e-4, act_off=0, na=None, gather=True):
+    """dojo_linesearch_select_dev on device tensors: of the T trials X [H+1,T P,n], U [H,T P,nu], status [H,T P] (None: all solved) of every problem the FIRST with
+    ok[p] != 0 (ok [P] int32 or None), no failed step and J_tr <= J0 + c1 (a dV[p,0] + a^2 dV[p,1]), a = alpha[tr,p].  cost: a QuadraticCost -- the costs are
+    evaluated in the kernel in fp64 (J0 too, from Xcur [H+1,P,n], Ucur [H,P,nu], unless given); None: J_trial [T,P] and J0 [P] (float64) are the caller's (any
+    cost object, the merit of an augmented Lagrangian).  -> dict: choice [P] int32 (-1: none), alpha [P] (0: none), J_trial [T,P], J_cur [P], J_acc [P] (float64)
+    and, with gather, X [H+1,P,n], U [H,P,nu]: exact copies of the accepted trial's columns, or of Xcur, Ucur.  One launch, nothing is read back."""
+    B, nu, T = gm_trials.batch, gm_trials.spec.nu, int(T); n, dt = 2 * nu, _dtype(gm_trials)
+    if T < 1 or B % T:
+        raise ValueError("the batch of gm_trials (%d) must be T (%d) trials of P problems" % (B, T))
+    P, H = B // T, int(U.shape[0]); na = int(nu - act_off if na is None else na)
+    X = _want(X, "X", dt, (H + 1, B, n)); U = _want(U, "U", dt, (H, B, nu)); status = _want(status, "status", torch.int32, (H, B))
+    alpha = _want(alpha, "alpha", dt, (T, P)); dV = _want(dV, "dV", dt, (P, 2)); ok = _want(ok, "ok", torch.int32, (P,))
+    Xcur = _want(Xcur, "Xcur", dt, (H + 1, P, n)); Ucur = _want(Ucur, "Ucur", dt, (H, P, nu)); J0 = _want(J0, "J0", torch.float64, (P,))
+    dev = X.device
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    J_trial = f64(T, P) if cost is not None else _want(J_trial, "J_trial", torch.float64, (T, P))
+    J_cur, J_acc = f64(P), f64(P)
+    choice = torch.empty(P, dtype=torch.int32, device=dev); a_acc = torch.empty(P, dtype=dt, device=dev)
+    Xn = torch.empty((H + 1, P, n), dtype=dt, device=dev) if gather else None; Un = torch.empty((H, P, nu), dtype=dt, device=dev) if gather else None
+    qc = None
+    if cost is not None:
+        per = cost.g.dim() == 2
+        keep = (_want(cost.Q, "Q", dt, (n, n)), _want(cost.R, "R", dt, (na, na)), _want(cost.Qf, "Qf", dt, (n, n)), _want(cost.g, "x_goal", dt, (P, n) if per else (n,)))
+        qc = api.DojoQuadraticCost(*map(api.addr, keep), int(per))
+    ls = api.DojoLineSearch(*map(api.addr, (X, U, status, alpha, dV, ok, Xcur, Ucur, J0, J_trial, J_cur, J_acc, choice, a_acc, Xn, Un)), float(c1), int(act_off), na)
+    api._chk(api.lib().dojo_linesearch_select_dev(gm_trials.h, H, T, None if qc is None else C.byref(qc), C.byref(ls), api.torch_stream(dev)))
+    out = {"choice": choice, "alpha": a_acc, "J_trial": J_trial, "J_cur": J_cur, "J_acc": J_acc}
+    if gather:
+        out.update(X=Xn, U=Un)
+    return out
+
+
+def solve_side_by_side(gm, gm_trials, x0, U0, cost, iters, lo=None, hi=None, act_off=0, na=None, c1=1e-4,
+                       alphas=(1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625, 0.0078125), mu_init=0.0, mu_min=1e-6, mu_grow=10.0, mu_shrink=0.1):
+    """`solve` (lo and hi None) / `solve_limited` with the step lengths of the line search side by side.  gm: a handle of batch P for the linearization and the
+    backward pass; gm_trials: a handle of the same mechanism and dtype with batch len(alphas) P for the trials; alphas: numbers, or a device tensor [T] or [T,P] (a
+    ladder per problem).  Each iteration:
+      1. linearize_rollout on gm;  2. cost.quadratize;  3. riccati (riccati_box with limits) on gm;
+      4. ONE fan rollout of all step lengths on gm_trials (rollout_minimal_fan);
+      5. ONE selection (linesearch_select): a QuadraticCost is evaluated by the kernel in fp64, any other cost object by cost.value on the [H+1,T P,n] trials and
+         handed over as J_trial; the first acceptable step length of every problem wins, as in `solve`;
+      6. `solve`'s update of mu from choice >= 0 (torch.where).
+    The loop reads nothing back from the device: all of it is enqueued on torch's current stream.
+    -> solve's dict (J, and the decisions, are fp64 whatever the handle dtype) plus choice [iters,P] int32 and J_trial [iters,T,P]; with limits also active."""
+    P, nu = gm.batch, gm.spec.nu; dt = _dtype(gm)
+    T = int(alphas.shape[0]) if torch.is_tensor(alphas) else len(alphas)
+    if gm_trials.batch != T * P or gm_trials.dtype_code != gm.dtype_code:
+        raise ValueError("gm_trials must have batch len(alphas) * gm.batch = %d and gm's dtype" % (T * P))
+    if int(iters) < 1:
+        raise ValueError("iters must be >= 1")
+    na = int(nu - act_off if na is None else na)
+    dev = x0.device
+    act = slice(act_off, act_off + na)
+    U = U0.clone()
+    limited = lo is not None or hi is not None
+    hist = {"J": [], "a": [], "mu": [], "fail": [], "dV": [], "choice": [], "J_trial": []}
+    if limited:
+        lo, hi = _limits(gm, lo, hi, na, dev)
+        U[:, :, act] = torch.clamp(U[:, :, act], lo, hi)
+        hist["active"] = []
+    mu = torch.full((P,), float(mu_init), dtype=dt, device=dev)
+    if torch.is_tensor(alphas):          # [T] or [T,P] on the device: nothing is uploaded
+        alpha = _want(alphas if alphas.dim() == 2 else alphas[:, None].expand(T, P), "alphas", dt, (T, P))
+    else:
+        alpha = torch.tensor([float(a) for a in alphas], dtype=dt, device=dev)[:, None].expand(T, P).contiguous()
+    device_cost = isinstance(cost, QuadraticCost)
+    for _ in range(int(iters)):
+        X, A, Bm, status = linearize_rollout(gm, x0, U)
+        lx, lu, lxx, luu, lux = cost.quadratize(X, U[:, :, act])
+        if limited:
+            K, kff, dV, fail, active, _ = riccati_box(gm, A, Bm, lx, lu, lxx, luu, U, lo, hi, lux, mu, status, act_off, na)
+            hist["active"].append(active)
+        else:
+            K, kff, dV, fail = riccati(gm, A, Bm, lx, lu, lxx, luu, lux, mu, status, act_off, na)
+        ok = ((status == 0).all(0) & (fail == 0)).to(torch.int32)
+        Xt, Ut, st = rollout_minimal_fan(gm_trials, T, x0, U, X, K, kff, alpha, lo if limited else None, hi if limited else None, act_off, na)
+        if device_cost:
+            sel = linesearch_select(gm_trials, T, Xt, Ut, st, alpha, dV, X, U, cost, ok, None, None, c1, act_off, na)
+        else:
+            J0 = cost.value(X, U[:, :, act]).to(torch.float64)
+            Jt = cost.value(Xt, Ut[:, :, act]).to(torch.float64).view(T, P).contiguous()
+            sel = linesearch_select(gm_trials, T, Xt, Ut, st, alpha, dV, X, U, None, ok, J0, Jt, c1, act_off, na)
+        accepted = sel["choice"] >= 0
+        hist["J"].append(sel["J_cur"]); hist["a"].append(sel["alpha"]); hist["mu"].append(mu.clone()); hist["fail"].append(fail); hist["dV"].append(dV)
+        hist["choice"].append(sel["choice"]); hist["J_trial"].append(sel["J_trial"])
+        shrunk = mu * mu_shrink
+        mu = torch.where(accepted, torch.where(shrunk < mu_min, torch.zeros_like(mu), shrunk), torch.clamp(mu * mu_grow, min=mu_min))
+        U = sel["U"]
+    X = replay(gm, x0, U)
+    hist["J"].append(cost.value(X, U[:, :, act]).to(torch.float64))
     return {"X": X, "U": U, **{k: torch.stack(v) for k, v in hist.items()}}
 
 

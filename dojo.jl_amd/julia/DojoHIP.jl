@@ -400,6 +400,72 @@ function rollout_minimal_box(bm::BatchedMechanism{T}, x0::Matrix{T}, Ubar::Array
     return jacobians ? (X, U, status, A, Bm) : (X, U, status)
 end
 
+"mirror of `DojoQuadraticCost` (include/dojo_hip_linesearch.h): four pointers, one Int32"
+struct DojoQuadraticCost
+    Q::Ptr{Cvoid}; R::Ptr{Cvoid}; Qf::Ptr{Cvoid}; goal::Ptr{Cvoid}
+    goal_per_problem::Int32
+end
+
+"mirror of `DojoLineSearch` (include/dojo_hip_linesearch.h): sixteen pointers, one Float64, two Int32"
+struct DojoLineSearch
+    X::Ptr{Cvoid}; U::Ptr{Cvoid}; status::Ptr{Cvoid}; alpha::Ptr{Cvoid}; dV::Ptr{Cvoid}; ok::Ptr{Cvoid}; Xcur::Ptr{Cvoid}; Ucur::Ptr{Cvoid}
+    J0::Ptr{Cvoid}; J_trial::Ptr{Cvoid}; J_cur::Ptr{Cvoid}; J_acc::Ptr{Cvoid}; choice::Ptr{Cvoid}; alpha_acc::Ptr{Cvoid}; X_new::Ptr{Cvoid}; U_new::Ptr{Cvoid}
+    c1::Float64; act_off::Int32; na::Int32
+end
+
+"""
+The step lengths of a line search side by side (include/dojo_hip_linesearch.h): dojo_rollout_minimal_fan.  The handle has batch B = T P; environment
+(tr - 1) P + p is trial tr of problem p.  x0[n, P], Ubar[nu, P, H], Xbar[n, P, H + 1], K[n, na, P, H], kff[na, P, H], lo[na, P], hi[na, P] are per problem,
+alpha[P, T] per environment.  lo and hi `nothing`: no limits.  -> X[n, B, H + 1], U[nu, B, H], status[B, H]: `rollout_minimal_box`'s (`rollout_minimal`'s
+without limits) on the inputs repeated T times, bit for bit.
+"""
+function rollout_minimal_fan(bm::BatchedMechanism{T}, trials::Integer, x0::Matrix{T}, Ubar::Array{T,3}; lo::Union{Nothing,Matrix{T}}=nothing,
+                             hi::Union{Nothing,Matrix{T}}=nothing, Xbar::Union{Nothing,Array{T,3}}=nothing, K::Union{Nothing,Array{T,4}}=nothing,
+                             kff::Union{Nothing,Array{T,3}}=nothing, alpha::Union{Nothing,Matrix{T}}=nothing, act_off::Integer=0, na::Integer=bm.nu - act_off) where T
+    H = size(Ubar, 3); n = 2 * bm.nu
+    X = Array{T}(undef, n, bm.batch, H + 1); U = Array{T}(undef, bm.nu, bm.batch, H); status = Matrix{Int32}(undef, bm.batch, H)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    limited = lo !== nothing || hi !== nothing
+    GC.@preserve x0 Ubar Xbar K kff alpha X U status lo hi begin
+        t = Ref(DojoTracking(p(x0), p(Ubar), p(Xbar), p(K), p(kff), p(alpha), p(X), p(U), p(status), Ptr{Cvoid}(C_NULL), Ptr{Cvoid}(C_NULL), Int32(act_off), Int32(na)))
+        lim = Ref(DojoControlLimits(p(lo), p(hi)))
+        GC.@preserve lim begin
+            limp = limited ? Base.unsafe_convert(Ptr{DojoControlLimits}, lim) : Ptr{DojoControlLimits}(C_NULL)
+            check(@ccall $(fn(:dojo_rollout_minimal_fan))(bm.handle::Ptr{Cvoid}, Int32(H)::Int32, Int32(trials)::Int32, t::Ptr{DojoTracking}, limp::Ptr{DojoControlLimits})::Cint)
+        end
+    end
+    return X, U, status
+end
+
+"""
+The selection of a side-by-side line search (include/dojo_hip_linesearch.h): dojo_linesearch_select on the trials X[n, B, H + 1], U[nu, B, H], status[B, H] of
+`rollout_minimal_fan`.  alpha[P, T], dV[2, P] (`riccati`'s), Xcur[n, P, H + 1], Ucur[nu, P, H]: the trajectory the pass was taken around.  `cost` = (Q, R, Qf, goal)
+(Q and Qf [n, n] and R [na, na], transposed as every matrix here; goal[n] or goal[n, P]): the costs are evaluated on the device in Float64; `nothing`: J_trial[P, T]
+and J0[P] are the caller's.  ok[P] (Int32, 0: the problem accepts nothing) and status may be `nothing`.
+-> choice[P] (Int32, 0-based trial or -1), alpha_acc[P], J_trial[P, T], J_cur[P], J_acc[P], X_new[n, P, H + 1], U_new[nu, P, H].
+"""
+function linesearch_select(bm::BatchedMechanism{T}, trials::Integer, X::Array{T,3}, U::Array{T,3}, alpha::Matrix{T}, dV::Matrix{T}, Xcur::Array{T,3}, Ucur::Array{T,3};
+                           cost=nothing, status::Union{Nothing,Matrix{Int32}}=nothing, ok::Union{Nothing,Vector{Int32}}=nothing,
+                           J0::Union{Nothing,Vector{Float64}}=nothing, J_trial::Union{Nothing,Matrix{Float64}}=nothing, c1::Real=1e-4, act_off::Integer=0,
+                           na::Integer=bm.nu - act_off) where T
+    H = size(U, 3); n = 2 * bm.nu; P = div(bm.batch, trials)
+    Jt = cost === nothing ? J_trial : Matrix{Float64}(undef, P, trials)
+    J_cur = Vector{Float64}(undef, P); J_acc = Vector{Float64}(undef, P); choice = Vector{Int32}(undef, P); alpha_acc = Vector{T}(undef, P)
+    X_new = Array{T}(undef, n, P, H + 1); U_new = Array{T}(undef, bm.nu, P, H)
+    p(a) = a === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(a))
+    GC.@preserve X U status alpha dV ok Xcur Ucur J0 Jt J_cur J_acc choice alpha_acc X_new U_new cost begin
+        ls = Ref(DojoLineSearch(p(X), p(U), p(status), p(alpha), p(dV), p(ok), p(Xcur), p(Ucur), p(J0), p(Jt), p(J_cur), p(J_acc), p(choice), p(alpha_acc), p(X_new), p(U_new),
+                                Float64(c1), Int32(act_off), Int32(na)))
+        qc = Ref(cost === nothing ? DojoQuadraticCost(C_NULL, C_NULL, C_NULL, C_NULL, Int32(0)) :
+                 DojoQuadraticCost(p(cost[1]), p(cost[2]), p(cost[3]), p(cost[4]), Int32(ndims(cost[4]) == 2)))
+        GC.@preserve qc begin
+            qcp = cost === nothing ? Ptr{DojoQuadraticCost}(C_NULL) : Base.unsafe_convert(Ptr{DojoQuadraticCost}, qc)
+            check(@ccall $(fn(:dojo_linesearch_select))(bm.handle::Ptr{Cvoid}, Int32(H)::Int32, Int32(trials)::Int32, qcp::Ptr{DojoQuadraticCost}, ls::Ptr{DojoLineSearch})::Cint)
+        end
+    end
+    return choice, alpha_acc, Jt, J_cur, J_acc, X_new, U_new
+end
+
 """
 reverse mode through a closed-loop rollout (no counterpart in Dojo.jl): the rollout of `rollout_policy` (without contact observations) and the
 gradient of a trajectory loss w.r.t. the policy, the feed-forward term and the initial state; the recorded Jacobians stay on the device.

@@ -23,7 +23,12 @@ include/dojo_hip_constraints.h): a terminal goal constraint x_H = 0 with a modes
 [iterations] / 4 inner ones each; the backward pass is ONE launch of dojo_riccati_al_dev, which adds the constraint's terms to the step's model inside the kernel.
 The terminal violation max |x_H| is printed per outer iteration next to that of `solve` under the same cost and as many iterations.  --limit F combines with it.
 
-    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations] [--fused] [--limit F] [--goal]     # needs a GPU: libdojo_hip has no CPU fallback
+With --side-by-side the line search runs side by side (ilqr.solve_side_by_side, include/dojo_hip_linesearch.h): a second handle of 8 x batch environments rolls
+out all eight step lengths of every cartpole in ONE call of dojo_rollout_minimal_fan_dev, and ONE launch of dojo_linesearch_select_dev evaluates the costs, applies
+the acceptance test and gathers the first accepted trial; the host reads nothing back during the iterations.  It pays when an iteration needs two or more step lengths; where every cartpole accepts the full step it costs more than the loop it replaces (DESIGN.md 5l has the measurements).
+--limit F combines with it; --goal does not.
+
+    python examples/cartpole_ilqr_device.py [batch] [horizon] [iterations] [--fused] [--limit F] [--goal] [--side-by-side]     # needs a GPU: libdojo_hip has no CPU fallback
 """
 import os
 import sys
@@ -42,6 +47,9 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     fused = "--fused" in argv; argv = [a for a in argv if a != "--fused"]
     goal = "--goal" in argv; argv = [a for a in argv if a != "--goal"]
+    side = "--side-by-side" in argv; argv = [a for a in argv if a != "--side-by-side"]
+    if side and goal:
+        raise SystemExit("--side-by-side does not combine with --goal (constraints in the side-by-side driver are not built)")
     limit = None
     if "--limit" in argv:
         i = argv.index("--limit"); limit = float(argv[i + 1]); del argv[i:i + 2]
@@ -62,7 +70,13 @@ def main(argv=None):
                               x_goal=torch.zeros(4, dtype=dt, device=dev))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    if goal:
+    if side:
+        trials = 8                                     # the step lengths 1, 1/2, .. 1/128 of ilqr.solve
+        gmt = api.BatchedMechanism(spec, trials * B, dtype="f64", opts=d.SolverOptions(rtol=1e-8, btol=1e-8))
+        lim = (None, None) if limit is None else (-limit, limit)
+        res = ilqr.solve_side_by_side(gm, gmt, x0, U0, cost, iters, lim[0], lim[1], act_off=0, na=1)
+        gmt.close()
+    elif goal:
         outer = 4; inner = max(1, iters // outer)
         lim = {} if limit is None else {"lo": -limit, "hi": limit}
         res = ilqr.solve_constrained(gm, x0, U0, cost, ilqr.GoalConstraint(torch.zeros(4, dtype=dt, device=dev)), inner, outer, act_off=0, na=1, fused=fused, **lim)
@@ -91,7 +105,10 @@ def main(argv=None):
             print("outer %d: terminal violation max |x_H - goal|  min %.3e  median %.3e  max %.3e%s" % (o, viol[o].min(), np.median(viol[o]), viol[o].max(), "   (the start)" if o == 0 else ""))
         print("without the constraint, same cost, %d iterations:    min %.3e  median %.3e  max %.3e" % (inner * outer, dist.min(), np.median(dist), dist.max()))
         print("rho %.1e, largest |lambda| %.3e" % (float(res["rho"].max()), float(res["lam"].abs().max())))
-    print("%d environments x %d steps x %d iterations in %.2f s%s" % (B, H, iters, el, " (fused rollouts)" if fused else ""))
+    if side:
+        ch = res["choice"].cpu().numpy()
+        print("line search side by side: accepted trial per iteration, mean %.2f, largest %d, none %d of %d" % (ch[ch >= 0].mean() if (ch >= 0).any() else -1, ch.max(), int((ch < 0).sum()), ch.size))
+    print("%d environments x %d steps x %d iterations in %.2f s%s" % (B, H, iters, el, " (line search side by side)" if side else " (fused rollouts)" if fused else ""))
     assert goal or (J[-1] <= J[0]).all()                # (under a goal constraint the cost alone may rise: the merit is what falls)
     gm.close()
     return res

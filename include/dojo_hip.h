@@ -698,7 +698,9 @@ int  dojo_rollout_mlp_gradients(DojoHandle h, const void* z0, const DojoMlpPolic
  * n + na > 110 (the accumulators of the lower triangle of [Qxx Qxu; Qux Quu] live in registers), na > 64 -- with the byte count in the text.
  * Not part of it: the forward pass and the linearization along it (each is one call of the rollout in minimal coordinates of include/dojo_hip_trajopt.h,
  * whose controller takes K and kff as they are written here), control limits (the box variant of this pass and of that rollout: include/dojo_hip_limits.h),
- * costs shared across the batch or given as diagonals, second-order dynamics terms (DDP), constraints (augmented Lagrangian), kinematic loops. */
+ * costs shared across the batch or given as diagonals, second-order dynamics terms (DDP), constraints (augmented Lagrangian), kinematic loops.
+ * (The line search that follows this pass -- all its step lengths as one rollout, the acceptance test as one kernel that reads this pass's dV --:
+ * include/dojo_hip_linesearch.h.) */
 typedef struct DojoRiccati {
     const void* A;      /* [H][B][n][n]   row-major, jx of dojo_minimal_gradients_dev per step */
     const void* Bm;     /* [H][B][n][nu]  row-major, ju ...; columns act_off .. act_off+na-1 are read */

@@ -56,7 +56,8 @@ typedef struct DojoStageConstraints {
  * with DOJO_ERR_INVALID.
  *
  * Not part of it: second-order constraint terms, constraints evaluated on the device, per-row penalties (the caller's w already is one), a warm start of the
- * multipliers across calls, running the step lengths of a line search side by side.
+ * multipliers across calls, running the step lengths of a line search side by side.  (The last came later, as entries of their own:
+ * include/dojo_hip_linesearch.h; its mode without a cost takes this loop's merit.)
  */
 int dojo_riccati_al_dev(DojoHandle h, int32_t H, const DojoRiccati* r, const DojoControlLimits* lim /* NULL: no limits */,
                         const void* U /* [H][B][nu]; may be NULL iff lim is NULL */, const DojoStageConstraints* con,

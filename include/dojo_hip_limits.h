@@ -71,6 +71,7 @@ int dojo_riccati_box(DojoHandle h, int32_t H, const DojoRiccati* r, const DojoCo
  * Refused: whatever dojo_rollout_minimal_dev refuses (with this entry's name); DOJO_ERR_INVALID: NULL lim; the host entry also lo > hi and NaN limits.
  *
  * Not part of it: state constraints, time-varying limits, a warm start of the QP from the previous iteration's clamped set, limits on inputs that are not driven.
+ * (The clamped law over T step lengths of a line search at once: include/dojo_hip_linesearch.h.)
  */
 int dojo_rollout_minimal_box_dev(DojoHandle h, int32_t H, const DojoTracking* t, const DojoControlLimits* lim, void* stream);
 int dojo_rollout_minimal_box(DojoHandle h, int32_t H, const DojoTracking* t, const DojoControlLimits* lim);

@@ -44,7 +44,8 @@ extern "C" {
  * or act_off + na > nu; exactly one of A, Bm given.  DOJO_ERR_UNSUPPORTED: a mechanism with a kinematic loop (as dojo_step_minimal_dev); with A, whatever the
  * recording rollouts refuse.  (The controller kernel keeps nothing in LDS: no shape is refused for its size.)
  * Not part of it: control limits / clamping (dojo_rollout_minimal_box_dev of include/dojo_hip_limits.h has them), costs on the device, running all step lengths of a line search side by side, reverse mode through the tracking
- * controller, contact observations, kinematic loops. */
+ * controller, contact observations, kinematic loops.  (The quadratic cost of a line search's trials and the step lengths side by side came later, as entries of
+ * their own: include/dojo_hip_linesearch.h.) */
 typedef struct DojoTracking {
     const void *x0, *Ubar, *Xbar, *K, *kff, *alpha;   /* [B][n] (required), [H][B][nu], [H+1][B][n], [H][B][na][n], [H][B][na], [B]; each of the last five may be NULL */
     void *X, *U_out;                                  /* [H+1][B][n], [H][B][nu]: required */
